@@ -16,7 +16,10 @@ of the path: an all-reduce of per-rank partial sums).  Members are sharded over 
 data-path collective (weak scaling: --members per GPU is fixed; 128/GPU = BASELINE configs[2]'s
 1024 members on 8 GPUs).  Rank 0 prints ONE JSON line.
 
-Auxiliary legs on one GPU (same JSON line), each with its OWN fixed protocol, independent of --steps:
+A plain run sets up, warms up, times the K steps and prints the headline line (with the roofline of the HIP events
+inside the timed region).  --dump-outputs DIR then writes what the timed loop computed in its last step (dump_outputs).
+
+--full adds the auxiliary legs on one GPU (same JSON line), each with its OWN fixed protocol, independent of --steps:
 `steady` (the headline workload under SURVEY ยง8d's protocol: 100 warm-up + 2,000 timed steps, 8 snapshots and 2 status
 checks inside, >= 200 event-bracketed launches of the roofline kernel), `exact_f32` (the same workload on the f32 matrix
 cores), `b1` (configs[1]: one member), `b1024` (configs[2] WHOLE on one GPU: 1024 members, the one-workgroup-per-member
@@ -44,6 +47,7 @@ MAC_PER_PIXEL = [12800, 204800, 18432, 9216, 9216, 9216, 9216, 576]   # SURVEY ย
 F32_MFMA_PEAK_TFLOPS = 157.3                                           # MI355X_MICROARCH.md, dense f32 matrix
 F16_MFMA_PEAK_TFLOPS = 2500.0                                          # dense f16/bf16, same guide
 HBM_PEAK_GBS = 8000.0                                                  # HBM3E, same guide
+DUMP_BYTES = 64_000_000                                                # --dump-outputs: at most this much in all
 PRECISIONS = {'f32': 0, 'f16x3': 3}
 JET = dict(rek=7e-8, delta=0.1, beta=1e-11)                            # tools/parameters.py:26-27,37
 
@@ -136,6 +140,23 @@ class OnlineLoop:
                 self.nstatus += 1
             if tc % self.snap_every == 0:
                 self.snapshot()
+
+
+def dump_outputs(eng, first, outdir):
+    """--dump-outputs: the state the timed loop leaves after its last step, as its caller receives it (float64, members x
+    layers x N x N): PV `q`, velocities `u` / `v`, streamfunction `psi` and `s`, the generator's subgrid forcing of that
+    step.  An ensemble too large for DUMP_BYTES is written as a fixed seeded sample of its members; `members` holds their
+    global ids (float64)."""
+    from pyqg_generative_amd import _lib
+    fields = {'q': _lib.F_Q, 'u': _lib.F_U, 'v': _lib.F_V, 'psi': _lib.F_P, 's': _lib.F_S}
+    B, N = eng.B, eng.N
+    keep = min(B, (DUMP_BYTES - 8 * B - 4096) // (len(fields) * 2 * N * N * 8))      # 4096: the .npy headers
+    idx = np.arange(B) if keep == B else np.sort(np.random.RandomState(0).choice(B, keep, replace=False))
+    sel = torch.as_tensor(idx, device=eng.device)
+    os.makedirs(outdir, exist_ok=True)
+    for name, f in fields.items():
+        np.save(os.path.join(outdir, name + '.npy'), eng.get(f)[sel].cpu().numpy())
+    np.save(os.path.join(outdir, 'members.npy'), (first + idx).astype(np.float64))
 
 
 def timed(fn, barrier=lambda: None):
@@ -397,8 +418,12 @@ def main():
     ap.add_argument('--precision', default='f16x3', choices=list(PRECISIONS),
                     help='generator conv arithmetic: f16x3 = hi/lo split f16 MFMA, f32-class accuracy (default); '
                          'f32 = exact f32 MFMA')
-    ap.add_argument('--no-aux', action='store_true', help='skip the steady / exact_f32 / b1 / b1024 / config3 / config4 legs')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: the steady / exact_f32 / b1 / b1024 / config3 / config4 legs and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the timed loop computed in its last step to DIR/<name>.npy (dump_outputs)')
+    ap.add_argument('--no-aux', action='store_true', help='with --full: skip the steady / exact_f32 / b1 / b1024 / config3 / config4 legs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-preheat', action='store_true',
                     help='profiling runs (profiles/): skip the 0.3 s of generator forwards in front of the timed region, so that the '
                          'per-kernel call counts of rocprofv3 are those of the warm-up + timed steps')
@@ -493,6 +518,8 @@ def main():
         elapsed = float(t.item())
     ke, cfl = eng.status()
     healthy = bool(np.isfinite(ke).all() and (cfl < 1).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, first, args.dump_outputs)
 
     out = None
     Bl = B // eng.step_streams(gen)              # members per launch (the ensemble advances as two halves on two streams)
@@ -531,7 +558,7 @@ def main():
             'healthy': healthy,
         }
 
-    aux = world == 1 and not args.no_aux and not strong
+    aux = world == 1 and args.full and not args.no_aux and not strong
     if aux:
         # SURVEY ยง8(d)'s protocol whatever --steps was: 100 warm-up + 2,000 timed steps of the SAME engine, 8 snapshots
         # and 2 status checks inside, HIP events around every 10th launch of the roofline kernel (200 launches)
@@ -570,7 +597,7 @@ def main():
         out['config3'] = leg_config3(qa, local_rank, one_stream=args.one_stream)
         out['config4'] = leg_config4(qa, local_rank)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(N, args.kind, dt)
     if rank == 0:
         print(json.dumps(out))

@@ -441,6 +441,33 @@ def test_bench_two_rank_rehearsal_over_gloo(mode):
     assert 'steady' not in out and 'config4' not in out                                      # auxiliary legs: one rank only
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_state(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps and runs no auxiliary leg (those need --full);
+    --dump-outputs writes the state of its last step: u, v and psi of that step's inversion (as in pyqg, one step behind the
+    updated q), so u, v are the derivatives of psi."""
+    import subprocess, sys
+    root = os.path.dirname(GOLDEN.rstrip('/')).rsplit('/tests', 1)[0]
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '30', '--warmup', '5', '--members', '8',
+           '--dump-outputs', str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    assert out['steps'] == 30 and out['warmup'] == 5 and out['healthy'] and out['higher_is_better'] is True
+    assert out['unit'] == 'ensemble-timesteps/sec' and out['metric'] and out['dtype']
+    assert abs(out['value'] - 8 * 30 / (out['ms_per_step'] * 30e-3)) < 1e-6 * out['value']
+    assert not {'steady', 'exact_f32', 'b1', 'b1024', 'config3', 'config4', 'cpu_baseline'} & set(out)
+    np.testing.assert_array_equal(np.load(tmp_path / 'members.npy'), np.arange(8.))
+    f = {n: np.load(tmp_path / f'{n}.npy') for n in ('q', 'u', 'v', 'psi', 's')}
+    for a in f.values():
+        assert a.dtype == np.float64 and a.shape == (8, 2, 64, 64) and np.isfinite(a).all()
+    assert np.abs(f['s']).max() > 0
+    rel = lambda a, b: np.abs(a - b).max() / np.abs(b).max()
+    m = qg_ref.QGModelRef(nx=64)
+    ph = np.fft.rfftn(f['psi'], axes=(-2, -1))
+    assert rel(f['u'], np.fft.irfftn(-m.il * ph, axes=(-2, -1))) < 1e-10
+    assert rel(f['v'], np.fft.irfftn(m.ik * ph, axes=(-2, -1))) < 1e-10
+
+
 _RCCL_CHILD = r'''
 import os, sys, json
 import numpy as np, torch

@@ -129,3 +129,40 @@ def test_product_set_initial_condition_matches_reference_golden():
         assert m2.q.shape == (3, 2, N, N)
         np.testing.assert_allclose(m2.q[1, 0], g[f'q1_{N}'], rtol=0, atol=1e-22)
         assert np.abs(m2.q[0, 0] - m2.q[1, 0]).max() > 1e-9
+
+
+def test_bench_dump_outputs_is_capped_and_seeded(tmp_path):
+    """bench.py --dump-outputs: float64 fields of the last step, whole ensemble while it fits in 64 MB, else the same seeded
+    sample of members every time (members.npy: their global ids)."""
+    import importlib.util
+    import torch
+    from conftest import ROOT
+    spec = importlib.util.spec_from_file_location('qgx_bench', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class _Eng:                                       # member m's fields hold 1000 m + field id
+        def __init__(self, B, N):
+            self.B, self.N, self.device = B, N, 'cpu'
+
+        def get(self, f):
+            return (1000. * torch.arange(self.B, dtype=torch.float64) + f)[:, None, None, None].expand(self.B, 2, self.N, self.N).clone()
+
+    names = ['members', 'psi', 'q', 's', 'u', 'v']
+    for B, N, first in ((128, 64, 0), (1024, 64, 3), (64, 256, 0)):
+        picks = []
+        for rep in range(2):
+            d = tmp_path / f'{B}_{N}_{rep}'
+            bench.dump_outputs(_Eng(B, N), first, str(d))
+            assert sorted(p.stem for p in d.iterdir()) == names
+            assert sum(p.stat().st_size for p in d.iterdir()) <= bench.DUMP_BYTES
+            ids = np.load(d / 'members.npy')
+            assert ids.dtype == np.float64 and np.all(np.diff(ids) > 0) and ids[0] >= first and ids[-1] < first + B
+            if B * 5 * 2 * N * N * 8 < 60e6:
+                np.testing.assert_array_equal(ids, np.arange(first, first + B))
+            for name in names[1:]:
+                a = np.load(d / f'{name}.npy')
+                assert a.dtype == np.float64 and a.shape == (len(ids), 2, N, N)
+                np.testing.assert_array_equal(a[:, 1, -1, -1] // 1000, ids - first)     # row i is member ids[i]
+            picks.append(ids)
+        np.testing.assert_array_equal(picks[0], picks[1])

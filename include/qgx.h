@@ -213,6 +213,39 @@ int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n_nets,
                          const float x_std[2], const float y_std[2], int device,
                          qgx_generator **out);
 int qgx_generator_destroy(qgx_generator *g);
+
+/* The DeepInversion U-Net generator of CGANRegression(generator='DeepInversion') (cgan_regression.py:50-53): the
+ * DeepInversionGenerator(4, 2) of tools/deep_inversion.py:44-94, blocks res_unit / down / up at :104-160, as the forecast
+ * sweep runs it (scripts/run_forecasting.py:25, 'CGANRegression-Unet').  Host pointers, float32, PyTorch layouts.
+ * A residual unit computes conv(bn(x)) + conv1(bn(x)), conv = LeakyReLU(0.2) -> conv_a 3x3 -> bn2 -> LeakyReLU(0.2) -> conv_b 3x3,
+ * conv1 = skip 1x1; state-dict keys <unit>.conv.1 (conv_a), .conv.2 (bn2), .conv.4 (conv_b), .conv1 (skip), .bn (bn). */
+typedef struct qgx_unet_res {
+    const float *bn_gamma, *bn_beta, *bn_mean, *bn_var;       /* bn (C_in): NULL for the bn='None' units 0 and 10    */
+    const float *conv_a_w, *conv_a_b;                         /* (C_out, C_in, 3, 3), (C_out)                        */
+    const float *bn2_gamma, *bn2_beta, *bn2_mean, *bn2_var;   /* (C_out): NULL for the bn='None' units              */
+    const float *conv_b_w, *conv_b_b;                         /* (C_out, C_out, 3, 3), (C_out)                       */
+    const float *skip_w, *skip_b;                             /* (C_out, C_in, 1, 1), (C_out)                        */
+} qgx_unet_res;
+
+typedef struct qgx_unet_weights {
+    const float *conv32_w, *conv32_b;   /* conv32: (32, 4, 3, 3), (32)                                               */
+    /* res32_start (32 -> 32, bn='None'), down64, down128, down256, down512 (each after AvgPool2d(2, 2): 32 -> 64 -> ...
+     * -> 512), res512 (512 -> 512), up512, up256, up128, up64 (each on cat((upsampled, skip), dim=1): 512 -> 256 -> ...
+     * -> 32), res32_end (32 -> 32, bn='None') */
+    qgx_unet_res res[11];
+    const float *up_w[4], *up_b[4];     /* up512 .. up64 .upsampling: ConvTranspose2d(C, C/2, 2, 2): (C, C/2, 2, 2), (C/2) */
+    const float *conv_end_w, *conv_end_b;   /* conv_end: (2, 32, 1, 1), (2)                                              */
+    float bn_eps;                       /* 1e-5                                                                       */
+} qgx_unet_weights;
+
+/* A GAN-kind handle whose generator is the U-Net (exact-f32 matrix-core kernels, unet.hip); net_mean: the AndrewCNN(2, 2)
+ * regression net of regression != 'None' (cgan_regression.py:59-60) or NULL.  S = y_std * (U-Net([q/x_std, z]) + net_mean(q/x_std)).
+ * The handle serves qgx_generator_forward, qgx_step (gen), qgx_cnn_forward (inet 0: the U-Net, inet 1: net_mean),
+ * qgx_generator_range_read and qgx_generator_info (precision 0).  N must be 32, 48, 64, 96 or 128 (QGX_ERR_INVALID before
+ * any launch otherwise).  The AndrewCNN-only options and queries (qgx_generator_set_option with anything but precision 0,
+ * _wino_info, _wino_info_n, _layer2_kernel, _profile, _profile_read) return QGX_ERR_INVALID on it. */
+int qgx_generator_create_unet(const qgx_unet_weights *g, const qgx_cnn_weights *net_mean, const float x_std[2],
+                              const float y_std[2], int device, qgx_generator **out);
 /* S = y_std * G([q/x_std, z]) — with a regression net S = y_std * (G([q/x_std, z]) + net_mean(q/x_std)), summed in
  * float32 — (cgan_regression.py:157-162; cvae_regression.py:131-136; mean_var_model.py:105-109).  demean != 0 also applies parameterization.py:25.
  * z is float for GAN/VAE, double for GZ. */

@@ -37,6 +37,19 @@ class qgx_cnn_weights(C.Structure):
                 ('bn_eps', C.c_float)]
 
 
+class qgx_unet_res(C.Structure):
+    _fields_ = [('bn_gamma', C.c_void_p), ('bn_beta', C.c_void_p), ('bn_mean', C.c_void_p), ('bn_var', C.c_void_p),
+                ('conv_a_w', C.c_void_p), ('conv_a_b', C.c_void_p),
+                ('bn2_gamma', C.c_void_p), ('bn2_beta', C.c_void_p), ('bn2_mean', C.c_void_p), ('bn2_var', C.c_void_p),
+                ('conv_b_w', C.c_void_p), ('conv_b_b', C.c_void_p), ('skip_w', C.c_void_p), ('skip_b', C.c_void_p)]
+
+
+class qgx_unet_weights(C.Structure):
+    _fields_ = [('conv32_w', C.c_void_p), ('conv32_b', C.c_void_p), ('res', qgx_unet_res * 11),
+                ('up_w', C.c_void_p * 4), ('up_b', C.c_void_p * 4),
+                ('conv_end_w', C.c_void_p), ('conv_end_b', C.c_void_p), ('bn_eps', C.c_float)]
+
+
 # enum mirrors (include/qgx.h)
 F_Q, F_QH, F_PH, F_U, F_V, F_DQHDT, F_DQHDT_P, F_DQHDT_PP, F_S, F_Z, F_P = range(11)
 T_FILTR, T_WV2, T_A, T_KK, T_LL = range(5)
@@ -70,6 +83,8 @@ SYMBOLS = [
     ('qgx_generator_create', C.c_int, [C.c_int, C.POINTER(qgx_cnn_weights), C.c_int,
                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                        C.POINTER(C.c_void_p)]),
+    ('qgx_generator_create_unet', C.c_int, [C.POINTER(qgx_unet_weights), C.POINTER(qgx_cnn_weights),
+                                            C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)]),
     ('qgx_generator_destroy', C.c_int, [C.c_void_p]),
     ('qgx_generator_forward', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_int, C.c_int, C.c_void_p]),

@@ -253,6 +253,14 @@ int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st)
 int diag_ensure_alloc(qgx_model *m);      // the increment's work fields and accumulators (allocated at first use)
 // the generator's activation workspace for the calls that follow (1: the second half of an ensemble stepped in halves)
 int generator_select_workspace(qgx_generator *g, int idx);
+// unet.hip: the DeepInversion U-Net generator body (exact-f32 matrix-core kernels)
+struct UNet;
+int unet_create(const qgx_unet_weights *w, UNet **out);
+void unet_destroy(UNet *u);
+bool unet_size_ok(int N);                       // N = 32, 48, 64, 96, 128
+size_t unet_workspace_floats(int B, int N);     // what unet_forward needs as `ws`
+// x planar (B, 4, N, N) float -> y planar (B, 2, N, N) float
+int unet_forward(const UNet *u, const float *x, float *y, float *ws, int B, int N, hipStream_t st);
 int noise_update(void *z, const void *xi_ext, bool is_double, int B, int n_per_member, uint64_t seed,
                  uint64_t member_offset, uint64_t step, double a, double b, hipStream_t st);
 int noise_normal(void *z, bool is_double, int B, int n_per_member, uint64_t seed,

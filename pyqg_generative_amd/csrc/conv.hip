@@ -825,6 +825,7 @@ struct NetHost {
 
 struct qgx_generator {
     int kind, device, n_nets;
+    qgx::UNet *unet = nullptr;     // qgx_generator_create_unet: net 0 is the DeepInversion U-Net (unet.hip), its workspace is actA
     qgx::NetHost nets[2];
     float x_std[2], y_std[2];
     // workspace (grown on demand, outside any captured region)
@@ -2170,7 +2171,8 @@ static int reserve(qgx_generator *g, int B, int N) {
     float **bufs[] = {&g->actA, &g->actB, &g->X, &g->Y0, &g->Y1};
     for (auto p : bufs) if (*p) { (void)hipFree(*p); *p = nullptr; }
     g->cap_elems = 0;
-    QGX_HIP(hipMalloc((void **)&g->actA, need * 128 * sizeof(float)));
+    const size_t actA = g->unet ? std::max(need * 128, unet_workspace_floats(B, N)) : need * 128;
+    QGX_HIP(hipMalloc((void **)&g->actA, actA * sizeof(float)));
     QGX_HIP(hipMalloc((void **)&g->actB, need * 64 * sizeof(float)));
     QGX_HIP(hipMalloc((void **)&g->X, need * 6 * sizeof(float)));    // (B, 4, N, N), and behind it (B, 2, N, N) for a regression net
     QGX_HIP(hipMalloc((void **)&g->Y0, need * 2 * sizeof(float)));
@@ -2395,9 +2397,16 @@ int generator_input_info(qgx_generator *g, int B, int N, GenFuse *gf) {
     return QGX_OK;
 }
 
+// net 0 of a GAN / VAE handle: the AndrewCNN generator / decoder, or the U-Net of qgx_generator_create_unet
+static int net0_forward(qgx_generator *g, const float *x, float *y, int B, int N, hipStream_t st) {
+    if (g->unet) return unet_forward(g->unet, x, y, g->actA, B, N, st);
+    return cnn_forward(g, g->nets[0], x, y, B, N, st);
+}
+
 int generator_forward(qgx_generator *g, const double *q, const void *z, double *S, int B, int N,
                       int demean, hipStream_t st, const NoiseUpdate *nu, GenFuse *defer, bool input_ready) {
     QGX_REQUIRE(g && q && z && S && B > 0, "generator_forward: bad argument");
+    QGX_REQUIRE(!g->unet || unet_size_ok(N), "U-Net generator: N = %d is not supported (32, 48, 64, 96 or 128)", N);
     int rc = reserve(g, B, N);
     if (rc) return rc;
     const int npix = N * N;
@@ -2428,7 +2437,7 @@ int generator_forward(qgx_generator *g, const double *q, const void *z, double *
             hipLaunchKernelGGL(k_take2, dim3((2 * npix / 4 + 255) / 256, B), pb, 0, st, (const float *)g->X, X2, 2 * npix);
             if ((rc = cnn_forward(g, g->nets[1], X2, g->Y1, B, N, st))) return rc;
         }
-        if ((rc = cnn_forward(g, g->nets[0], g->X, g->Y0, B, N, st))) return rc;
+        if ((rc = net0_forward(g, g->X, g->Y0, B, N, st))) return rc;
         if (defer) {
             defer->y = g->Y0; defer->y1 = regression ? g->Y1 : nullptr;
             defer->ys[0] = g->y_std[0]; defer->ys[1] = g->y_std[1]; defer->demean = demean;
@@ -2448,6 +2457,8 @@ int generator_forward(qgx_generator *g, const double *q, const void *z, double *
 }  // namespace qgx
 
 using namespace qgx;
+
+#define UNET_REFUSE "%s: a U-Net generator handle runs the exact-f32 kernels of unet.hip only; this applies to the AndrewCNN kernels"
 
 extern "C" int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n_nets, const float x_std[2],
                                     const float y_std[2], int device, qgx_generator **out) {
@@ -2489,6 +2500,41 @@ extern "C" int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n
     return QGX_OK;
 }
 
+extern "C" int qgx_generator_create_unet(const qgx_unet_weights *w, const qgx_cnn_weights *net_mean, const float x_std[2],
+                                         const float y_std[2], int device, qgx_generator **out) {
+    QGX_REQUIRE(w && out && x_std && y_std, "qgx_generator_create_unet: null argument");
+    QGX_REQUIRE(!net_mean || (net_mean->n_in == 2 && net_mean->n_out == 2),
+                "qgx_generator_create_unet: net_mean must be an AndrewCNN(2, 2) (n_in=%d n_out=%d)", net_mean->n_in, net_mean->n_out);
+    QGX_HIP(hipSetDevice(device));
+    qgx_generator *g = new (std::nothrow) qgx_generator();
+    if (!g) { set_error("out of host memory"); return QGX_ERR_NOMEM; }
+    g->kind = QGX_GEN_GAN; g->device = device; g->n_nets = net_mean ? 2 : 1;
+    for (int i = 0; i < 2; ++i) { g->x_std[i] = x_std[i]; g->y_std[i] = y_std[i]; }
+    // exact f32 throughout: the U-Net has no f16x3 path, and net_mean takes the exact-f32 AndrewCNN kernels
+    g->opt_precision = g->auto_precision = 0; g->opt_fold = g->auto_fold = 0; g->opt_wino = 0;
+    g->nets[0].n_in = 4; g->nets[0].n_out = 2;
+    int rc = unet_create(w, &g->unet);
+    if (!rc && net_mean) {
+        NetHost &net = g->nets[1];
+        net.n_in = 2; net.n_out = 2;
+        for (int li = 0; li < 8 && !rc; ++li) {
+            LayerHost &L = net.L[li];
+            L.cin = li == 0 ? 2 : HID[li - 1];
+            L.cout = li == 7 ? 2 : HID[li];
+            L.ks = KSZ[li];
+            rc = pack_layer(L, li, net_mean, li == 0);
+        }
+    }
+    if (!rc) {
+        hipError_t e = hipMalloc((void **)&g->range_dev, 2 * sizeof(unsigned));
+        if (e == hipSuccess) e = hipMemset(g->range_dev, 0, 2 * sizeof(unsigned));
+        if (e != hipSuccess) { set_error("qgx_generator_create_unet: %s", hipGetErrorString(e)); rc = QGX_ERR_HIP; }
+    }
+    if (rc) { qgx_generator_destroy(g); return rc; }
+    *out = g;
+    return QGX_OK;
+}
+
 extern "C" int qgx_generator_range_read(qgx_generator *g, unsigned *flags, float *input_absmax, void *stream) {
     QGX_REQUIRE(g && flags && input_absmax, "qgx_generator_range_read: null argument");
     unsigned h[2] = {0, 0};
@@ -2502,6 +2548,7 @@ extern "C" int qgx_generator_range_read(qgx_generator *g, unsigned *flags, float
 
 extern "C" int qgx_generator_wino_info_n(const qgx_generator *g, int N, int *enabled, int *chosen_by_calibration, float *calibration_error) {
     QGX_REQUIRE(g, "qgx_generator_wino_info_n: null generator");
+    QGX_REQUIRE(!g->unet, UNET_REFUSE, "qgx_generator_wino_info_n");
     const int si = wino_size_index(N);
     if (enabled) *enabled = si >= 0 && (g->opt_wino == 1 || (g->opt_wino == 2 && g->auto_wino_n[si]));
     if (chosen_by_calibration) *chosen_by_calibration = si >= 0 ? g->auto_wino_n[si] : 0;
@@ -2514,6 +2561,7 @@ extern "C" int qgx_generator_wino_info_n(const qgx_generator *g, int N, int *ena
 // 4 1-D Winograd with the transform under the MFMAs (k_convw2).  Mirrors cnn_forward_half / launch_convw.
 extern "C" int qgx_generator_layer2_kernel(const qgx_generator *g, int inet, int B, int N, int *kernel) {
     QGX_REQUIRE(g && kernel, "qgx_generator_layer2_kernel: null argument");
+    QGX_REQUIRE(!g->unet, UNET_REFUSE, "qgx_generator_layer2_kernel");
     QGX_REQUIRE(inet >= 0 && inet < g->n_nets, "qgx_generator_layer2_kernel: net %d of %d", inet, g->n_nets);
     const NetHost &net = g->nets[inet];
     *kernel = 0;
@@ -2536,6 +2584,7 @@ extern "C" int qgx_generator_layer2_kernel(const qgx_generator *g, int inet, int
 
 extern "C" int qgx_generator_wino_info(const qgx_generator *g, int *enabled, int *chosen_by_calibration, float *calibration_error) {
     QGX_REQUIRE(g, "qgx_generator_wino_info: null generator");
+    QGX_REQUIRE(!g->unet, UNET_REFUSE, "qgx_generator_wino_info");
     // the 64 x 64 grid (the headline workload); qgx_generator_wino_info_n reports every size
     if (enabled) *enabled = g->opt_wino == 1 || (g->opt_wino == 2 && g->auto_wino_n[2]);
     if (chosen_by_calibration) *chosen_by_calibration = g->auto_wino_n[2];
@@ -2572,6 +2621,7 @@ extern "C" int qgx_generator_destroy(qgx_generator *g) {
                      g->ws_other.actA, g->ws_other.actB, g->ws_other.X, g->ws_other.Y0, g->ws_other.Y1, g->ws_other.part};
     for (float *p : bufs) if (p) (void)hipFree(p);
     if (g->range_dev) (void)hipFree(g->range_dev);
+    unet_destroy(g->unet);
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     delete g;
     return QGX_OK;
@@ -2585,15 +2635,18 @@ extern "C" int qgx_generator_forward(qgx_generator *g, const double *q_dev, cons
 extern "C" int qgx_cnn_forward(qgx_generator *g, int inet, const float *x_dev, float *y_dev, int B, int N,
                                void *stream) {
     QGX_REQUIRE(g && x_dev && y_dev && inet >= 0 && inet < g->n_nets && B > 0, "qgx_cnn_forward: bad argument");
+    QGX_REQUIRE(!(g->unet && inet == 0) || unet_size_ok(N), "U-Net generator: N = %d is not supported (32, 48, 64, 96 or 128)", N);
     int rc = reserve(g, B, N);
     if (rc) return rc;
     hipLaunchKernelGGL(k_absmax, dim3(256), dim3(256), 0, (hipStream_t)stream, x_dev,
                        (size_t)B * g->nets[inet].n_in * N * N, g->range_dev);
+    if (inet == 0) return net0_forward(g, x_dev, y_dev, B, N, (hipStream_t)stream);
     return cnn_forward(g, g->nets[inet], x_dev, y_dev, B, N, (hipStream_t)stream);
 }
 
 extern "C" int qgx_generator_profile(qgx_generator *g, int layer) {
     QGX_REQUIRE(g && layer >= -1 && layer < 8, "qgx_generator_profile: bad argument");
+    QGX_REQUIRE(!g->unet, UNET_REFUSE, "qgx_generator_profile (per-layer profile)");
     g->prof_layer = layer;
     g->prof_used = 0;
     g->prof_seen = 0;
@@ -2602,6 +2655,7 @@ extern "C" int qgx_generator_profile(qgx_generator *g, int layer) {
 
 extern "C" int qgx_generator_profile_read(qgx_generator *g, double *total_ms, int64_t *launches) {
     QGX_REQUIRE(g && total_ms && launches, "qgx_generator_profile_read: null argument");
+    QGX_REQUIRE(!g->unet, UNET_REFUSE, "qgx_generator_profile_read (per-layer profile)");
     double tot = 0.0;
     for (size_t i = 0; i + 1 < g->prof_used; i += 2) {
         QGX_HIP(hipEventSynchronize(g->prof_ev[i + 1]));
@@ -2617,6 +2671,11 @@ extern "C" int qgx_generator_profile_read(qgx_generator *g, double *total_ms, in
 
 extern "C" int qgx_generator_set_option(qgx_generator *g, const char *name, int value) {
     QGX_REQUIRE(g && name, "qgx_generator_set_option: null argument");
+    if (g->unet) {       // every option selects between AndrewCNN kernels (net_mean runs the exact-f32 ones): only precision 0 holds
+        QGX_REQUIRE(!strcmp(name, "precision") && value == 0,
+                    "qgx_generator_set_option('%s'=%d): a U-Net generator handle runs exact f32 (precision 0) only; the option applies to the AndrewCNN kernels", name, value);
+        return QGX_OK;
+    }
     if (!strcmp(name, "chunk")) { QGX_REQUIRE(value == 16 || value == 32, "chunk must be 16 or 32"); g->opt_cc = value; }
     else if (!strcmp(name, "last_valu")) g->opt_last_valu = value ? 1 : 0;
     else if (!strcmp(name, "small")) g->opt_small = value ? 1 : 0;

@@ -29,35 +29,79 @@ class Generator:
 
     def __init__(self, kind, nets, x_std, y_std, device=0):
         """nets: list of dicts with float32 numpy arrays
-        conv_w[8], conv_b[8], bn_g[7], bn_b[7], bn_m[7], bn_v[7] (PyTorch layouts)."""
+        conv_w[8], conv_b[8], bn_g[7], bn_b[7], bn_m[7], bn_v[7] (PyTorch layouts).  kind 'gan' also takes the DeepInversion
+        U-Net as nets[0] (a weights.unet_from_state_dict / weights.synthetic_unet dict), optionally followed by net_mean."""
+        from .weights import is_unet
         self.kind = kind
         self.device = device
         self._h = C.c_void_p(0)
         keep = []
-        arr = (_lib.qgx_cnn_weights * len(nets))()
-        for n, net in enumerate(nets):
-            w = arr[n]
-            w.n_in = int(net['conv_w'][0].shape[1])
-            w.n_out = int(net['conv_w'][7].shape[0])
-            w.bn_eps = 1e-5
-            for i in range(8):
-                cw = np.ascontiguousarray(net['conv_w'][i], dtype=np.float32)
-                cb = np.ascontiguousarray(net['conv_b'][i], dtype=np.float32)
-                keep += [cw, cb]
-                w.conv_w[i] = cw.ctypes.data
-                w.conv_b[i] = cb.ctypes.data
-            for i in range(7):
-                for field, key in (('bn_gamma', 'bn_g'), ('bn_beta', 'bn_b'),
-                                   ('bn_mean', 'bn_m'), ('bn_var', 'bn_v')):
-                    a = np.ascontiguousarray(net[key][i], dtype=np.float32)
-                    keep.append(a)
-                    getattr(w, field)[i] = a.ctypes.data
         xs = (C.c_float * 2)(*[float(v) for v in np.asarray(x_std, np.float32).reshape(-1)])
         ys = (C.c_float * 2)(*[float(v) for v in np.asarray(y_std, np.float32).reshape(-1)])
         self.x_std = np.asarray(x_std, np.float32).reshape(-1)
         self.y_std = np.asarray(y_std, np.float32).reshape(-1)
-        check(lib.qgx_generator_create(self.KINDS[kind], arr, len(nets), xs, ys, device, C.byref(self._h)))
+        self.unet = bool(nets) and is_unet(nets[0])
+        if self.unet:
+            if kind != 'gan' or len(nets) > 2:
+                raise ValueError("the U-Net generator is a CGAN generator ('gan'), optionally with one regression net")
+            u = self._unet_struct(nets[0], keep)
+            mean = None
+            if len(nets) == 2:
+                mean = _lib.qgx_cnn_weights()
+                self._cnn_struct(nets[1], mean, keep)
+            check(lib.qgx_generator_create_unet(C.byref(u), C.byref(mean) if mean is not None else None, xs, ys, device,
+                                                C.byref(self._h)))
+        else:
+            arr = (_lib.qgx_cnn_weights * len(nets))()
+            for n, net in enumerate(nets):
+                self._cnn_struct(net, arr[n], keep)
+            check(lib.qgx_generator_create(self.KINDS[kind], arr, len(nets), xs, ys, device, C.byref(self._h)))
         self.n_in = 2 if kind == 'gz' else 4
+
+    @staticmethod
+    def _cnn_struct(net, w, keep):
+        w.n_in = int(net['conv_w'][0].shape[1])
+        w.n_out = int(net['conv_w'][7].shape[0])
+        w.bn_eps = 1e-5
+        for i in range(8):
+            cw = np.ascontiguousarray(net['conv_w'][i], dtype=np.float32)
+            cb = np.ascontiguousarray(net['conv_b'][i], dtype=np.float32)
+            keep += [cw, cb]
+            w.conv_w[i] = cw.ctypes.data
+            w.conv_b[i] = cb.ctypes.data
+        for i in range(7):
+            for field, key in (('bn_gamma', 'bn_g'), ('bn_beta', 'bn_b'),
+                               ('bn_mean', 'bn_m'), ('bn_var', 'bn_v')):
+                a = np.ascontiguousarray(net[key][i], dtype=np.float32)
+                keep.append(a)
+                getattr(w, field)[i] = a.ctypes.data
+
+    @staticmethod
+    def _unet_struct(net, keep):
+        """flat DeepInversionGenerator(4, 2) state dict -> qgx_unet_weights (host pointers into `keep`)"""
+        from .weights import UNET_UNITS, UNET_UPS
+
+        def ptr(key):
+            a = np.ascontiguousarray(net[key], dtype=np.float32)
+            keep.append(a)
+            return a.ctypes.data
+        u = _lib.qgx_unet_weights()
+        u.conv32_w, u.conv32_b = ptr('conv32.weight'), ptr('conv32.bias')
+        for i, (p, _, _, bn) in enumerate(UNET_UNITS):
+            r = u.res[i]
+            if bn:
+                r.bn_gamma, r.bn_beta = ptr(f'{p}.bn.weight'), ptr(f'{p}.bn.bias')
+                r.bn_mean, r.bn_var = ptr(f'{p}.bn.running_mean'), ptr(f'{p}.bn.running_var')
+                r.bn2_gamma, r.bn2_beta = ptr(f'{p}.conv.2.weight'), ptr(f'{p}.conv.2.bias')
+                r.bn2_mean, r.bn2_var = ptr(f'{p}.conv.2.running_mean'), ptr(f'{p}.conv.2.running_var')
+            r.conv_a_w, r.conv_a_b = ptr(f'{p}.conv.1.weight'), ptr(f'{p}.conv.1.bias')
+            r.conv_b_w, r.conv_b_b = ptr(f'{p}.conv.4.weight'), ptr(f'{p}.conv.4.bias')
+            r.skip_w, r.skip_b = ptr(f'{p}.conv1.weight'), ptr(f'{p}.conv1.bias')
+        for i, (p, _) in enumerate(UNET_UPS):
+            u.up_w[i], u.up_b[i] = ptr(f'{p}.upsampling.weight'), ptr(f'{p}.upsampling.bias')
+        u.conv_end_w, u.conv_end_b = ptr('conv_end.weight'), ptr('conv_end.bias')
+        u.bn_eps = 1e-5
+        return u
 
     @property
     def noise_dtype(self):
@@ -149,6 +193,8 @@ class Generator:
         assert q.is_cuda and q.dtype == torch.float64 and q.is_contiguous() and q.dim() == 4
         assert z.is_cuda and z.dtype == self.noise_dtype and z.is_contiguous()
         B, _, N, _ = q.shape
+        if self.unet and N not in (32, 48, 64, 96, 128):
+            raise ValueError(f'the U-Net generator runs on N = 32, 48, 64, 96 or 128, not {N}')
         assert z.numel() == q.numel()
         S = out if out is not None else torch.empty_like(q)
 
@@ -158,8 +204,11 @@ class Generator:
         return self._guarded(launch)
 
     def cnn_forward(self, x, inet=0):
-        """Raw AndrewCNN forward: x (B,n_in,N,N) float32 -> (B,2,N,N) float32."""
+        """Raw net forward: x (B,n_in,N,N) float32 -> (B,2,N,N) float32 (net 0: the AndrewCNN or U-Net generator, 4 channels)."""
         n_in = 2 if (self.kind == 'gz' or inet == 1) else 4          # net 1 of a GAN / VAE generator: the regression net
+        B, _, N, _ = x.shape
+        if self.unet and inet == 0 and N not in (32, 48, 64, 96, 128):
+            raise ValueError(f'the U-Net generator runs on N = 32, 48, 64, 96 or 128, not {N}')
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == n_in
         B, _, N, _ = x.shape
         y = torch.empty((B, 2, N, N), dtype=torch.float32, device=x.device)

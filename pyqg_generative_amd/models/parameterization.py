@@ -19,9 +19,10 @@ from ..tools.cnn_tools import ChannelwiseScaler, DeviceNet
 class Parameterization(QParameterization):
     kind = None          # 'gan' | 'vae' | 'gz'
 
-    def _load(self, folder, device=0):
+    def _load(self, folder, device=0, generator='Andrew'):
         self.folder = folder
-        nets, xs, ys = _weights.load_folder(folder, self.kind, regression=getattr(self, 'regression', 'None') != 'None')
+        nets, xs, ys = _weights.load_folder(folder, self.kind, regression=getattr(self, 'regression', 'None') != 'None',
+                                            generator=generator)
         self.x_scale = ChannelwiseScaler(xs)
         self.y_scale = ChannelwiseScaler(ys)
         self._gen = Generator(self.kind, nets, xs, ys, device=device)

@@ -54,17 +54,20 @@ def read_scaler_std(path):
     return np.array(ast.literal_eval(d['std'])).astype('float32').reshape(-1)
 
 
-def load_folder(folder, kind, regression=False):
+def load_folder(folder, kind, regression=False, generator='Andrew'):
     """Reference model folder -> (nets, x_std, y_std).  kind: 'gan' | 'vae' | 'gz'; regression ('gan' / 'vae' trained with
-    regression != 'None'): the folder also holds net_mean.pt (cgan_regression.py:98-101, cvae_regression.py:75-76)."""
+    regression != 'None'): the folder also holds net_mean.pt (cgan_regression.py:98-101, cvae_regression.py:75-76).
+    generator='DeepInversion' (CGAN only, cgan_regression.py:50-53): G.pt is the U-Net, nets[0] its unet_from_state_dict."""
     import torch
+    if generator not in ('Andrew', 'DeepInversion') or (generator == 'DeepInversion' and kind != 'gan'):
+        raise ValueError(f'generator={generator!r} is not available for kind {kind!r}')
     files = {'gan': ['G.pt'], 'vae': ['decoder.pt'], 'gz': ['net_mean.pt', 'net_var.pt']}[kind]
     if regression and kind != 'gz':
         files = files + ['net_mean.pt']
     nets = []
-    for f in files:
+    for i, f in enumerate(files):
         sd = torch.load(os.path.join(folder, f), map_location='cpu', weights_only=True)
-        nets.append(net_from_state_dict(sd))
+        nets.append(unet_from_state_dict(sd) if generator == 'DeepInversion' and i == 0 else net_from_state_dict(sd))
     return nets, read_scaler_std(os.path.join(folder, 'x_scale.json')), \
         read_scaler_std(os.path.join(folder, 'y_scale.json'))
 
@@ -92,3 +95,101 @@ def synthetic(kind, seed=0, regression=False):
     x_std = np.array([7.784383342368528e-06, 1.0471941322975908e-06], np.float32)
     y_std = np.array([7.60611105349307e-12, 1.656513061486578e-13], np.float32)
     return nets, x_std, y_std
+
+
+# ---- DeepInversion U-Net generator (CGANRegression(generator='DeepInversion'), deep_inversion.py:44-160) -------------
+# residual units in qgx_unet_weights order: (state-dict prefix, C_in, C_out, with BatchNorm)
+UNET_UNITS = [('res32_start', 32, 32, False), ('down64.conv.1', 32, 64, True), ('down128.conv.1', 64, 128, True),
+              ('down256.conv.1', 128, 256, True), ('down512.conv.1', 256, 512, True), ('res512', 512, 512, True),
+              ('up512.conv', 512, 256, True), ('up256.conv', 256, 128, True), ('up128.conv', 128, 64, True),
+              ('up64.conv', 64, 32, True), ('res32_end', 32, 32, False)]
+UNET_UPS = [('up512', 512), ('up256', 256), ('up128', 128), ('up64', 64)]
+
+
+def unet_shapes():
+    """every parameter / buffer of DeepInversionGenerator(4, 2)'s state dict -> shape (num_batches_tracked left out)"""
+    s = {'conv32.weight': (32, 4, 3, 3), 'conv32.bias': (32,)}
+    for p, ci, co, bn in UNET_UNITS:
+        if bn:
+            for k in ('weight', 'bias', 'running_mean', 'running_var'):
+                s[f'{p}.bn.{k}'] = (ci,)
+        s[f'{p}.conv.1.weight'] = (co, ci, 3, 3); s[f'{p}.conv.1.bias'] = (co,)
+        if bn:
+            for k in ('weight', 'bias', 'running_mean', 'running_var'):
+                s[f'{p}.conv.2.{k}'] = (co,)
+        s[f'{p}.conv.4.weight'] = (co, co, 3, 3); s[f'{p}.conv.4.bias'] = (co,)
+        s[f'{p}.conv1.weight'] = (co, ci, 1, 1); s[f'{p}.conv1.bias'] = (co,)
+    for p, c in UNET_UPS:
+        s[f'{p}.upsampling.weight'] = (c, c // 2, 2, 2); s[f'{p}.upsampling.bias'] = (c // 2,)
+    s['conv_end.weight'] = (2, 32, 1, 1); s['conv_end.bias'] = (2,)
+    return s
+
+
+def is_unet(net):
+    return isinstance(net, dict) and 'conv32.weight' in net
+
+
+def unet_from_state_dict(sd):
+    """DeepInversionGenerator(4, 2) state dict -> {key: float32 array}; raises KeyError on a missing or an unexpected key
+    (BatchNorm's num_batches_tracked counters are ignored)"""
+    shapes = unet_shapes()
+    keys = {k for k in sd.keys() if not k.endswith('num_batches_tracked')}
+    missing, extra = sorted(set(shapes) - keys), sorted(keys - set(shapes))
+    if missing or extra:
+        raise KeyError(f'not a DeepInversionGenerator(4, 2) state dict: missing {missing[:5]}, unexpected {extra[:5]}')
+    out = {}
+    for k, shp in shapes.items():
+        v = sd[k]
+        a = np.asarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else v, dtype=np.float32)
+        if a.shape != shp:
+            raise ValueError(f'{k}: shape {a.shape}, expected {shp}')
+        out[k] = np.ascontiguousarray(a)
+    return out
+
+
+def _splitmix64(x):
+    x = x + np.uint64(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def _hash_uniform(tensor_id, n):
+    """n values uniform in [-1, 1) from splitmix64(tensor_id << 32 | index), bit-reproducible on any machine"""
+    with np.errstate(over='ignore'):
+        z = _splitmix64((np.uint64(tensor_id) << np.uint64(32)) | np.arange(n, dtype=np.uint64))
+    return (z >> np.uint64(11)).astype(np.float64) * (2.0 / 2.0 ** 53) - 1.0
+
+
+def synthetic_unet():
+    """Deterministic U-Net weights for tests and timing (no torch / numpy RNG stream): Kaiming-like scales (uniform of
+    variance 2 / fan_in; the two branches of a residual unit 1 / 2 each) so that every stage's activations stay O(1),
+    BatchNorm with non-trivial running statistics.  Keys and layouts of the reference's state dict."""
+    out = {}
+    r3 = np.sqrt(3.0)
+    for tid, (k, shp) in enumerate(unet_shapes().items()):
+        n = int(np.prod(shp))
+        u = _hash_uniform(tid + 1, n)
+        if k.endswith('running_mean'):
+            v = 0.2 * u
+        elif k.endswith('running_var'):
+            v = 1.0 + 0.5 * u
+        elif '.bn.' in k or '.conv.2.' in k:
+            v = 1.0 + 0.2 * u if k.endswith('weight') else 0.1 * u
+        elif k.endswith('bias'):
+            v = 0.05 * u
+        else:
+            fan_in = n // shp[0] if 'upsampling' not in k else shp[0]
+            branch = 0.5 if ('.conv.4.' in k or '.conv1.' in k) else 1.0
+            v = u * r3 * np.sqrt(2.0 * branch / fan_in)
+        out[k] = v.astype(np.float32).reshape(shp)
+    return out
+
+
+def unet_checksum(net):
+    """sha256 of the tensors' float32 bytes in state-dict order, first 16 hex digits"""
+    import hashlib
+    h = hashlib.sha256()
+    for k in unet_shapes():
+        h.update(np.ascontiguousarray(net[k], dtype=np.float32).tobytes())
+    return h.hexdigest()[:16]

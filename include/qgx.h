@@ -117,7 +117,8 @@ typedef struct qgx_param {
     uint64_t seed;           /* Philox key for on-device latent noise                    */
     uint64_t member_offset;  /* global id of member 0 on this device (multi-GPU shards)  */
     const void *z_external_dev; /* if non-NULL: white noise xi for THIS step, layout of z
-                                   (parity tests); only honoured for nsteps_to_run == 1  */
+                                   (parity tests); only honoured for nsteps_to_run == 1;
+                                   refused (QGX_ERR_INVALID) with an OLS generator        */
     const double *forcing_dev;  /* gen == NULL: externally supplied S (B,2,N,N), used as is
                                    (plain pyqg q_parameterization semantics)             */
     int32_t  demean;         /* subtract the per-layer spatial mean of S (parameterization.py:25) */
@@ -195,8 +196,8 @@ int qgx_diag_reset(qgx_model *m);
 
 /* ---- generator ---------------------------------------------------------------
  * Replaces AndrewCNN inference through apply_function (cnn_tools.py:125-176,
- * 702-735) for CGANRegression.G / CVAERegression.decoder / MeanVarModel nets. */
-enum qgx_gen_kind { QGX_GEN_GAN = 0, QGX_GEN_VAE = 1, QGX_GEN_GZ = 2 };
+ * 702-735) for CGANRegression.G / CVAERegression.decoder / MeanVarModel nets / OLSModel.net. */
+enum qgx_gen_kind { QGX_GEN_GAN = 0, QGX_GEN_VAE = 1, QGX_GEN_GZ = 2, QGX_GEN_OLS = 3 };
 
 typedef struct qgx_cnn_weights {      /* host pointers, float32, PyTorch layouts */
     int32_t n_in, n_out;              /* 4/2 and 2                                   */
@@ -208,7 +209,11 @@ typedef struct qgx_cnn_weights {      /* host pointers, float32, PyTorch layouts
 
 /* nets: GAN / VAE — the generator / decoder (n_in 4), optionally followed by the regression net `net_mean` (n_in 2) of a
  * model trained with regression != 'None' (cgan_regression.py:59-60, cvae_regression.py:49-50): n_nets 1 or 2;
- * GZ — net_mean, net_var (n_in 2): n_nets 2 (mean_var_model.py:82-100). */
+ * GZ — net_mean, net_var (n_in 2): n_nets 2 (mean_var_model.py:82-100);
+ * OLS — the deterministic AndrewCNN(2, 2) `net` of OLSModel (ols_model.py:29-31), S = y_std * net(q/x_std) (:68-75): n_nets 1,
+ * n_in 2.  It takes no latent noise: qgx_generator_forward ignores z (NULL allowed), qgx_step draws none and writes no z,
+ * and refuses z_external_dev; the sampler still decides when the forcing is recomputed (generate_latent_noise returns 0,
+ * parameterization.py:23-34).  Any other n_nets, n_in or n_out is refused (QGX_ERR_INVALID) before any allocation. */
 int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n_nets,
                          const float x_std[2], const float y_std[2], int device,
                          qgx_generator **out);
@@ -247,8 +252,9 @@ typedef struct qgx_unet_weights {
 int qgx_generator_create_unet(const qgx_unet_weights *g, const qgx_cnn_weights *net_mean, const float x_std[2],
                               const float y_std[2], int device, qgx_generator **out);
 /* S = y_std * G([q/x_std, z]) — with a regression net S = y_std * (G([q/x_std, z]) + net_mean(q/x_std)), summed in
- * float32 — (cgan_regression.py:157-162; cvae_regression.py:131-136; mean_var_model.py:105-109).  demean != 0 also applies parameterization.py:25.
- * z is float for GAN/VAE, double for GZ. */
+ * float32 — (cgan_regression.py:157-162; cvae_regression.py:131-136; mean_var_model.py:105-109); OLS: S = y_std * net(q/x_std)
+ * (ols_model.py:68-75).  demean != 0 also applies parameterization.py:25.
+ * z is float for GAN/VAE, double for GZ, unused (may be NULL) for OLS. */
 int qgx_generator_forward(qgx_generator *g, const double *q_dev, const void *z_dev,
                           double *S_dev, int B, int N, int demean, void *stream);
 /* raw CNN forward of net `inet`: x (B,n_in,N,N) float -> y (B,n_out,N,N) float

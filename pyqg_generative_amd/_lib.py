@@ -57,7 +57,7 @@ SAMPLING_AR1, SAMPLING_CONSTANT = 0, 1
 DIAGS = ['KEspec', 'Ensspec', 'entspec', 'APEflux', 'KEflux', 'APEgenspec', 'KEfrictionspec', 'paramspec',
          'paramspec_APEflux', 'paramspec_KEflux', 'Dissspec', 'ENSDissspec', 'ENSflux', 'ENSgenspec', 'ENSfrictionspec',
          'ENSparamspec']
-GEN_GAN, GEN_VAE, GEN_GZ = 0, 1, 2
+GEN_GAN, GEN_VAE, GEN_GZ, GEN_OLS = 0, 1, 2, 3
 
 # every symbol include/qgx.h declares: (name, restype, argtypes)
 SYMBOLS = [

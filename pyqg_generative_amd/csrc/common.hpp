@@ -104,11 +104,12 @@ struct SpecDev {
     double H[2], Htot;
 };
 
-// Work the spectral step kernel does on the generator's behalf (small grids in layer-split form, GAN / VAE):
+// Work the spectral step kernel does on the generator's behalf (small grids in layer-split form, GAN / VAE / OLS):
 //  * y != null: the forcing is still the net's raw output (B,2,N,N) float; the kernel's prologue does what k_finish<FIN_PLAIN>
 //    does — S = double(y * y_std) - mean_{y,x} — with the same arithmetic and summation order, and stores S;
 //  * X != null: the kernel's epilogue assembles the NEXT step's network input from q^{n+1} and fresh white noise,
-//    X = [float(q)/x_std, z], z = b * xi(Philox; seed, member, step) — what k_prep_noise does with a == 0.
+//    X = [float(q)/x_std, z], z = b * xi(Philox; seed, member, step) — what k_prep_noise does with a == 0;
+//    no_noise (OLS): X = float(q)/x_std alone, (B, xc = 2, N, N) — what k_prep_input does with n_in = 2 (no Philox, no z).
 struct GenFuse {
     const float *y = nullptr;
     const float *y1 = nullptr;      // regression net's output, summed with y in float32 before the scaling (k_finish<FIN_SUM>)
@@ -118,6 +119,8 @@ struct GenFuse {
     float *X = nullptr;
     float *z = nullptr;
     float xs[2] = {1.f, 1.f};
+    int xc = 4;                     // channels of X per member: 4 ([q, z]) or 2 (OLS: q only)
+    int no_noise = 0;               // OLS: no latent channels, z is not written
     float b = 1.f;
     uint64_t seed = 0, member_offset = 0, step = 0;
 };
@@ -249,6 +252,7 @@ int small_qh_to_q(const SpecDev &d, const ModelOpts &o, const double2 *qh, doubl
 int small_invert(const SpecDev &d, const ModelOpts &o, const double2 *qh, double2 *ph, double *u, double *v, hipStream_t st);
 
 bool generator_noise_is_double(const qgx_generator *g);
+bool generator_takes_noise(const qgx_generator *g);     // false for OLS: no latent noise at all
 int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st);
 int diag_ensure_alloc(qgx_model *m);      // the increment's work fields and accumulators (allocated at first use)
 // the generator's activation workspace for the calls that follow (1: the second half of an ensemble stepped in halves)

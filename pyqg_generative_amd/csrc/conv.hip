@@ -23,6 +23,7 @@
 #include "philox.hpp"
 #include <cmath>
 #include <utility>
+#include <functional>
 #include <new>
 
 namespace qgx {
@@ -2251,6 +2252,45 @@ static int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, flo
 // per size; option "wino" = 0 / 1 overrides it, 2 restores it.)  The two tile shapes a size may run in (full / half
 // height) give bit-identical results, as do k_convw and k_convw2: one evaluation per size covers them.
 static constexpr float WINO_MAX_ERR = 1e-5f;
+// An OLS net's input is PV alone, a field without power at the smallest scales: its noise members are band-limited (wavenumbers
+// |k_x|, |k_y| <= N/3, unit variance, then the member's amplitude factor) like the q it is fed.  On such inputs the Winograd
+// form's error for the AndrewCNN(2, 2) shipped as GZ's net_mean is 3e-5 of max|y| where white noise shows 5-7e-6.
+static void band_limited_field(std::vector<float> &f, int N, const std::function<float()> &white) {
+    const int kc = N / 3;
+    std::vector<double> re((size_t)N * N), im((size_t)N * N, 0.0), tr((size_t)N * N), ti((size_t)N * N), cs(N), sn(N);
+    for (auto &v : re) v = white();
+    for (int t = 0; t < N; ++t) { cs[t] = cos(6.283185307179586 * t / N); sn[t] = sin(6.283185307179586 * t / N); }
+    auto pass = [&](bool rows, double sign) {       // DFT along x (rows) or y
+        for (int a = 0; a < N; ++a)
+            for (int k = 0; k < N; ++k) {
+                double sr = 0.0, si = 0.0;
+                for (int j = 0; j < N; ++j) {
+                    const size_t o = rows ? (size_t)a * N + j : (size_t)j * N + a;
+                    const int t = (int)(((long)k * j) % N);
+                    const double c = cs[t], sv = sign * sn[t];
+                    sr += re[o] * c - im[o] * sv;
+                    si += re[o] * sv + im[o] * c;
+                }
+                const size_t o = rows ? (size_t)a * N + k : (size_t)k * N + a;
+                tr[o] = sr; ti[o] = si;
+            }
+        re.swap(tr); im.swap(ti);
+    };
+    pass(true, -1.0); pass(false, -1.0);            // forward transform
+    for (int y = 0; y < N; ++y)                       // low-pass
+        for (int x = 0; x < N; ++x) {
+            const int ky = y <= N / 2 ? y : y - N, kx = x <= N / 2 ? x : x - N;
+            if (ky > kc || ky < -kc || kx > kc || kx < -kc) { re[(size_t)y * N + x] = 0.0; im[(size_t)y * N + x] = 0.0; }
+        }
+    pass(true, 1.0); pass(false, 1.0);              // inverse (unnormalised: the field is scaled to unit variance below)
+    double m = 0.0, m2 = 0.0;
+    for (double v : re) { m += v; m2 += v * v; }
+    m /= (double)N * N;
+    const double sd = sqrt(fmax(m2 / ((double)N * N) - m * m, 1e-300));
+    f.resize((size_t)N * N);
+    for (size_t i = 0; i < f.size(); ++i) f[i] = (float)((re[i] - m) / sd);
+}
+
 static int calibrate_wino(qgx_generator *g) {
     for (int i = 0; i < 5; ++i) { g->auto_wino_n[i] = 0; g->wino_err_n[i] = 0.f; }
     g->opt_wino = 0;
@@ -2277,19 +2317,23 @@ static int calibrate_wino(qgx_generator *g) {
             std::vector<float> x((size_t)B * net.n_in * npix);
             uint32_t lcg = 54321u + 977u * n;
             auto uni = [&]() { lcg = lcg * 1664525u + 1013904223u; return ((lcg >> 8) + 0.5f) * (1.0f / 16777216.0f); };
+            std::vector<float> band;
             for (int b = 0; b < B; ++b)
-                for (int c = 0; c < net.n_in; ++c)
+                for (int c = 0; c < net.n_in; ++c) {
+                    const bool banded = g->kind == QGX_GEN_OLS && pat[b] < 5;
+                    if (banded) band_limited_field(band, N, [&]() { return sqrtf(-2.f * logf(uni())) * cosf(6.2831853f * uni()); });
                     for (int y = 0; y < N; ++y)
                         for (int xx = 0; xx < N; ++xx) {
                             float v;
                             const int pb = pat[b];
-                            const float white = sqrtf(-2.f * logf(uni())) * cosf(6.2831853f * uni());
+                            const float white = banded ? band[(size_t)y * N + xx] : sqrtf(-2.f * logf(uni())) * cosf(6.2831853f * uni());
                             if (pb < 5) v = white * (pb == 3 ? 2.f : (pb == 4 ? 1.5f : 1.f));
                             else if (pb < 7) v = 2.f * sinf(6.2831853f * (y * (c + 1) + xx * (pb - 4)) / N)
                                                  + cosf(6.2831853f * 2 * xx / N) + 0.3f * white;
                             else v = 3.f * ((c & 1) ? -1.f : 1.f);
                             x[(((size_t)b * net.n_in + c) * N + y) * N + xx] = v;
                         }
+                }
             QGX_HIP(hipMemcpy(g->X, x.data(), x.size() * sizeof(float), hipMemcpyHostToDevice));
             g->opt_precision = 0;
             rc = cnn_forward(g, net, g->X, g->Y0, B, N, nullptr);
@@ -2388,12 +2432,16 @@ static int calibrate(qgx_generator *g) {
 }
 
 bool generator_noise_is_double(const qgx_generator *g) { return g->kind == QGX_GEN_GZ; }
+bool generator_takes_noise(const qgx_generator *g) { return g->kind != QGX_GEN_OLS; }
 
 int generator_input_info(qgx_generator *g, int B, int N, GenFuse *gf) {
     QGX_REQUIRE(g && gf && g->kind != QGX_GEN_GZ, "generator_input_info: bad argument");
     int rc = reserve(g, B, N);
     if (rc) return rc;
     gf->X = g->X; gf->xs[0] = g->x_std[0]; gf->xs[1] = g->x_std[1]; gf->range = g->range_dev;
+    // OLS: X = float(q)/x_std alone, (B, 2, N, N) as k_prep_input lays it out with n_in = 2
+    gf->xc = g->kind == QGX_GEN_OLS ? 2 : 4;
+    gf->no_noise = g->kind == QGX_GEN_OLS;
     return QGX_OK;
 }
 
@@ -2405,7 +2453,7 @@ static int net0_forward(qgx_generator *g, const float *x, float *y, int B, int N
 
 int generator_forward(qgx_generator *g, const double *q, const void *z, double *S, int B, int N,
                       int demean, hipStream_t st, const NoiseUpdate *nu, GenFuse *defer, bool input_ready) {
-    QGX_REQUIRE(g && q && z && S && B > 0, "generator_forward: bad argument");
+    QGX_REQUIRE(g && q && (z || g->kind == QGX_GEN_OLS) && S && B > 0, "generator_forward: bad argument");
     QGX_REQUIRE(!g->unet || unet_size_ok(N), "U-Net generator: N = %d is not supported (32, 48, 64, 96 or 128)", N);
     int rc = reserve(g, B, N);
     if (rc) return rc;
@@ -2420,6 +2468,19 @@ int generator_forward(qgx_generator *g, const double *q, const void *z, double *
         if ((rc = cnn_forward(g, g->nets[1], g->X, g->Y1, B, N, st))) return rc;
         hipLaunchKernelGGL(k_finish<FIN_GZ>, dim3(2 * B), dim3(1024), 0, st, (const float *)g->Y0, (const float *)g->Y1,
                            (const double *)z, S, npix, g->y_std[0], g->y_std[1], demean, g->range_dev);
+    } else if (g->kind == QGX_GEN_OLS) {
+        // OLSModel.predict_snapshot (ols_model.py:68-75): S = y_std * net(float(q)/x_std); no latent noise, z is never read
+        if (!input_ready)      // (else the previous step kernel wrote X: GenFuse::X with xc = 2, no_noise)
+            hipLaunchKernelGGL(k_prep_input, pg, pb, 0, st, q, (const float *)nullptr, g->X, 2, npix, g->x_std[0], g->x_std[1], g->range_dev);
+        if ((rc = cnn_forward(g, g->nets[0], g->X, g->Y0, B, N, st))) return rc;
+        if (defer) {
+            defer->y = g->Y0; defer->y1 = nullptr;
+            defer->ys[0] = g->y_std[0]; defer->ys[1] = g->y_std[1]; defer->demean = demean;
+            defer->range = g->range_dev;
+        } else {
+            hipLaunchKernelGGL(k_finish<FIN_PLAIN>, dim3(2 * B), dim3(1024), 0, st, (const float *)g->Y0, (const float *)nullptr,
+                               (const double *)nullptr, S, npix, g->y_std[0], g->y_std[1], demean, g->range_dev);
+        }
     } else {
         if (input_ready) {
             // the previous step kernel wrote X and z (GenFuse::X)
@@ -2463,10 +2524,18 @@ using namespace qgx;
 extern "C" int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n_nets, const float x_std[2],
                                     const float y_std[2], int device, qgx_generator **out) {
     QGX_REQUIRE(nets && out && x_std && y_std, "qgx_generator_create: null argument");
-    QGX_REQUIRE(kind == QGX_GEN_GAN || kind == QGX_GEN_VAE || kind == QGX_GEN_GZ, "unknown generator kind %d", kind);
-    // GAN / VAE: the generator or decoder, and optionally (regression != 'None', cgan_regression.py:59-60) the 2-channel net_mean
-    QGX_REQUIRE(kind == QGX_GEN_GZ ? n_nets == 2 : (n_nets == 1 || n_nets == 2), "generator kind %d needs %s nets, not %d", kind,
-                kind == QGX_GEN_GZ ? "2" : "1 or 2", n_nets);
+    QGX_REQUIRE(kind == QGX_GEN_GAN || kind == QGX_GEN_VAE || kind == QGX_GEN_GZ || kind == QGX_GEN_OLS,
+                "unknown generator kind %d", kind);
+    // GAN / VAE: the generator or decoder, and optionally (regression != 'None', cgan_regression.py:59-60) the 2-channel net_mean;
+    // OLS: the one AndrewCNN(2, 2) of OLSModel (ols_model.py:29-31)
+    QGX_REQUIRE(kind == QGX_GEN_GZ ? n_nets == 2 : kind == QGX_GEN_OLS ? n_nets == 1 : (n_nets == 1 || n_nets == 2),
+                "generator kind %d needs %s nets, not %d", kind,
+                kind == QGX_GEN_GZ ? "2" : kind == QGX_GEN_OLS ? "1" : "1 or 2", n_nets);
+    for (int n = 0; n < n_nets; ++n) {      // every net's shape before anything is allocated
+        const int want_in = kind == QGX_GEN_GZ || kind == QGX_GEN_OLS || n == 1 ? 2 : 4;
+        QGX_REQUIRE(nets[n].n_in == want_in && nets[n].n_out == 2, "net %d: n_in=%d n_out=%d, expected %d and 2", n,
+                    nets[n].n_in, nets[n].n_out, want_in);
+    }
     QGX_HIP(hipSetDevice(device));
     qgx_generator *g = new (std::nothrow) qgx_generator();
     if (!g) { set_error("out of host memory"); return QGX_ERR_NOMEM; }
@@ -2474,12 +2543,6 @@ extern "C" int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n
     for (int i = 0; i < 2; ++i) { g->x_std[i] = x_std[i]; g->y_std[i] = y_std[i]; }
     for (int n = 0; n < n_nets; ++n) {
         const qgx_cnn_weights *w = &nets[n];
-        const int want_in = kind == QGX_GEN_GZ || n == 1 ? 2 : 4;
-        if (w->n_in != want_in || w->n_out != 2) {
-            set_error("net %d: n_in=%d n_out=%d, expected %d and 2", n, w->n_in, w->n_out, want_in);
-            qgx_generator_destroy(g);
-            return QGX_ERR_INVALID;
-        }
         NetHost &net = g->nets[n];
         net.n_in = w->n_in; net.n_out = w->n_out;
         for (int li = 0; li < 8; ++li) {

@@ -534,8 +534,12 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
                     "qgx_step: constant sampler needs nsteps >= 1");
         QGX_REQUIRE(p->nsteps != 0, "qgx_step: nsteps == 0 is not a valid decorrelation time");
         QGX_REQUIRE(!(p->z_external_dev && nsteps != 1), "qgx_step: external noise needs nsteps_to_run == 1");
+        QGX_REQUIRE(!(p->z_external_dev && !generator_takes_noise(p->gen)), "qgx_step: an OLS generator takes no latent noise (z_external_dev)");
         m->z_double = generator_noise_is_double(p->gen);
     }
+    // OLS (generate_latent_noise returns 0, ols_model.py:65-66): the sampler only decides when the forcing is recomputed —
+    // AR1 on every step, constant on steps 1, n+1, 2n+1, ... (stochastic_pyqg.py:30-72) — with no draw and no write to z
+    const bool noisy = p && p->gen && generator_takes_noise(p->gen);
     const bool plain = !(p && (p->gen || p->forcing_dev));
     const bool fuse_ok = m->opts.genfuse != 0;
     m->x_ready_gen = nullptr;                                            // an assembled input never outlives its call
@@ -575,6 +579,7 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
             bool compute = true;
             double a = 0.0, b = 1.0;
             bool draw = true;
+            const bool fusable = fuse_ok && m->small && small_layer_split(m->d, m->opts) && !m->z_double;
             if (p->sampling == QGX_SAMPLING_AR1) {
                 if (m->have_noise) {
                     if (p->nsteps > 0) {
@@ -620,16 +625,15 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
                     }
                     have_pre = true;
                 }
-                // Small grids in layer-split form, GAN / VAE: the generator's output kernel rides in the step kernel's
-                // prologue (unless this step's diagnostics need S first) and — white-in-time Philox noise, more steps to
-                // come in this call — the next step's input kernel in its epilogue (GenFuse, common.hpp)
-                const bool fusable = fuse_ok && m->small && small_layer_split(m->d, m->opts) && !m->z_double;
+                // Small grids in layer-split form, GAN / VAE / OLS: the generator's output kernel rides in the step kernel's
+                // prologue (unless this step's diagnostics need S first) and the next step's input kernel in its epilogue
+                // (below; GenFuse, common.hpp)
                 const bool diag_due = m->dg_every > 0 && m->tc >= 1 && m->tc >= m->dg_start && m->tc % m->dg_every == 0;
                 const bool input_ready = fusable && draw && m->x_ready_gen == (const void *)p->gen && m->x_ready_step == nu.step;
                 m->x_ready_gen = nullptr;
-                // a redraw always comes with a recompute; the sampler update rides in the input kernel
-                int rc = generator_forward(p->gen, m->q, m->z, m->S, B, N, p->demean, st, draw ? &nu : nullptr,
-                                           fusable && !diag_due ? &gf : nullptr, input_ready);
+                // a redraw always comes with a recompute; the sampler update rides in the input kernel (OLS: nothing to draw)
+                int rc = generator_forward(p->gen, m->q, noisy ? m->z : nullptr, m->S, B, N, p->demean, st,
+                                           draw && noisy ? &nu : nullptr, fusable && !diag_due ? &gf : nullptr, input_ready);
                 if (rc) {
                     if (have_pre) {        // the first half wrote a dead tendency slot only: the state is that of step n - 1
                         (void)hipStreamWaitEvent(st, m->adv_event[m->adv_slot][1], 0);
@@ -638,16 +642,21 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
                     return rc;
                 }
                 m->have_forcing = true;
-                const bool white = (p->sampling == QGX_SAMPLING_AR1 && p->nsteps == 1) ||
-                                   (p->sampling == QGX_SAMPLING_CONSTANT && p->nsteps == 1);
-                if (fusable && white && !p->z_external_dev && s + 1 < nsteps) {
-                    if ((rc = generator_input_info(p->gen, B, N, &gf))) return rc;
+            }
+            // the next step's input in this step kernel's epilogue, more steps to come in this call: GAN / VAE when it draws
+            // white-in-time Philox noise (a draw on every step); OLS whenever the next step recomputes the forcing (AR1: every
+            // step; constant: the step after the counter reached nsteps) — also behind a step that holds its forcing
+            const bool next_input = noisy ? (p->nsteps == 1)
+                                          : (p->sampling == QGX_SAMPLING_AR1 || m->const_counter % p->nsteps == 0);
+            if (fusable && next_input && !p->z_external_dev && s + 1 < nsteps) {
+                if (int rc = generator_input_info(p->gen, B, N, &gf)) return rc;
+                if (noisy) {
                     gf.z = (float *)m->z; gf.b = 1.f;
                     gf.seed = p->seed; gf.member_offset = p->member_offset; gf.step = m->noise_step;
-                    m->x_ready_gen = p->gen; m->x_ready_step = m->noise_step;
                 }
-                use_gf = gf.y != nullptr || gf.X != nullptr;
+                m->x_ready_gen = p->gen; m->x_ready_step = m->noise_step;
             }
+            use_gf = gf.y != nullptr || gf.X != nullptr;
             has_S = m->have_forcing;
             S = m->S;
         } else if (p && p->forcing_dev) {

@@ -170,7 +170,7 @@ __global__ void k_step_small(SpecDev d, StepArgs a) {
             yraw[u] = i < rz ? yk[i] : 0.f;
         }
     }
-    if (LSPLIT && fside && a.gf.X) {
+    if (LSPLIT && fside && a.gf.X && !a.gf.no_noise) {
         // next step's latent channel first: it depends on nothing this kernel computes, and here its arithmetic
         // (Philox rounds, log, sincos) runs while the first global loads of the step are in flight
         // latent channel kown: z = b * xi, white in time (k_prep_noise with a == 0; quads of the flat (2, N*N) field)
@@ -183,7 +183,7 @@ __global__ void k_step_small(SpecDev d, StepArgs a) {
             for (int e = 0; e < 4; ++e) {
                 const float zn = a.gf.b * xi[e];
                 a.gf.z[o + e] = zn;
-                a.gf.X[(size_t)b * 4 * rz + 2 * (size_t)rz + 4 * (size_t)quad + e] = zn;
+                a.gf.X[(size_t)b * a.gf.xc * rz + 2 * (size_t)rz + 4 * (size_t)quad + e] = zn;
                 in_max = fmaxf(in_max, zn != zn ? __uint_as_float(0x7f800000u) : fabsf(zn));
             }
         }
@@ -427,9 +427,9 @@ __global__ void k_step_small(SpecDev d, StepArgs a) {
         const double2 w = Z[y * LD + x];
         if (LSPLIT) {
             a.q[ro + kown * rz + idx] = w.x;
-            if (a.gf.X) {       // the next step's network input, channel kown: float(q) / x_std (k_prep_noise, conv.hip)
+            if (a.gf.X) {       // the next step's network input, channel kown: float(q) / x_std (k_prep_noise / k_prep_input, conv.hip)
                 const float xq = (float)w.x / a.gf.xs[kown];
-                a.gf.X[((size_t)b * 4 + kown) * rz + idx] = xq;
+                a.gf.X[((size_t)b * a.gf.xc + kown) * rz + idx] = xq;
                 in_max = fmaxf(in_max, xq != xq ? __uint_as_float(0x7f800000u) : fabsf(xq));
             }
         } else {

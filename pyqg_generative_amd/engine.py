@@ -24,8 +24,8 @@ def _stream():
 
 class Generator:
     """Device-resident generator (CGAN G / CVAE decoder, each optionally with the regression net `net_mean` as a second
-    net / GZ mean+var nets)."""
-    KINDS = {'gan': _lib.GEN_GAN, 'vae': _lib.GEN_VAE, 'gz': _lib.GEN_GZ}
+    net / GZ mean+var nets / OLSModel's one deterministic net, which takes no latent noise)."""
+    KINDS = {'gan': _lib.GEN_GAN, 'vae': _lib.GEN_VAE, 'gz': _lib.GEN_GZ, 'ols': _lib.GEN_OLS}
 
     def __init__(self, kind, nets, x_std, y_std, device=0):
         """nets: list of dicts with float32 numpy arrays
@@ -56,7 +56,7 @@ class Generator:
             for n, net in enumerate(nets):
                 self._cnn_struct(net, arr[n], keep)
             check(lib.qgx_generator_create(self.KINDS[kind], arr, len(nets), xs, ys, device, C.byref(self._h)))
-        self.n_in = 2 if kind == 'gz' else 4
+        self.n_in = 2 if kind in ('gz', 'ols') else 4
 
     @staticmethod
     def _cnn_struct(net, w, keep):
@@ -105,6 +105,9 @@ class Generator:
 
     @property
     def noise_dtype(self):
+        """element type of the latent noise z; None for 'ols' (no noise)"""
+        if self.kind == 'ols':
+            return None
         return torch.float64 if self.kind == 'gz' else torch.float32
 
     # ---- f16x3 range guard ---------------------------------------------------------------------
@@ -188,14 +191,18 @@ class Generator:
             del self.check_range            # back to the class default
         return out
 
-    def forward(self, q, z, demean=True, out=None):
-        """q: (B,2,N,N) float64 cuda; z: (B,2,N,N) float32 (float64 for gz) -> S (B,2,N,N) float64."""
+    def forward(self, q, z=None, demean=True, out=None):
+        """q: (B,2,N,N) float64 cuda; z: (B,2,N,N) float32 (float64 for gz; 'ols' takes none) -> S (B,2,N,N) float64."""
         assert q.is_cuda and q.dtype == torch.float64 and q.is_contiguous() and q.dim() == 4
-        assert z.is_cuda and z.dtype == self.noise_dtype and z.is_contiguous()
         B, _, N, _ = q.shape
+        if self.kind == 'ols':
+            if z is not None:
+                raise ValueError("the 'ols' generator takes no latent noise")
+        else:
+            assert z is not None and z.is_cuda and z.dtype == self.noise_dtype and z.is_contiguous()
+            assert z.numel() == q.numel()
         if self.unet and N not in (32, 48, 64, 96, 128):
             raise ValueError(f'the U-Net generator runs on N = 32, 48, 64, 96 or 128, not {N}')
-        assert z.numel() == q.numel()
         S = out if out is not None else torch.empty_like(q)
 
         def launch():
@@ -204,8 +211,9 @@ class Generator:
         return self._guarded(launch)
 
     def cnn_forward(self, x, inet=0):
-        """Raw net forward: x (B,n_in,N,N) float32 -> (B,2,N,N) float32 (net 0: the AndrewCNN or U-Net generator, 4 channels)."""
-        n_in = 2 if (self.kind == 'gz' or inet == 1) else 4          # net 1 of a GAN / VAE generator: the regression net
+        """Raw net forward: x (B,n_in,N,N) float32 -> (B,2,N,N) float32 (net 0: the AndrewCNN or U-Net generator, 4 channels;
+        'gz' / 'ols': 2 channels)."""
+        n_in = 2 if (self.kind in ('gz', 'ols') or inet == 1) else 4   # net 1 of a GAN / VAE generator: the regression net
         B, _, N, _ = x.shape
         if self.unet and inet == 0 and N not in (32, 48, 64, 96, 128):
             raise ValueError(f'the U-Net generator runs on N = 32, 48, 64, 96 or 128, not {N}')

@@ -2,5 +2,6 @@ from .parameterization import Parameterization
 from .cgan_regression import CGANRegression
 from .cvae_regression import CVAERegression
 from .mean_var_model import MeanVarModel
+from .ols_model import OLSModel
 
-__all__ = ['Parameterization', 'CGANRegression', 'CVAERegression', 'MeanVarModel']
+__all__ = ['Parameterization', 'CGANRegression', 'CVAERegression', 'MeanVarModel', 'OLSModel']

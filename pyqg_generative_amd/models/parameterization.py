@@ -17,7 +17,7 @@ from ..tools.cnn_tools import ChannelwiseScaler, DeviceNet
 
 
 class Parameterization(QParameterization):
-    kind = None          # 'gan' | 'vae' | 'gz'
+    kind = None          # 'gan' | 'vae' | 'gz' | 'ols'
 
     def _load(self, folder, device=0, generator='Andrew'):
         self.folder = folder
@@ -42,8 +42,9 @@ class Parameterization(QParameterization):
         self = cls.__new__(cls)
         self.folder = None
         # a second net beside a generator / decoder is the regression net (cgan_regression.py:59-60)
-        self.regression = kw.get('regression', 'full_loss' if cls.kind != 'gz' and len(nets) == 2 else 'None')
-        if (self.regression != 'None') != (cls.kind != 'gz' and len(nets) == 2):
+        latent = cls.kind in ('gan', 'vae')
+        self.regression = kw.get('regression', 'full_loss' if latent and len(nets) == 2 else 'None')
+        if (self.regression != 'None') != (latent and len(nets) == 2):
             raise ValueError("regression != 'None' takes two nets (generator / decoder, net_mean); 'None' one")
         if self.regression != 'None':
             self.NET_NAMES = tuple(cls.NET_NAMES[:1]) + ('net_mean',)
@@ -66,8 +67,11 @@ class Parameterization(QParameterization):
         q = np.asarray(q, dtype='float64')
         single = q.ndim == 3
         qd = torch.as_tensor(np.ascontiguousarray(q.reshape((-1, 2) + q.shape[-2:]))).cuda()
-        z = np.asarray(noise).reshape(qd.shape)
-        z = torch.as_tensor(np.ascontiguousarray(z), dtype=self._gen.noise_dtype).cuda()
+        if self._gen.noise_dtype is None:          # OLS: no latent noise
+            z = None
+        else:
+            z = np.asarray(noise).reshape(qd.shape)
+            z = torch.as_tensor(np.ascontiguousarray(z), dtype=self._gen.noise_dtype).cuda()
         S = self._gen.forward(qd, z, demean=demean).cpu().numpy()
         return S[0] if single else S
 

@@ -233,3 +233,20 @@ def run_forecast(pyqg_params, parameterization, q_init, n_ens, operator=None, sa
     if n_local == 1:
         ds = ds.expand_dims('run')
     return forecast_statistics(ds, n_local, xr)
+
+
+def load_parameterization(folder='model', model_weight=1.0, device=0):
+    """The parameterization a trained model folder describes, times ``model_weight`` (reference: simulate.py:238-242,
+    255-259): ``model_args.json`` (written by save_model_args, cnn_tools.py:21-25) names the class under 'model' and holds
+    its constructor arguments; the model is built from ``folder`` on ``device``."""
+    import json
+    import os
+    from ..models import OLSModel, MeanVarModel, CGANRegression, CVAERegression
+    classes = {c.__name__: c for c in (OLSModel, MeanVarModel, CGANRegression, CVAERegression)}
+    with open(os.path.join(folder, 'model_args.json')) as f:
+        args = json.load(f)
+    name = args.pop('model')
+    if name not in classes:
+        raise NotImplementedError(f'model {name!r} has no device path (available: {", ".join(classes)})')
+    args.pop('folder', None)
+    return model_weight * classes[name](**args, folder=folder, device=device)

@@ -55,14 +55,15 @@ def read_scaler_std(path):
 
 
 def load_folder(folder, kind, regression=False, generator='Andrew'):
-    """Reference model folder -> (nets, x_std, y_std).  kind: 'gan' | 'vae' | 'gz'; regression ('gan' / 'vae' trained with
+    """Reference model folder -> (nets, x_std, y_std).  kind: 'gan' | 'vae' | 'gz' | 'ols' (OLSModel: net.pt,
+    ols_model.py:59-66); regression ('gan' / 'vae' trained with
     regression != 'None'): the folder also holds net_mean.pt (cgan_regression.py:98-101, cvae_regression.py:75-76).
     generator='DeepInversion' (CGAN only, cgan_regression.py:50-53): G.pt is the U-Net, nets[0] its unet_from_state_dict."""
     import torch
     if generator not in ('Andrew', 'DeepInversion') or (generator == 'DeepInversion' and kind != 'gan'):
         raise ValueError(f'generator={generator!r} is not available for kind {kind!r}')
-    files = {'gan': ['G.pt'], 'vae': ['decoder.pt'], 'gz': ['net_mean.pt', 'net_var.pt']}[kind]
-    if regression and kind != 'gz':
+    files = {'gan': ['G.pt'], 'vae': ['decoder.pt'], 'gz': ['net_mean.pt', 'net_var.pt'], 'ols': ['net.pt']}[kind]
+    if regression and kind in ('gan', 'vae'):
         files = files + ['net_mean.pt']
     nets = []
     for i, f in enumerate(files):
@@ -91,7 +92,10 @@ def synthetic(kind, seed=0, regression=False):
                 net['bn_m'].append((0.5 + 0.1 * rs.randn(cout)).astype('float32'))
                 net['bn_v'].append((0.5 + 0.2 * rs.rand(cout)).astype('float32'))
         return net
-    nets = [one(2), one(2)] if kind == 'gz' else ([one(4), one(2)] if regression else [one(4)])
+    if kind == 'ols':
+        nets = [one(2)]
+    else:
+        nets = [one(2), one(2)] if kind == 'gz' else ([one(4), one(2)] if regression else [one(4)])
     x_std = np.array([7.784383342368528e-06, 1.0471941322975908e-06], np.float32)
     y_std = np.array([7.60611105349307e-12, 1.656513061486578e-13], np.float32)
     return nets, x_std, y_std
@@ -192,4 +196,18 @@ def unet_checksum(net):
     h = hashlib.sha256()
     for k in unet_shapes():
         h.update(np.ascontiguousarray(net[k], dtype=np.float32).tobytes())
+    return h.hexdigest()[:16]
+
+
+def net_checksum(net):
+    """sha256 of an AndrewCNN's float32 parameters in state-dict order (per block: conv weight, bias, BatchNorm weight, bias,
+    running mean, running var), first 16 hex digits"""
+    import hashlib
+    h = hashlib.sha256()
+    for i in range(8):
+        arrays = [net['conv_w'][i], net['conv_b'][i]]
+        if i < 7:
+            arrays += [net['bn_g'][i], net['bn_b'][i], net['bn_m'][i], net['bn_v'][i]]
+        for a in arrays:
+            h.update(np.ascontiguousarray(a, dtype=np.float32).tobytes())
     return h.hexdigest()[:16]

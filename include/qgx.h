@@ -318,6 +318,45 @@ int qgx_generator_layer2_kernel(const qgx_generator *g, int inet, int B, int N, 
 int qgx_generator_profile(qgx_generator *g, int layer);
 int qgx_generator_profile_read(qgx_generator *g, double *total_ms, int64_t *launches);
 
+/* ---- online metrics ------------------------------------------------------------
+ * The exact 1-Wasserstein distance of two empirical distributions, scipy.stats.wasserstein_distance(u, v)
+ * (comparison_tools.py:116-195 scores every distributional feature with it): with a the merged sorted sample,
+ *     W1 = sum_k |i_k/n_u - j_k/n_v| * (a_{k+1} - a_k),   i_k, j_k = number of u, v values <= a_k.
+ * Three steps, all on `stream`: qgx_w1_keys turns each sample into order-preserving unsigned keys (float64 value:
+ * uint64 key; float32 identity feature: optionally uint32 key), qgx_w1_sorted sorts both key arrays (LSD radix sort,
+ * 8-bit digits: histogram -> scan -> stable scatter) and sums the terms along the merge path.  The result is bitwise
+ * the same on every call and for every permutation of either input (fixed partition, fixed reduction order, no float
+ * atomics, no inter-workgroup waiting).  Sizes are 64-bit. */
+enum qgx_w1_feature {
+    QGX_W1_IDENTITY = 0,   /* x                                          (q, u, v)                       */
+    QGX_W1_SUMSQ2 = 1,     /* x*x + y*y, in float64                      (KE = u^2 + v^2)                */
+    QGX_W1_SQUARE = 2      /* x*x, in float64                            (Ens = curl(u, v)^2)            */
+};
+enum { QGX_W1_PARTIALS = 1024 };   /* per-block partial sums of qgx_w1_keys: the size of its scratch */
+
+/* bytes of work space qgx_w1_sorted needs for nu and nv keys of key_bits (32 or 64) bits */
+int qgx_w1_workspace(size_t nu, size_t nv, int key_bits, size_t *bytes);
+/* keys of the feature selected by `feature` over a strided view: R x T rows of P contiguous values each, row (r, t)
+ * starting at element r*stride_r + t*stride_t of x (and of y, same strides; y is used by QGX_W1_SUMSQ2 only) — for the
+ * last T snapshots of layer z of an (R, T_all, 2, N, N) array pass x + (T_all-T)*stride_t + z*N*N, P = N*N,
+ * stride_t = 2*N*N, stride_r = T_all*stride_t.  is_double: x, y are double (1) or float (0).  key_bits 32 only for a
+ * float identity feature.  keys_dev: R*T*P keys.  partials_dev: scratch of 2 * QGX_W1_PARTIALS doubles.
+ * stats_dev (2 doubles, written): [0] = sum of feature^2 in a fixed order, [1] = number of NaN / +-inf feature values.
+ * QGX_ERR_INVALID before any device call for an empty view, a bad is_double / feature / key_bits, or null pointers. */
+int qgx_w1_keys(const void *x_dev, const void *y_dev, int is_double, int feature, int key_bits, int64_t R, int64_t T,
+                int64_t P, int64_t stride_r, int64_t stride_t, void *keys_dev, double *partials_dev, double *stats_dev,
+                void *stream);
+/* W1 of the two samples whose keys qgx_w1_keys wrote: sorts both key arrays IN PLACE, then merges them; out_dev (one
+ * double) <- W1, or NaN when stats_u[1] or stats_v[1] (may be NULL) count a non-finite value.  QGX_ERR_INVALID before any
+ * device call for nu == 0, nv == 0, key_bits not 32 / 64, or work_bytes below qgx_w1_workspace(nu, nv, key_bits). */
+int qgx_w1_sorted(void *keys_u_dev, size_t nu, const double *stats_u_dev, void *keys_v_dev, size_t nv,
+                  const double *stats_v_dev, int key_bits, void *work_dev, size_t work_bytes, double *out_dev,
+                  void *stream);
+/* out = ik*vh - il*uh = spectral curl(u, v) = ddx(v) - ddy(u) on an N-grid of domain size L (pyqg_parameterization_benchmarks
+ * FeatureExtractor 'curl(u,v)'); nfields (N, N/2+1) complex fields each */
+int qgx_spec_curl(const double *uh_dev, const double *vh_dev, double *out_dev, int nfields, int N, double L,
+                  void *stream);
+
 /* ---- latent noise ------------------------------------------------------------
  * z <- a z + b xi with xi ~ N(0,1) from Philox4x32-10 (stochastic_pyqg.py:43-49). */
 int qgx_noise_normal(void *z_dev, int is_double, int B, int n_per_member, uint64_t seed,

@@ -58,6 +58,8 @@ DIAGS = ['KEspec', 'Ensspec', 'entspec', 'APEflux', 'KEflux', 'APEgenspec', 'KEf
          'paramspec_APEflux', 'paramspec_KEflux', 'Dissspec', 'ENSDissspec', 'ENSflux', 'ENSgenspec', 'ENSfrictionspec',
          'ENSparamspec']
 GEN_GAN, GEN_VAE, GEN_GZ, GEN_OLS = 0, 1, 2, 3
+W1_IDENTITY, W1_SUMSQ2, W1_SQUARE = 0, 1, 2
+W1_PARTIALS = 1024
 
 # every symbol include/qgx.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -109,6 +111,12 @@ SYMBOLS = [
     ('qgx_generator_profile_read', C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     ('qgx_noise_normal', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
                                    C.c_uint64, C.c_double, C.c_double, C.c_void_p]),
+    ('qgx_w1_workspace', C.c_int, [C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]),
+    ('qgx_w1_keys', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                              C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('qgx_w1_sorted', C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
+                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ('qgx_spec_curl', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     ('qgx_last_error', C.c_char_p, []),
     ('qgx_version', C.c_char_p, []),
 ]

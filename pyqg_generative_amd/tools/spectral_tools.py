@@ -72,8 +72,24 @@ class _Grid:
         self.dk = self.dl = 2. * np.pi / L
         self.kk = self.dk * np.arange(0., nx / 2 + 1)
         self.ll = self.dl * np.append(np.arange(0., nx / 2), np.arange(-nx / 2, 0.))
-        k, l = np.meshgrid(self.kk, self.ll)
-        self.wv = np.sqrt(k ** 2 + l ** 2)
+        self.k, self.l = np.meshgrid(self.kk, self.ll)
+        self.wv = np.sqrt(self.k ** 2 + self.l ** 2)
+        self.dx = self.dy = self.L / self.nx
+
+    @property
+    def filtr(self):
+        """pyqg's exponential filter (model.py::_initialize_filter, default filterfac = 23.6)"""
+        cphi = 0.65 * np.pi
+        wvx = np.sqrt((self.k * self.dx) ** 2. + (self.l * self.dy) ** 2.)
+        filtr = np.exp(-23.6 * (wvx - cphi) ** 4.)
+        filtr[wvx <= cphi] = 1.
+        return filtr
+
+
+def twothirds_nyquist(m):
+    """the first wavenumber k (l = 0) where pyqg's filter drops below 1: two thirds of the Nyquist wavenumber
+    (comparison_tools.py:145-146); m: anything with pyqg's ``k`` and ``filtr``, e.g. ``_Grid(nx)``"""
+    return m.k[0][np.argwhere(np.array(m.filtr)[0] < 1)[0, 0]]
 
 
 class spectrum:

@@ -357,6 +357,51 @@ int qgx_w1_sorted(void *keys_u_dev, size_t nu, const double *stats_u_dev, void *
 int qgx_spec_curl(const double *uh_dev, const double *vh_dev, double *out_dev, int nfields, int N, double L,
                   void *stream);
 
+/* ---- offline metrics -----------------------------------------------------------
+ * The reductions behind Parameterization.test_offline (models/parameterization.py:36-168) and subgrid_scores /
+ * PDF_histogram (tools/computational_tools.py:5-84) over (R, T, 2, N, N) snapshot arrays: truth T, Monte-Carlo mean M,
+ * one sample G, streamfunction psi.  Every entry point returns QGX_ERR_INVALID before any device call for bad sizes,
+ * empty views, null pointers or bad flags; indexing is 64-bit; results are bitwise the same on every call and on any
+ * stream (fixed partitions, fixed-order merges, no float atomics).  Non-finite input gives NaN sums (spectra, moments)
+ * and is counted by qgx_histogram. */
+enum { QGX_OFFLINE_PLANES = 22,          /* (l, k) planes per time window of qgx_offline_spectra          */
+       QGX_OFFLINE_SPEC_GROUPS = 32,     /* snapshot s is accumulated in group s % 32                      */
+       QGX_HIST_MAX_BINS = 4096 };
+enum qgx_offline_work { QGX_WORK_SPECTRA = 0, QGX_WORK_MOMENTS = 1, QGX_WORK_HISTOGRAM = 2 };
+enum { QGX_HIST_STATS = 1,               /* first: mean and population std of the view (two passes)        */
+       QGX_HIST_SCALE_STD = 2 };         /* divide by that std instead of `scale` (needs QGX_HIST_STATS)   */
+
+/* bytes of device work space: SPECTRA the accumulator of qgx_offline_spectra for N (R, T, nbins unused), MOMENTS that of
+ * qgx_offline_moments for (R, T, N), HISTOGRAM that of qgx_histogram for nbins */
+int qgx_offline_workspace(int which, int64_t R, int64_t T, int64_t N, int nbins, size_t *bytes);
+/* Adds S consecutive snapshots (global indices s0 .. s0+S-1, time index s % T) to the accumulator acc_dev
+ * (QGX_OFFLINE_SPEC_GROUPS, 2, QGX_OFFLINE_PLANES, N, N/2+1) doubles; accumulate = 0 overwrites it (first call).
+ * th, gh, mh, psih: rfft2 of T, G, M, psi, (S, 2, N, N/2+1) complex (psih may be NULL: its planes are 0).  With
+ * X = rfft2(x)/N^2, R = T - M, GR = G - M, window w = (t >= t0), plane p of window w:
+ *   p = f*2 + z        |X_f,z|^2                 f = T, G, M, R, GR
+ *   p = 10 + f*2 + z   Re(conj(Psi_z) X_f,z)
+ *   p = 20, 21         Re(conj(R_0) R_1), Re(conj(GR_0) GR_1) */
+int qgx_offline_spectra(const double *th_dev, const double *gh_dev, const double *mh_dev, const double *psih_dev,
+                        int64_t S, int N, int64_t s0, int64_t T, int64_t t0, int accumulate, double *acc_dev,
+                        void *stream);
+/* out_dev (2, QGX_OFFLINE_PLANES, N, N/2+1) <- sum over the groups of acc_dev, in group order */
+int qgx_offline_spectra_finish(const double *acc_dev, int N, double *out_dev, void *stream);
+/* Grouped sums of truth t, mean m, sample g over (R, T, 2, N, N) in two passes; dtypes bit 0 / 1 / 2: t / m / g are
+ * double (else float).  out_dev, doubles, quantities q = [(t-m)^2, t^2, (t-t')^2, (m-m')^2, (t-t')(m-m'), (g-m)^2]
+ * with t', m' the group means:
+ *   spatial  (6, 2, N, N)   over (run, time)
+ *   temporal (6, T, 2)      over (run, y, x)
+ *   global   (6, 2)         over (run, time, y, x) */
+int qgx_offline_moments(const void *t_dev, const void *m_dev, const void *g_dev, int dtypes, int64_t R, int64_t T, int N,
+                        void *work_dev, size_t work_bytes, double *out_dev, void *stream);
+/* np.histogram(x / scale, bins = nbins, range = (edges[0], edges[nbins])) in float64 over the view layer z, t >= t0 of an
+ * (R, T, nlev, P) array; edges_dev: the np.linspace edges (nbins + 1 doubles).  counts_dev: nbins int64.  stats_dev (4
+ * doubles): [0] mean, [1] population std (QGX_HIST_STATS only), [2] non-finite values in the view, [3] the scale used.
+ * nbins = 0 with QGX_HIST_STATS computes the statistics only. */
+int qgx_histogram(const void *x_dev, int is_double, int64_t R, int64_t T, int64_t nlev, int64_t P, int64_t z, int64_t t0,
+                  const double *edges_dev, int nbins, int flags, double scale, void *work_dev, size_t work_bytes,
+                  int64_t *counts_dev, double *stats_dev, void *stream);
+
 /* ---- latent noise ------------------------------------------------------------
  * z <- a z + b xi with xi ~ N(0,1) from Philox4x32-10 (stochastic_pyqg.py:43-49). */
 int qgx_noise_normal(void *z_dev, int is_double, int B, int n_per_member, uint64_t seed,

@@ -60,6 +60,9 @@ DIAGS = ['KEspec', 'Ensspec', 'entspec', 'APEflux', 'KEflux', 'APEgenspec', 'KEf
 GEN_GAN, GEN_VAE, GEN_GZ, GEN_OLS = 0, 1, 2, 3
 W1_IDENTITY, W1_SUMSQ2, W1_SQUARE = 0, 1, 2
 W1_PARTIALS = 1024
+OFFLINE_PLANES, OFFLINE_SPEC_GROUPS, HIST_MAX_BINS = 22, 32, 4096
+WORK_SPECTRA, WORK_MOMENTS, WORK_HISTOGRAM = 0, 1, 2
+HIST_STATS, HIST_SCALE_STD = 1, 2
 
 # every symbol include/qgx.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -117,6 +120,15 @@ SYMBOLS = [
     ('qgx_w1_sorted', C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ('qgx_spec_curl', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    ('qgx_offline_workspace', C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
+    ('qgx_offline_spectra', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64,
+                                      C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    ('qgx_offline_spectra_finish', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    ('qgx_offline_moments', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int,
+                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ('qgx_histogram', C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
     ('qgx_last_error', C.c_char_p, []),
     ('qgx_version', C.c_char_p, []),
 ]

@@ -81,6 +81,19 @@ class Parameterization(QParameterization):
     def predict_mean_snapshot(self, m, M=100):
         raise NotImplementedError
 
+    def test_offline(self, ds, ensemble_size=1000, **predict_kwargs):
+        """Offline scores of this parameterization on a dataset with q, q_forcing_advection and psi
+        (run, time, lev, y, x) (reference: models/parameterization.py:36-168): predict(ds, ensemble_size,
+        **predict_kwargs), then the metrics on the GPU (tools/computational_tools.py::offline_dataset).  Returns the
+        reference's dataset in float32 with ds's attrs and time coordinate; ds is not modified."""
+        from ..tools.computational_tools import check_fields, offline_dataset, _values
+        for name in ('q', 'q_forcing_advection', 'psi'):
+            if name not in ds:
+                raise ValueError(f'test_offline needs {name!r} in the dataset')
+        check_fields(*(_values(ds[name]) for name in ('q', 'q_forcing_advection', 'psi')))
+        preds = self.predict(ds, ensemble_size, **predict_kwargs)
+        return offline_dataset(ds, preds, device=self._gen.device if hasattr(self._gen, 'device') else 0)
+
     def __call__(self, m):
         if m.sampling_type == 'deterministic':
             S = self.predict_mean_snapshot(m)

@@ -118,7 +118,7 @@ typedef struct qgx_param {
     uint64_t member_offset;  /* global id of member 0 on this device (multi-GPU shards)  */
     const void *z_external_dev; /* if non-NULL: white noise xi for THIS step, layout of z
                                    (parity tests); only honoured for nsteps_to_run == 1;
-                                   refused (QGX_ERR_INVALID) with an OLS generator        */
+                                   refused (QGX_ERR_INVALID) with an OLS or ANN generator */
     const double *forcing_dev;  /* gen == NULL: externally supplied S (B,2,N,N), used as is
                                    (plain pyqg q_parameterization semantics)             */
     int32_t  demean;         /* subtract the per-layer spatial mean of S (parameterization.py:25) */
@@ -251,10 +251,34 @@ typedef struct qgx_unet_weights {
  * _wino_info, _wino_info_n, _layer2_kernel, _profile, _profile_read) return QGX_ERR_INVALID on it. */
 int qgx_generator_create_unet(const qgx_unet_weights *g, const qgx_cnn_weights *net_mean, const float x_std[2],
                               const float y_std[2], int device, qgx_generator **out);
+
+/* ANNModel (models/ann_model.py): the pointwise MLP of tools/cnn_tools.py:184-210 (ANN), applied at every grid point of every
+ * layer of every member to the s x s PV stencil around it (wrapped), one net shared by both layers.  Feature dy*s + dx is
+ * float32(q) at offset (dy - s/2, dx - s/2) divided by x_scale (xarray_to_stencil, cnn_tools.py:321-339); the net is
+ * Linear(s*s, h0) -> ReLU -> ... -> Linear(h_last, 1) in float32, with scale_invariant y = |x|^2 layers(x / |x|) (degree 2);
+ * S = double(float32(y_scale * y)) (ann_model.py:82-93).  A zero stencil under scale_invariant gives NaN, as in torch.
+ * Its kind is QGX_GEN_ANN; qgx_generator_create refuses it.  The handle serves qgx_generator_forward (z unused, may be NULL),
+ * qgx_step (no latent noise, as OLS: no draw, no write to z, z_external_dev refused), qgx_cnn_forward (inet 0: the raw net on
+ * (B, 1, N, N) normalised float images -> (B, 1, N, N)), qgx_generator_info (precision 0) and qgx_generator_range_read, on
+ * any N up to 512.  The AndrewCNN-only options and queries return QGX_ERR_INVALID on it, as on the U-Net handle.
+ * Shapes are checked before any HIP call: odd stencil_size 1 ... 7, 1 ... 4 hidden layers of width 1 ... 128. */
+enum qgx_gen_kind_ann { QGX_GEN_ANN = 4 };
+
+typedef struct qgx_ann_weights {      /* host pointers, float32, PyTorch layouts (state-dict keys layers.{2l}.weight / bias) */
+    int32_t stencil_size;             /* s                                                          */
+    int32_t n_hidden;                 /* hidden layers                                              */
+    int32_t hidden[4];                /* their widths                                               */
+    int32_t scale_invariant;          /* != 0: ANN(degree = 2)                                      */
+    const float *w[5];                /* linear layer l = 0 .. n_hidden: weight (out, in)           */
+    const float *b[5];                /*                                  bias (out)                */
+} qgx_ann_weights;
+
+int qgx_generator_create_ann(const qgx_ann_weights *w, float x_scale, float y_scale, int device, qgx_generator **out);
 /* S = y_std * G([q/x_std, z]) — with a regression net S = y_std * (G([q/x_std, z]) + net_mean(q/x_std)), summed in
  * float32 — (cgan_regression.py:157-162; cvae_regression.py:131-136; mean_var_model.py:105-109); OLS: S = y_std * net(q/x_std)
- * (ols_model.py:68-75).  demean != 0 also applies parameterization.py:25.
- * z is float for GAN/VAE, double for GZ, unused (may be NULL) for OLS. */
+ * (ols_model.py:68-75); ANN: S = y_scale * net(stencil(q) / x_scale) (ann_model.py:82-93).  demean != 0 also applies
+ * parameterization.py:25.
+ * z is float for GAN/VAE, double for GZ, unused (may be NULL) for OLS and ANN. */
 int qgx_generator_forward(qgx_generator *g, const double *q_dev, const void *z_dev,
                           double *S_dev, int B, int N, int demean, void *stream);
 /* raw CNN forward of net `inet`: x (B,n_in,N,N) float -> y (B,n_out,N,N) float

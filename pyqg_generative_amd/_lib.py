@@ -50,6 +50,11 @@ class qgx_unet_weights(C.Structure):
                 ('conv_end_w', C.c_void_p), ('conv_end_b', C.c_void_p), ('bn_eps', C.c_float)]
 
 
+class qgx_ann_weights(C.Structure):
+    _fields_ = [('stencil_size', C.c_int32), ('n_hidden', C.c_int32), ('hidden', C.c_int32 * 4),
+                ('scale_invariant', C.c_int32), ('w', C.c_void_p * 5), ('b', C.c_void_p * 5)]
+
+
 # enum mirrors (include/qgx.h)
 F_Q, F_QH, F_PH, F_U, F_V, F_DQHDT, F_DQHDT_P, F_DQHDT_PP, F_S, F_Z, F_P = range(11)
 T_FILTR, T_WV2, T_A, T_KK, T_LL = range(5)
@@ -58,6 +63,7 @@ DIAGS = ['KEspec', 'Ensspec', 'entspec', 'APEflux', 'KEflux', 'APEgenspec', 'KEf
          'paramspec_APEflux', 'paramspec_KEflux', 'Dissspec', 'ENSDissspec', 'ENSflux', 'ENSgenspec', 'ENSfrictionspec',
          'ENSparamspec']
 GEN_GAN, GEN_VAE, GEN_GZ, GEN_OLS = 0, 1, 2, 3
+GEN_ANN = 4          # enum qgx_gen_kind_ann: handles of qgx_generator_create_ann only
 W1_IDENTITY, W1_SUMSQ2, W1_SQUARE = 0, 1, 2
 W1_PARTIALS = 1024
 OFFLINE_PLANES, OFFLINE_SPEC_GROUPS, HIST_MAX_BINS = 22, 32, 4096
@@ -90,6 +96,8 @@ SYMBOLS = [
                                        C.POINTER(C.c_void_p)]),
     ('qgx_generator_create_unet', C.c_int, [C.POINTER(qgx_unet_weights), C.POINTER(qgx_cnn_weights),
                                             C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)]),
+    ('qgx_generator_create_ann', C.c_int, [C.POINTER(qgx_ann_weights), C.c_float, C.c_float, C.c_int,
+                                           C.POINTER(C.c_void_p)]),
     ('qgx_generator_destroy', C.c_int, [C.c_void_p]),
     ('qgx_generator_forward', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_int, C.c_int, C.c_void_p]),

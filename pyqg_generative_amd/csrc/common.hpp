@@ -252,7 +252,8 @@ int small_qh_to_q(const SpecDev &d, const ModelOpts &o, const double2 *qh, doubl
 int small_invert(const SpecDev &d, const ModelOpts &o, const double2 *qh, double2 *ph, double *u, double *v, hipStream_t st);
 
 bool generator_noise_is_double(const qgx_generator *g);
-bool generator_takes_noise(const qgx_generator *g);     // false for OLS: no latent noise at all
+bool generator_takes_noise(const qgx_generator *g);     // false for OLS and ANN: no latent noise at all
+bool generator_reads_q(const qgx_generator *g);         // true for ANN: its kernel reads q itself, there is no input to assemble
 int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st);
 int diag_ensure_alloc(qgx_model *m);      // the increment's work fields and accumulators (allocated at first use)
 // the generator's activation workspace for the calls that follow (1: the second half of an ensemble stepped in halves)
@@ -265,6 +266,14 @@ bool unet_size_ok(int N);                       // N = 32, 48, 64, 96, 128
 size_t unet_workspace_floats(int B, int N);     // what unet_forward needs as `ws`
 // x planar (B, 4, N, N) float -> y planar (B, 2, N, N) float
 int unet_forward(const UNet *u, const float *x, float *y, float *ws, int B, int N, hipStream_t st);
+// ann.hip: ANNModel's pointwise stencil network
+struct Ann;
+int ann_check(const qgx_ann_weights *w);         // the shape rules, no HIP call
+int ann_create(const qgx_ann_weights *w, Ann **out);
+void ann_destroy(Ann *a);
+// q (n_img, N, N) double -> raw y (n_img, N, N) float, features float32(q) / x_scale; _x: already normalised float input
+int ann_forward_q(const Ann *a, const double *q, float x_scale, float *y, int64_t n_img, int N, hipStream_t st);
+int ann_forward_x(const Ann *a, const float *x, float *y, int64_t n_img, int N, hipStream_t st);
 int noise_update(void *z, const void *xi_ext, bool is_double, int B, int n_per_member, uint64_t seed,
                  uint64_t member_offset, uint64_t step, double a, double b, hipStream_t st);
 int noise_normal(void *z, bool is_double, int B, int n_per_member, uint64_t seed,

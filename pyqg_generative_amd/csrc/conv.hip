@@ -827,6 +827,7 @@ struct NetHost {
 struct qgx_generator {
     int kind, device, n_nets;
     qgx::UNet *unet = nullptr;     // qgx_generator_create_unet: net 0 is the DeepInversion U-Net (unet.hip), its workspace is actA
+    qgx::Ann *ann = nullptr;       // qgx_generator_create_ann: the pointwise stencil network (ann.hip); its only workspace is Y0
     qgx::NetHost nets[2];
     float x_std[2], y_std[2];
     // workspace (grown on demand, outside any captured region)
@@ -2172,6 +2173,11 @@ static int reserve(qgx_generator *g, int B, int N) {
     float **bufs[] = {&g->actA, &g->actB, &g->X, &g->Y0, &g->Y1};
     for (auto p : bufs) if (*p) { (void)hipFree(*p); *p = nullptr; }
     g->cap_elems = 0;
+    if (g->ann) {        // the ANN kernel reads q and writes its raw output (B, 2, N, N): no activations, no input buffer
+        QGX_HIP(hipMalloc((void **)&g->Y0, need * 2 * sizeof(float)));
+        g->cap_elems = need;
+        return QGX_OK;
+    }
     const size_t actA = g->unet ? std::max(need * 128, unet_workspace_floats(B, N)) : need * 128;
     QGX_HIP(hipMalloc((void **)&g->actA, actA * sizeof(float)));
     QGX_HIP(hipMalloc((void **)&g->actB, need * 64 * sizeof(float)));
@@ -2432,10 +2438,11 @@ static int calibrate(qgx_generator *g) {
 }
 
 bool generator_noise_is_double(const qgx_generator *g) { return g->kind == QGX_GEN_GZ; }
-bool generator_takes_noise(const qgx_generator *g) { return g->kind != QGX_GEN_OLS; }
+bool generator_takes_noise(const qgx_generator *g) { return g->kind != QGX_GEN_OLS && g->kind != QGX_GEN_ANN; }
+bool generator_reads_q(const qgx_generator *g) { return g->ann != nullptr; }
 
 int generator_input_info(qgx_generator *g, int B, int N, GenFuse *gf) {
-    QGX_REQUIRE(g && gf && g->kind != QGX_GEN_GZ, "generator_input_info: bad argument");
+    QGX_REQUIRE(g && gf && g->kind != QGX_GEN_GZ && !g->ann, "generator_input_info: bad argument");
     int rc = reserve(g, B, N);
     if (rc) return rc;
     gf->X = g->X; gf->xs[0] = g->x_std[0]; gf->xs[1] = g->x_std[1]; gf->range = g->range_dev;
@@ -2453,14 +2460,27 @@ static int net0_forward(qgx_generator *g, const float *x, float *y, int B, int N
 
 int generator_forward(qgx_generator *g, const double *q, const void *z, double *S, int B, int N,
                       int demean, hipStream_t st, const NoiseUpdate *nu, GenFuse *defer, bool input_ready) {
-    QGX_REQUIRE(g && q && (z || g->kind == QGX_GEN_OLS) && S && B > 0, "generator_forward: bad argument");
+    QGX_REQUIRE(g && q && (z || !generator_takes_noise(g)) && S && B > 0, "generator_forward: bad argument");
     QGX_REQUIRE(!g->unet || unet_size_ok(N), "U-Net generator: N = %d is not supported (32, 48, 64, 96 or 128)", N);
     int rc = reserve(g, B, N);
     if (rc) return rc;
     const int npix = N * N;
     QGX_REQUIRE(npix % 4 == 0, "generator_forward: N*N must be a multiple of 4");
     dim3 pg((npix + 255) / 256, B), pb(256);
-    if (g->kind == QGX_GEN_GZ) {
+    if (g->ann) {
+        // ANNModel.predict_snapshot (ann_model.py:82-93): y = net(stencil(float32(q)) / x_scale) per point of each (member,
+        // layer) image, read from q by the kernel itself; S = double(float32(y_scale * y)) is k_finish<FIN_PLAIN> with
+        // ys0 = ys1 = y_scale, or the step kernel's prologue (GenFuse::y).  No latent noise, no input to assemble.
+        if ((rc = ann_forward_q(g->ann, q, g->x_std[0], g->Y0, 2 * (int64_t)B, N, st))) return rc;
+        if (defer) {
+            defer->y = g->Y0; defer->y1 = nullptr;
+            defer->ys[0] = g->y_std[0]; defer->ys[1] = g->y_std[1]; defer->demean = demean;
+            defer->range = g->range_dev;
+        } else {
+            hipLaunchKernelGGL(k_finish<FIN_PLAIN>, dim3(2 * B), dim3(1024), 0, st, (const float *)g->Y0, (const float *)nullptr,
+                               (const double *)nullptr, S, npix, g->y_std[0], g->y_std[1], demean, g->range_dev);
+        }
+    } else if (g->kind == QGX_GEN_GZ) {
         if (nu && (rc = noise_update(const_cast<void *>(z), nu->xi_ext, true, B, 2 * npix, nu->seed, nu->member_offset,
                                      nu->step, nu->a, nu->b, st))) return rc;
         hipLaunchKernelGGL(k_prep_input, pg, pb, 0, st, q, (const float *)nullptr, g->X, 2, npix, g->x_std[0], g->x_std[1], g->range_dev);
@@ -2520,6 +2540,12 @@ int generator_forward(qgx_generator *g, const double *q, const void *z, double *
 using namespace qgx;
 
 #define UNET_REFUSE "%s: a U-Net generator handle runs the exact-f32 kernels of unet.hip only; this applies to the AndrewCNN kernels"
+#define ANN_REFUSE "%s: an ANN generator handle runs the stencil-network kernels of ann.hip only; this applies to the AndrewCNN kernels"
+#define REFUSE_NON_ANDREW(g, what)                                  \
+    do {                                                            \
+        QGX_REQUIRE(!(g)->unet, UNET_REFUSE, what);                 \
+        QGX_REQUIRE(!(g)->ann, ANN_REFUSE, what);                   \
+    } while (0)
 
 extern "C" int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n_nets, const float x_std[2],
                                     const float y_std[2], int device, qgx_generator **out) {
@@ -2598,6 +2624,28 @@ extern "C" int qgx_generator_create_unet(const qgx_unet_weights *w, const qgx_cn
     return QGX_OK;
 }
 
+extern "C" int qgx_generator_create_ann(const qgx_ann_weights *w, float x_scale, float y_scale, int device,
+                                        qgx_generator **out) {
+    QGX_REQUIRE(w && out, "qgx_generator_create_ann: null argument");
+    if (int rc = ann_check(w)) return rc;        // every shape before the device is touched
+    QGX_HIP(hipSetDevice(device));
+    qgx_generator *g = new (std::nothrow) qgx_generator();
+    if (!g) { set_error("out of host memory"); return QGX_ERR_NOMEM; }
+    g->kind = QGX_GEN_ANN; g->device = device; g->n_nets = 1;
+    for (int i = 0; i < 2; ++i) { g->x_std[i] = x_scale; g->y_std[i] = y_scale; }   // scalars: one net for both layers
+    g->opt_precision = g->auto_precision = 0; g->opt_fold = g->auto_fold = 0; g->opt_wino = 0;
+    g->nets[0].n_in = 1; g->nets[0].n_out = 1;
+    int rc = ann_create(w, &g->ann);
+    if (!rc) {
+        hipError_t e = hipMalloc((void **)&g->range_dev, 2 * sizeof(unsigned));
+        if (e == hipSuccess) e = hipMemset(g->range_dev, 0, 2 * sizeof(unsigned));
+        if (e != hipSuccess) { set_error("qgx_generator_create_ann: %s", hipGetErrorString(e)); rc = QGX_ERR_HIP; }
+    }
+    if (rc) { qgx_generator_destroy(g); return rc; }
+    *out = g;
+    return QGX_OK;
+}
+
 extern "C" int qgx_generator_range_read(qgx_generator *g, unsigned *flags, float *input_absmax, void *stream) {
     QGX_REQUIRE(g && flags && input_absmax, "qgx_generator_range_read: null argument");
     unsigned h[2] = {0, 0};
@@ -2611,7 +2659,7 @@ extern "C" int qgx_generator_range_read(qgx_generator *g, unsigned *flags, float
 
 extern "C" int qgx_generator_wino_info_n(const qgx_generator *g, int N, int *enabled, int *chosen_by_calibration, float *calibration_error) {
     QGX_REQUIRE(g, "qgx_generator_wino_info_n: null generator");
-    QGX_REQUIRE(!g->unet, UNET_REFUSE, "qgx_generator_wino_info_n");
+    REFUSE_NON_ANDREW(g, "qgx_generator_wino_info_n");
     const int si = wino_size_index(N);
     if (enabled) *enabled = si >= 0 && (g->opt_wino == 1 || (g->opt_wino == 2 && g->auto_wino_n[si]));
     if (chosen_by_calibration) *chosen_by_calibration = si >= 0 ? g->auto_wino_n[si] : 0;
@@ -2624,7 +2672,7 @@ extern "C" int qgx_generator_wino_info_n(const qgx_generator *g, int N, int *ena
 // 4 1-D Winograd with the transform under the MFMAs (k_convw2).  Mirrors cnn_forward_half / launch_convw.
 extern "C" int qgx_generator_layer2_kernel(const qgx_generator *g, int inet, int B, int N, int *kernel) {
     QGX_REQUIRE(g && kernel, "qgx_generator_layer2_kernel: null argument");
-    QGX_REQUIRE(!g->unet, UNET_REFUSE, "qgx_generator_layer2_kernel");
+    REFUSE_NON_ANDREW(g, "qgx_generator_layer2_kernel");
     QGX_REQUIRE(inet >= 0 && inet < g->n_nets, "qgx_generator_layer2_kernel: net %d of %d", inet, g->n_nets);
     const NetHost &net = g->nets[inet];
     *kernel = 0;
@@ -2647,7 +2695,7 @@ extern "C" int qgx_generator_layer2_kernel(const qgx_generator *g, int inet, int
 
 extern "C" int qgx_generator_wino_info(const qgx_generator *g, int *enabled, int *chosen_by_calibration, float *calibration_error) {
     QGX_REQUIRE(g, "qgx_generator_wino_info: null generator");
-    QGX_REQUIRE(!g->unet, UNET_REFUSE, "qgx_generator_wino_info");
+    REFUSE_NON_ANDREW(g, "qgx_generator_wino_info");
     // the 64 x 64 grid (the headline workload); qgx_generator_wino_info_n reports every size
     if (enabled) *enabled = g->opt_wino == 1 || (g->opt_wino == 2 && g->auto_wino_n[2]);
     if (chosen_by_calibration) *chosen_by_calibration = g->auto_wino_n[2];
@@ -2685,6 +2733,7 @@ extern "C" int qgx_generator_destroy(qgx_generator *g) {
     for (float *p : bufs) if (p) (void)hipFree(p);
     if (g->range_dev) (void)hipFree(g->range_dev);
     unet_destroy(g->unet);
+    ann_destroy(g->ann);
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     delete g;
     return QGX_OK;
@@ -2703,13 +2752,14 @@ extern "C" int qgx_cnn_forward(qgx_generator *g, int inet, const float *x_dev, f
     if (rc) return rc;
     hipLaunchKernelGGL(k_absmax, dim3(256), dim3(256), 0, (hipStream_t)stream, x_dev,
                        (size_t)B * g->nets[inet].n_in * N * N, g->range_dev);
+    if (g->ann) return ann_forward_x(g->ann, x_dev, y_dev, B, N, (hipStream_t)stream);   // (B, 1, N, N) -> (B, 1, N, N)
     if (inet == 0) return net0_forward(g, x_dev, y_dev, B, N, (hipStream_t)stream);
     return cnn_forward(g, g->nets[inet], x_dev, y_dev, B, N, (hipStream_t)stream);
 }
 
 extern "C" int qgx_generator_profile(qgx_generator *g, int layer) {
     QGX_REQUIRE(g && layer >= -1 && layer < 8, "qgx_generator_profile: bad argument");
-    QGX_REQUIRE(!g->unet, UNET_REFUSE, "qgx_generator_profile (per-layer profile)");
+    REFUSE_NON_ANDREW(g, "qgx_generator_profile (per-layer profile)");
     g->prof_layer = layer;
     g->prof_used = 0;
     g->prof_seen = 0;
@@ -2718,7 +2768,7 @@ extern "C" int qgx_generator_profile(qgx_generator *g, int layer) {
 
 extern "C" int qgx_generator_profile_read(qgx_generator *g, double *total_ms, int64_t *launches) {
     QGX_REQUIRE(g && total_ms && launches, "qgx_generator_profile_read: null argument");
-    QGX_REQUIRE(!g->unet, UNET_REFUSE, "qgx_generator_profile_read (per-layer profile)");
+    REFUSE_NON_ANDREW(g, "qgx_generator_profile_read (per-layer profile)");
     double tot = 0.0;
     for (size_t i = 0; i + 1 < g->prof_used; i += 2) {
         QGX_HIP(hipEventSynchronize(g->prof_ev[i + 1]));
@@ -2734,9 +2784,10 @@ extern "C" int qgx_generator_profile_read(qgx_generator *g, double *total_ms, in
 
 extern "C" int qgx_generator_set_option(qgx_generator *g, const char *name, int value) {
     QGX_REQUIRE(g && name, "qgx_generator_set_option: null argument");
-    if (g->unet) {       // every option selects between AndrewCNN kernels (net_mean runs the exact-f32 ones): only precision 0 holds
+    if (g->unet || g->ann) {   // every option selects between AndrewCNN kernels (net_mean runs the exact-f32 ones): only precision 0 holds
         QGX_REQUIRE(!strcmp(name, "precision") && value == 0,
-                    "qgx_generator_set_option('%s'=%d): a U-Net generator handle runs exact f32 (precision 0) only; the option applies to the AndrewCNN kernels", name, value);
+                    "qgx_generator_set_option('%s'=%d): a%s generator handle runs exact f32 (precision 0) only; the option applies to the AndrewCNN kernels",
+                    name, value, g->ann ? "n ANN" : " U-Net");
         return QGX_OK;
     }
     if (!strcmp(name, "chunk")) { QGX_REQUIRE(value == 16 || value == 32, "chunk must be 16 or 32"); g->opt_cc = value; }

@@ -534,7 +534,8 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
                     "qgx_step: constant sampler needs nsteps >= 1");
         QGX_REQUIRE(p->nsteps != 0, "qgx_step: nsteps == 0 is not a valid decorrelation time");
         QGX_REQUIRE(!(p->z_external_dev && nsteps != 1), "qgx_step: external noise needs nsteps_to_run == 1");
-        QGX_REQUIRE(!(p->z_external_dev && !generator_takes_noise(p->gen)), "qgx_step: an OLS generator takes no latent noise (z_external_dev)");
+        QGX_REQUIRE(!(p->z_external_dev && !generator_takes_noise(p->gen)),
+                    "qgx_step: an OLS or ANN generator takes no latent noise (z_external_dev)");
         m->z_double = generator_noise_is_double(p->gen);
     }
     // OLS (generate_latent_noise returns 0, ols_model.py:65-66): the sampler only decides when the forcing is recomputed —
@@ -645,8 +646,10 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
             }
             // the next step's input in this step kernel's epilogue, more steps to come in this call: GAN / VAE when it draws
             // white-in-time Philox noise (a draw on every step); OLS whenever the next step recomputes the forcing (AR1: every
-            // step; constant: the step after the counter reached nsteps) — also behind a step that holds its forcing
-            const bool next_input = noisy ? (p->nsteps == 1)
+            // step; constant: the step after the counter reached nsteps) — also behind a step that holds its forcing.  ANN: never,
+            // its kernel reads q itself (ann.hip)
+            const bool next_input = generator_reads_q(p->gen) ? false
+                                  : noisy ? (p->nsteps == 1)
                                           : (p->sampling == QGX_SAMPLING_AR1 || m->const_counter % p->nsteps == 0);
             if (fusable && next_input && !p->z_external_dev && s + 1 < nsteps) {
                 if (int rc = generator_input_info(p->gen, B, N, &gf)) return rc;

@@ -25,7 +25,8 @@ def _stream():
 class Generator:
     """Device-resident generator (CGAN G / CVAE decoder, each optionally with the regression net `net_mean` as a second
     net / GZ mean+var nets / OLSModel's one deterministic net, which takes no latent noise)."""
-    KINDS = {'gan': _lib.GEN_GAN, 'vae': _lib.GEN_VAE, 'gz': _lib.GEN_GZ, 'ols': _lib.GEN_OLS}
+    KINDS = {'gan': _lib.GEN_GAN, 'vae': _lib.GEN_VAE, 'gz': _lib.GEN_GZ, 'ols': _lib.GEN_OLS, 'ann': _lib.GEN_ANN}
+    NOISE_FREE = ('ols', 'ann')
 
     def __init__(self, kind, nets, x_std, y_std, device=0):
         """nets: list of dicts with float32 numpy arrays
@@ -41,6 +42,15 @@ class Generator:
         self.x_std = np.asarray(x_std, np.float32).reshape(-1)
         self.y_std = np.asarray(y_std, np.float32).reshape(-1)
         self.unet = bool(nets) and is_unet(nets[0])
+        if kind == 'ann':
+            # ANNModel's stencil network: nets = [weights.ann_from_state_dict dict], x_std / y_std the scalars x_scale, y_scale
+            if len(nets) != 1 or self.x_std.size != 1 or self.y_std.size != 1:
+                raise ValueError("the 'ann' generator takes one ANN and the scalars x_scale, y_scale")
+            a = self._ann_struct(nets[0], keep)
+            check(lib.qgx_generator_create_ann(C.byref(a), float(self.x_std[0]), float(self.y_std[0]), device,
+                                               C.byref(self._h)))
+            self.n_in = 1
+            return
         if self.unet:
             if kind != 'gan' or len(nets) > 2:
                 raise ValueError("the U-Net generator is a CGAN generator ('gan'), optionally with one regression net")
@@ -77,6 +87,21 @@ class Generator:
                 getattr(w, field)[i] = a.ctypes.data
 
     @staticmethod
+    def _ann_struct(net, keep):
+        """weights.ann_from_state_dict dict -> qgx_ann_weights (host pointers into `keep`)"""
+        a = _lib.qgx_ann_weights()
+        hidden = list(net['hidden'])
+        a.stencil_size, a.n_hidden, a.scale_invariant = int(net['stencil_size']), len(hidden), int(bool(net['scale_invariant']))
+        for l, h in enumerate(hidden[:4]):
+            a.hidden[l] = int(h)
+        for l in range(min(len(hidden) + 1, 5)):
+            w = np.ascontiguousarray(net['w'][l], dtype=np.float32)
+            b = np.ascontiguousarray(net['b'][l], dtype=np.float32)
+            keep += [w, b]
+            a.w[l], a.b[l] = w.ctypes.data, b.ctypes.data
+        return a
+
+    @staticmethod
     def _unet_struct(net, keep):
         """flat DeepInversionGenerator(4, 2) state dict -> qgx_unet_weights (host pointers into `keep`)"""
         from .weights import UNET_UNITS, UNET_UPS
@@ -105,8 +130,8 @@ class Generator:
 
     @property
     def noise_dtype(self):
-        """element type of the latent noise z; None for 'ols' (no noise)"""
-        if self.kind == 'ols':
+        """element type of the latent noise z; None for 'ols' and 'ann' (no noise)"""
+        if self.kind in self.NOISE_FREE:
             return None
         return torch.float64 if self.kind == 'gz' else torch.float32
 
@@ -192,12 +217,12 @@ class Generator:
         return out
 
     def forward(self, q, z=None, demean=True, out=None):
-        """q: (B,2,N,N) float64 cuda; z: (B,2,N,N) float32 (float64 for gz; 'ols' takes none) -> S (B,2,N,N) float64."""
+        """q: (B,2,N,N) float64 cuda; z: (B,2,N,N) float32 (float64 for gz; 'ols' and 'ann' take none) -> S (B,2,N,N) float64."""
         assert q.is_cuda and q.dtype == torch.float64 and q.is_contiguous() and q.dim() == 4
         B, _, N, _ = q.shape
-        if self.kind == 'ols':
+        if self.kind in self.NOISE_FREE:
             if z is not None:
-                raise ValueError("the 'ols' generator takes no latent noise")
+                raise ValueError(f"the {self.kind!r} generator takes no latent noise")
         else:
             assert z is not None and z.is_cuda and z.dtype == self.noise_dtype and z.is_contiguous()
             assert z.numel() == q.numel()
@@ -212,14 +237,15 @@ class Generator:
 
     def cnn_forward(self, x, inet=0):
         """Raw net forward: x (B,n_in,N,N) float32 -> (B,2,N,N) float32 (net 0: the AndrewCNN or U-Net generator, 4 channels;
-        'gz' / 'ols': 2 channels)."""
+        'gz' / 'ols': 2 channels; 'ann': the stencil network on (B,1,N,N) images normalised by x_scale -> (B,1,N,N))."""
         n_in = 2 if (self.kind in ('gz', 'ols') or inet == 1) else 4   # net 1 of a GAN / VAE generator: the regression net
+        n_in, n_out = (1, 1) if self.kind == 'ann' else (n_in, 2)
         B, _, N, _ = x.shape
         if self.unet and inet == 0 and N not in (32, 48, 64, 96, 128):
             raise ValueError(f'the U-Net generator runs on N = 32, 48, 64, 96 or 128, not {N}')
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == n_in
         B, _, N, _ = x.shape
-        y = torch.empty((B, 2, N, N), dtype=torch.float32, device=x.device)
+        y = torch.empty((B, n_out, N, N), dtype=torch.float32, device=x.device)
 
         def launch():
             check(lib.qgx_cnn_forward(self._h, inet, _ptr(x), _ptr(y), B, N, _stream()))

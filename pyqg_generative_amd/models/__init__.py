@@ -3,5 +3,6 @@ from .cgan_regression import CGANRegression
 from .cvae_regression import CVAERegression
 from .mean_var_model import MeanVarModel
 from .ols_model import OLSModel
+from .ann_model import ANNModel
 
-__all__ = ['Parameterization', 'CGANRegression', 'CVAERegression', 'MeanVarModel', 'OLSModel']
+__all__ = ['Parameterization', 'CGANRegression', 'CVAERegression', 'MeanVarModel', 'OLSModel', 'ANNModel']

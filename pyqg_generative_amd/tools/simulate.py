@@ -241,8 +241,9 @@ def load_parameterization(folder='model', model_weight=1.0, device=0):
     its constructor arguments; the model is built from ``folder`` on ``device``."""
     import json
     import os
-    from ..models import OLSModel, MeanVarModel, CGANRegression, CVAERegression
-    classes = {c.__name__: c for c in (OLSModel, MeanVarModel, CGANRegression, CVAERegression)}
+    from ..models import OLSModel, MeanVarModel, CGANRegression, CVAERegression, ANNModel
+    # ANNModel: the reference's simulate.py does not import it; its folders load here all the same
+    classes = {c.__name__: c for c in (OLSModel, MeanVarModel, CGANRegression, CVAERegression, ANNModel)}
     with open(os.path.join(folder, 'model_args.json')) as f:
         args = json.load(f)
     name = args.pop('model')

@@ -54,14 +54,82 @@ def read_scaler_std(path):
     return np.array(ast.literal_eval(d['std'])).astype('float32').reshape(-1)
 
 
+ANN_DEFAULTS = dict(stencil_size=3, hidden_channels=[24, 24], scale_invariant=False)   # ANNModel's (ann_model.py:18)
+
+
+def ann_from_state_dict(sd, stencil_size=3, hidden_channels=(24, 24), scale_invariant=False):
+    """ANN state_dict (cnn_tools.py:184-210: keys layers.{2l}.weight (out, in) / layers.{2l}.bias, l = 0 .. len(hidden)) ->
+    dict(stencil_size, hidden, scale_invariant, w, b), float32.  The shapes must be those of ANN(s*s, 1, hidden_channels):
+    anything else raises ValueError."""
+    get = lambda k: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], 'detach') else sd[k], dtype=np.float32)
+    s, hidden = int(stencil_size), [int(h) for h in hidden_channels]
+    widths = [s * s] + hidden + [1]
+    want = {}
+    for l in range(len(widths) - 1):
+        want[f'layers.{2 * l}.weight'] = (widths[l + 1], widths[l])
+        want[f'layers.{2 * l}.bias'] = (widths[l + 1],)
+    if set(sd) != set(want):
+        raise ValueError(f'ANN state dict keys {sorted(sd)} are not those of ANN({s * s}, 1, {hidden}): {sorted(want)}')
+    for k, shape in want.items():
+        if tuple(get(k).shape) != shape:
+            raise ValueError(f'{k}: shape {tuple(get(k).shape)}, ANN({s * s}, 1, {hidden}) has {shape}')
+    n = len(widths) - 1
+    return dict(stencil_size=s, hidden=hidden, scale_invariant=bool(scale_invariant),
+                w=[get(f'layers.{2 * l}.weight') for l in range(n)], b=[get(f'layers.{2 * l}.bias') for l in range(n)])
+
+
+def is_ann_state_dict(sd):
+    return 'layers.0.weight' in sd
+
+
+def read_ann_scale(folder):
+    """scale.json of an ANNModel folder (ann_model.py:61-62, 71-75) -> (x_scale, y_scale) as Python floats"""
+    with open(os.path.join(folder, 'scale.json')) as f:
+        d = json.load(f)
+    return float(d['x_scale']), float(d['y_scale'])
+
+
+def load_ann_folder(folder, stencil_size=None, hidden_channels=None, scale_invariant=None):
+    """ANNModel folder -> ([net], x_scale, y_scale): net.pt, scale.json, and the architecture from the arguments, else from
+    model_args.json (save_model_args, cnn_tools.py:21-25), else ANNModel's defaults"""
+    import torch
+    args = dict(ANN_DEFAULTS)
+    path = os.path.join(folder, 'model_args.json')
+    if os.path.exists(path):
+        with open(path) as f:
+            args.update({k: v for k, v in json.load(f).items() if k in ANN_DEFAULTS})
+    for k, v in (('stencil_size', stencil_size), ('hidden_channels', hidden_channels), ('scale_invariant', scale_invariant)):
+        if v is not None:
+            args[k] = v
+    sd = torch.load(os.path.join(folder, 'net.pt'), map_location='cpu', weights_only=True)
+    xs, ys = read_ann_scale(folder)
+    return [ann_from_state_dict(sd, **args)], xs, ys
+
+
+def synthetic_ann(stencil_size=3, hidden_channels=(24, 24), scale_invariant=False, seed=0):
+    """Seeded ANN weights with nn.Linear's initialisation range U(-1/sqrt(in), 1/sqrt(in))."""
+    rs = np.random.RandomState(seed)
+    widths = [stencil_size * stencil_size] + list(hidden_channels) + [1]
+    w, b = [], []
+    for l in range(len(widths) - 1):
+        k = 1.0 / np.sqrt(widths[l])
+        w.append(rs.uniform(-k, k, (widths[l + 1], widths[l])).astype(np.float32))
+        b.append(rs.uniform(-k, k, widths[l + 1]).astype(np.float32))
+    return dict(stencil_size=int(stencil_size), hidden=[int(h) for h in hidden_channels],
+                scale_invariant=bool(scale_invariant), w=w, b=b)
+
+
 def load_folder(folder, kind, regression=False, generator='Andrew'):
     """Reference model folder -> (nets, x_std, y_std).  kind: 'gan' | 'vae' | 'gz' | 'ols' (OLSModel: net.pt,
-    ols_model.py:59-66); regression ('gan' / 'vae' trained with
+    ols_model.py:59-66) | 'ann' (ANNModel: net.pt, scale.json, ann_model.py:68-77 — see load_ann_folder; x_std, y_std are
+    the scalars x_scale, y_scale); regression ('gan' / 'vae' trained with
     regression != 'None'): the folder also holds net_mean.pt (cgan_regression.py:98-101, cvae_regression.py:75-76).
     generator='DeepInversion' (CGAN only, cgan_regression.py:50-53): G.pt is the U-Net, nets[0] its unet_from_state_dict."""
     import torch
     if generator not in ('Andrew', 'DeepInversion') or (generator == 'DeepInversion' and kind != 'gan'):
         raise ValueError(f'generator={generator!r} is not available for kind {kind!r}')
+    if kind == 'ann':
+        return load_ann_folder(folder)
     files = {'gan': ['G.pt'], 'vae': ['decoder.pt'], 'gz': ['net_mean.pt', 'net_var.pt'], 'ols': ['net.pt']}[kind]
     if regression and kind in ('gan', 'vae'):
         files = files + ['net_mean.pt']

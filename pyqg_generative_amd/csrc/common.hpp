@@ -115,7 +115,7 @@ struct GenFuse {
     const float *y1 = nullptr;      // regression net's output, summed with y in float32 before the scaling (k_finish<FIN_SUM>)
     float ys[2] = {1.f, 1.f};
     int demean = 0;
-    unsigned *range = nullptr;      // the generator's range-guard words (conv.hip)
+    unsigned *range = nullptr;      // the generator's range-guard words (generator.hpp)
     float *X = nullptr;
     float *z = nullptr;
     float xs[2] = {1.f, 1.f};
@@ -229,7 +229,7 @@ struct qgx_model {
 };
 
 namespace qgx {
-// generator entry used by the stepper (conv.hip)
+// generator entry used by the stepper (generator.hip)
 // optional sampler update z <- a z + b xi folded into the generator's input kernel
 struct NoiseUpdate {
     const void *xi_ext;      // external draw or nullptr (Philox)

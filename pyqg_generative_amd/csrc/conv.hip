@@ -4,9 +4,8 @@
 // Replaces AndrewCNN.forward evaluated through apply_function
 // (pyqg_generative/tools/cnn_tools.py:79-98 make_block = Conv2d('same', circular) -> ReLU ->
 // BatchNorm2d; :125-176 channels [n_in,128,64,32,32,32,32,32,n_out], kernels [5,5,3,3,3,3,3,3];
-// :702-735 eval mode, no grad) and the model wrappers
-// models/cgan_regression.py:157-162, cvae_regression.py:131-136, mean_var_model.py:105-109,
-// plus the per-layer de-mean of models/parameterization.py:25.
+// :702-735 eval mode, no grad).  The handle, the model wrappers around the nets and the C ABI that is not
+// AndrewCNN-specific are in generator.hip; generator.hpp holds the handle and the functions between the two files.
 //
 // Data layout: activations NHWC float32 (B, N, N, C) so that the GEMM K index
 // (tap, input channel) is contiguous per pixel; the first layer reads a small planar
@@ -18,13 +17,11 @@
 // MFMA 32x32x2 f32: A[i = lane&31][k = lane>>5] = pixel x K, B[k][j = lane&31] = K x cout.
 // Lane half h consumes K indices 8g+4h .. 8g+4h+3 of every group of 8 with one 16-byte
 // read of A (LDS) and of B (packed weights, L2 resident) feeding 4 consecutive MFMAs.
-#include "common.hpp"
+#include "generator.hpp"
 #include <unordered_map>
-#include "philox.hpp"
 #include <cmath>
 #include <utility>
 #include <functional>
-#include <new>
 
 namespace qgx {
 
@@ -47,6 +44,7 @@ struct ConvArgs {
 // conv_wino2.hip (a translation unit of its own: built without the SLP vectoriser): the same layer with the input transform
 // under the MFMAs, bit-identical to k_convw, for the tile shapes where it is faster; *done = false: take k_convw
 int launch_convw2(int N, int TW, int R, const ConvWArgs &a, int total_tiles, hipStream_t st, bool *done);
+bool convw2_takes(int N, int TW, int R);     // the tile shapes k_convw2 is built for
 // Kernel variants that were measured slower than the ones above (k_convh generic / plain f16, k_convh_res,
 // k_convh3 on 16x16x32 MFMAs, k_convh4 with full-line chunks) are compiled only into the A/B library
 // (`make ab` -> libqgx_ab.so, bench_tools/ab_conv.py): the product library carries one path per layer and size.
@@ -553,7 +551,6 @@ __global__ void k_conv_reduce(const float *partial, int nsplit, size_t npix_tota
 // ---- last layer (32 -> n_out <= 2, 3x3): VALU kernel ---------------------------------------------
 // Two output channels would fill 2 of 32 MFMA columns; on the vector ALUs the 288x2 dot products per
 // pixel run at full useful rate: one thread per pixel, weights broadcast from scalar registers.
-struct LastWeights { float w[3 * 3 * 32 * 2]; };   // [tap][c][2], passed BY VALUE: kernarg -> scalar loads
 
 // PARTS = 4 (single-row tiles of 64 pixels, i.e. one or two members at 64 x 64): the four waves split the input
 // channels of the same 64 pixels and combine through LDS — a 4x shorter dependent FMA chain per thread
@@ -620,54 +617,6 @@ __global__ __launch_bounds__(256) void k_conv_last(ConvArgs a, LastWeights lw) {
     }
 }
 
-// ---- small pointwise kernels around the CNN ---------------------------------------------
-// X = [float(q)/x_std, z]  (cgan_regression.py:158 + generate :133-137)
-// largest |x| of the network input, for the f16x3 range guard: a NaN counts as infinity; non-negative floats
-// order like their bit patterns, so one atomicMax on the bits per wave keeps the running maximum
-__device__ __forceinline__ void input_absmax(float m, unsigned *range) {
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o));
-    // the running maximum settles after the first launches: read it, and only a new record costs an atomic
-    if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __builtin_nontemporal_load(range + 1)) atomicMax(range + 1, __float_as_uint(m));
-}
-__device__ __forceinline__ float abs_or_inf(float x) { return x != x ? __uint_as_float(0x7f800000u) : fabsf(x); }
-
-__global__ void k_prep_input(const double *q, const float *z, float *X, int n_in, int npix, float xs0, float xs1,
-                             unsigned *range) {
-    const int b = blockIdx.y;
-    float m = 0.f;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
-        const size_t qo = (size_t)b * 2 * npix + i;
-        float *x = X + (size_t)b * n_in * npix + i;
-        const float x0 = (float)q[qo] / xs0, x1 = (float)q[qo + npix] / xs1;
-        x[0] = x0;
-        x[npix] = x1;
-        m = fmaxf(m, fmaxf(abs_or_inf(x0), abs_or_inf(x1)));
-        if (n_in == 4) {
-            const float z0 = z[qo], z1 = z[qo + npix];
-            x[2 * (size_t)npix] = z0;
-            x[3 * (size_t)npix] = z1;
-            m = fmaxf(m, fmaxf(abs_or_inf(z0), abs_or_inf(z1)));
-        }
-    }
-    input_absmax(m, range);
-}
-
-// the normalised PV of every member (channels 0, 1 of the generator's 4-channel input) as the 2-channel input of the
-// regression net (cgan_regression.py:159-161: apply_function(self.net_mean, X) on the same X)
-__global__ void k_take2(const float *X, float *X2, int npix2) {      // npix2 = 2 npix, a multiple of 4
-    const int b = blockIdx.y;
-    const f32x4 *src = reinterpret_cast<const f32x4 *>(X + (size_t)b * 2 * npix2);
-    f32x4 *dst = reinterpret_cast<f32x4 *>(X2 + (size_t)b * npix2);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npix2 / 4; i += gridDim.x * blockDim.x) dst[i] = src[i];
-}
-
-__global__ void k_absmax(const float *x, size_t n, unsigned *range) {
-    float m = 0.f;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        m = fmaxf(m, abs_or_inf(x[i]));
-    input_absmax(m, range);
-}
-
 // out[0] = max |a - b|, out[1] = max |b| (float bits; calibration of the Winograd layer against the exact-f32 path)
 __global__ void k_absdiff_max(const float *a, const float *b, size_t n, unsigned *out) {
     float d = 0.f, m = 0.f;
@@ -679,227 +628,7 @@ __global__ void k_absdiff_max(const float *a, const float *b, size_t n, unsigned
     if ((threadIdx.x & 63) == 0) { atomicMax(out, __float_as_uint(d)); atomicMax(out + 1, __float_as_uint(m)); }
 }
 
-// Fused sampler update + input assembly of one online step (GAN / VAE):
-//   z <- a z + b xi  (float; xi from Philox or the external draw), X = [float(q)/x_std, z]
-// One thread per quad of 4 consecutive elements of the (2,N,N) member field.
-__global__ void k_prep_noise(const double *q, float *z, const float *xi_ext, float *X, int npix, float xs0,
-                             float xs1, uint64_t seed, uint64_t member_offset, uint64_t step, float a, float b,
-                             unsigned *range) {
-    const int member = blockIdx.y;
-    const int quads = 2 * npix / 4;
-    const int quad = blockIdx.x * blockDim.x + threadIdx.x;
-    float m = 0.f;
-    if (quad < quads) {
-        const size_t o = (size_t)member * 2 * npix + 4 * (size_t)quad;
-        float x[4];
-        if (xi_ext) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[e] = xi_ext[o + e];
-        } else {
-            philox_normal4(seed, member_offset + member, step, (uint32_t)quad, x);
-        }
-        float *Xm = X + (size_t)member * 4 * npix;
-        const int i = 4 * quad;                          // flat index in (2, npix); npix % 4 == 0
-        const float xs = i < npix ? xs0 : xs1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float zn = a == 0.f ? b * x[e] : a * z[o + e] + b * x[e];
-            z[o + e] = zn;
-            Xm[2 * (size_t)npix + i + e] = zn;
-            const float xq = (float)q[o + e] / xs;
-            Xm[i + e] = xq;
-            m = fmaxf(m, fmaxf(abs_or_inf(zn), abs_or_inf(xq)));
-        }
-    }
-    input_absmax(m, range);
-}
-
-// Fused output scaling + per-layer de-mean: one workgroup per (member, layer).
-//   GAN/VAE: S = double(y * y_std)                         (cgan_regression.py:162)
-//   GZ:      S = (mean + z sqrt(softplus(var))) * y_std    (mean_var_model.py:14-17,105-109)
-//   GAN/VAE with regression != 'None': S = double((y + net_mean(x)) * y_std), the sum in float32
-//                                                          (cgan_regression.py:159-162, cvae_regression.py:133-136)
-//   then S -= mean_{y,x} S                                 (parameterization.py:25)
-enum { FIN_PLAIN = 0, FIN_GZ = 1, FIN_SUM = 2 };
-template <int MODE>
-__global__ __launch_bounds__(1024) void k_finish(const float *y0, const float *y1, const double *z, double *S, int npix, float ys0,
-                                                 float ys1, int demean, unsigned *range) {
-    __shared__ double sm[16];
-    __shared__ double mean_s;
-    const size_t o = (size_t)blockIdx.x * npix;
-    const float ys = (blockIdx.x & 1) ? ys1 : ys0;
-    auto value = [&](int i) -> double {
-        if constexpr (MODE == FIN_GZ) {
-            const float vr = y1[o + i];
-            const float sp = vr > 20.f ? vr : log1pf(expf(vr));
-            return ((double)y0[o + i] + z[o + i] * (double)sqrtf(sp)) * (double)ys;
-        } else if constexpr (MODE == FIN_SUM) {
-            return (double)((y0[o + i] + y1[o + i]) * ys);
-        } else {
-            return (double)(y0[o + i] * ys);
-        }
-    };
-    // one workgroup per (member, layer) is a short latency chain: 1024 threads, and the values are read ONCE
-    // (kept in registers between the mean and the store for grids up to 128 x 128)
-    constexpr int KEEP = 16;
-    double keep[KEEP];
-    const bool cached = npix <= KEEP * (int)blockDim.x;
-    double acc = 0.0;
-    if (cached) {
-#pragma unroll
-        for (int u = 0; u < KEEP; ++u) {
-            const int i = u * blockDim.x + threadIdx.x;
-            keep[u] = i < npix ? value(i) : 0.0;
-            acc += keep[u];
-        }
-    } else if (demean) {
-        for (int i = threadIdx.x; i < npix; i += blockDim.x) acc += value(i);
-    }
-    double mu = 0.0;
-    if (demean) {
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-        if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0;
-            for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sm[w];
-            mean_s = t / (double)npix;
-        }
-        __syncthreads();
-        mu = mean_s;
-    }
-    if (cached) {
-        bool bad = false;
-#pragma unroll
-        for (int u = 0; u < KEEP; ++u) {
-            const int i = u * blockDim.x + threadIdx.x;
-            if (i < npix) S[o + i] = keep[u] - mu;
-            bad |= !(fabs(keep[u]) <= 1.79e308);
-        }
-        if (bad) atomicOr(range, 0x80000000u);      // a non-finite forcing never reaches the model unnoticed
-    } else {
-        bool bad = false;
-        for (int i = threadIdx.x; i < npix; i += blockDim.x) {
-            const double val = value(i);
-            S[o + i] = val - mu;
-            bad |= !(fabs(val) <= 1.79e308);
-        }
-        if (bad) atomicOr(range, 0x80000000u);
-    }
-}
-
-// running first and second moments over Monte-Carlo samples (generate_mean_var, cgan_regression.py:139-146)
-__global__ void k_moments(const float *y, double *sum, double *sumsq, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const double v = (double)y[i];
-        sum[i] += v;
-        sumsq[i] += v * v;
-    }
-}
-
 // ---- host side ---------------------------------------------------------------------------
-struct LayerHost {
-    int cin, cout, ks, coutp, cc, ngroups;
-    LastWeights wv_host;   // last layer, VALU kernel layout (kernel argument)
-    float *wl16 = nullptr, *wl8 = nullptr;   // k_conv3 layout [chunk][tap][g8][h][coutp][4], 16- / 8-channel chunks
-    float *w = nullptr, *w32 = nullptr, *bias = nullptr, *scale = nullptr, *shift = nullptr;   // w: 16-ch chunks (or planar), w32: 32-ch chunks
-    void *wh[2] = {nullptr, nullptr};        // conv_half.hpp layouts: [0] f16 (NS = 1), [1] f16 hi/lo (NS = 2)
-    float wh_unscale[2] = {1.f, 1.f};        // 2^-s of the power-of-two weight pre-scale
-    // layer 2 with layer 1's BatchNorm folded in (W' = W alpha[c_in], b' = b + sum W beta'[c_in]; exact under circular
-    // padding): layer 1 then stores ReLU output, half of which is exactly zero -> a sparser MFMA operand
-    void *whF = nullptr, *wh16F = nullptr; float whF_unscale = 1.f; float *biasF = nullptr;
-    // layer 2 as a 1-D Winograd convolution F(4, 5) along x (conv_wino.hpp): transformed weights, [0] plain, [1] with layer
-    // 1's BatchNorm folded in; per-position 2^-s of the power-of-two pre-scale
-    void *ww[2] = {nullptr, nullptr};
-    float ww_unscale[2][8] = {{1, 1, 1, 1, 1, 1, 1, 1}, {1, 1, 1, 1, 1, 1, 1, 1}};
-    float *ones = nullptr, *zeros = nullptr; // layer 1: identity BatchNorm for the folded variant
-    void *wh16 = nullptr;                    // k_convh3 (16x16x32 MFMA): [chunk32][tap][part][octet][cout][8] f16
-    void *whf = nullptr;                     // first layer, f16x3: [step][part][h][128][8] f16
-    float whf_unscale = 1.f;
-};
-struct NetHost {
-    int n_in, n_out;
-    LayerHost L[8];
-};
-
-}  // namespace qgx
-
-struct qgx_generator {
-    int kind, device, n_nets;
-    qgx::UNet *unet = nullptr;     // qgx_generator_create_unet: net 0 is the DeepInversion U-Net (unet.hip), its workspace is actA
-    qgx::Ann *ann = nullptr;       // qgx_generator_create_ann: the pointwise stencil network (ann.hip); its only workspace is Y0
-    qgx::NetHost nets[2];
-    float x_std[2], y_std[2];
-    // workspace (grown on demand, outside any captured region)
-    size_t cap_elems = 0;          // capacity in units of B*N*N pixels
-    float *actA = nullptr, *actB = nullptr, *X = nullptr, *Y0 = nullptr, *Y1 = nullptr;
-    float *part = nullptr;         // split-K partial sums of the small-ensemble path
-    size_t part_elems = 0;
-    // second workspace: the other half of an ensemble stepped in halves on two streams (model.hip::qgx_step); the members
-    // above are the ACTIVE set, generator_select_workspace swaps the two
-    struct Workspace { size_t cap_elems = 0, part_elems = 0; float *actA = nullptr, *actB = nullptr, *X = nullptr, *Y0 = nullptr, *Y1 = nullptr, *part = nullptr; } ws_other;
-    int ws_active = 0;
-    // optional per-layer timing with HIP events on the launch stream (bench.py roofline leg)
-    // kernel variant selection (qgx_generator_set_option; defaults = fastest measured)
-    int opt_cc = 32, opt_last_valu = 1, opt_first_split = 2, opt_v3 = -1, opt_small = 1;
-    unsigned long long *stamps = nullptr;   // diagnostic builds only
-    int stamp_layer = -1;
-    int opt_h2_tw32 = 0;           // 5x5 layer at 64 x 64: 16-row x 32-column tiles instead of 8 full rows
-    int opt_h2_x96 = 1;            // 3x3 layers at 96 x 96 as 8-wave workgroups on 16-row x 32-column tiles (-1.4 % of the step at 32 members, -3.6 % at 64)
-    int opt_h2_w8_min96 = 1024;    // 5x5 layer at 96 x 96: minimum tile count for the 8-wave x-tiled kernel
-    int opt_h2_w8 = 3;             // k_convh2 as one 8-wave workgroup per CU: bit 0 the 5x5 layer, bit 1 the 3x3 layers (64 x 64)
-    int opt_prio_alt = 1;          // k_convh2 with two workgroups per CU: alternate their wave priority per tile
-    int opt_h4 = 0;                // 5x5 layer: k_convh4 (full-line patch chunks, 8 waves, R = 8)
-    int opt_h2_grid = 0;           // k_convh2: persistent workgroups per launch (0 = one or two per CU by LDS size)
-    int opt_wino = 2;              // f16x3: the 5x5 layer as a 1-D Winograd convolution F(4, 5) along x (k_convw): 0 never, 1 on every
-                                   //   specialised grid, 2 = per grid size, where calibrate_wino() admitted it
-    int auto_wino_n[5] = {0, 0, 0, 0, 0};            //   ... what calibrate_wino() decided for N = 32, 48, 64, 96, 128 and the errors it measured
-    float wino_err_n[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    int opt_stop_layer = 0;        //   A/B library, debugging: return after this many layers (the activation buffers keep their outputs)
-    int opt_wino2 = 1;             //   ... as k_convw2 (conv_wino2.hpp: transform under the MFMAs, bit-identical) where that kernel exists; 0 = k_convw
-    int opt_wino_pl = 0;           //   A/B library: 1 = channel-planar layer-1 output and the MFMA input transform (measured: see wino_planar)
-    int opt_wino_exp = 0;          //   A/B library: timing experiments (conv_wino.hpp EXP)
-    int opt_h2_rows96 = 0;         // 3x3 layers at 96 x 96: tile rows, 0 = by tile-count quantisation, 12 (6 waves), 16 (8 waves)
-    int opt_wino_rows64 = 0;       //   ... its tile shape at 64 x 64, 128 x 128 and 32 x 32: 0 = by tile-count quantisation, 4 = the half-height
-                                   //   shape (4 x 64 tiles; 8 x 32 at 32 x 32), 8 = the full one
-    int opt_wino_rows96 = 0;       //   ... its tile rows at 96 x 96: 0 = by tile-count quantisation (launch_convw), 12, 16
-    int opt_wino_min_tiles = 48;   //   ... from this many full-height tiles on (measured crossovers, bench_tools/ab_conv.py: with the half-height
-                                   //   shapes the Winograd kernel is ahead of the 25-tap kernels from 6 members at 64 x 64, 4 at 96 x 96, 24 at 32 x 32)
-    int opt_fold = 1;              // f16x3: layer 1 stores ReLU output, its BatchNorm is folded into layer 2's weights
-    int opt_part_max_tiles = 96;   // f16x3: split K on the wide layers below this many quarter-height tiles (crossover against the Winograd
-                                   //   layer's half-height shape: 6 members at 64 x 64 — forward 166.8 -> 158.0 us —, 4 at 96 x 96: 217.5 -> 184.3)
-    int opt_last_rows = 0;         // VALU last layer: rows per workgroup (0 = automatic)
-    int opt_h3 = 0;                // 5x5 layer on 16x16x32 MFMAs (k_convh3): measured no faster in the full kernel
-    int opt_half_min_tiles = 1;
-    int opt_tiny_pairs = 7;        // tiny ensembles at 64 x 64 (split-K path): bit 0 layers (7, 8), bit 1 layers (5, 6), bit 2 layers (3, 4) as ONE fused launch on 2-row strips
-    int opt_pair_lp = 1;           // A/B library only: 0 = the pair kernels fetch the two halves of a line in different chunk iterations
-    int opt_small_tiles = 1;       // 64 x 64, at most 4 members: half-height tiles (small_tiles())
-    int opt_fuse96 = 2;            // ... at 96 x 96 (4-row strips): bit 0 (5,6), 1 (7,8)
-    int opt_fuse = 3;              // f16x3, 64x64: 3x3 layers fused pairwise (k_convh_pair): bit 0 (5,6), 1 (7,8), 2 (3,4)
-    int opt_pair = 1;              // 3x3 k_convh2: fetch both 64-byte halves of a pixel's 128-byte line together
-    int opt_h2 = 3;                // bit 1: k_convh2 for the 5x5 layer, bit 0: for the 3x3 layers (64x64 grids)
-    int opt_res = 1;               // f16x3 3x3 layers: resident-weight kernel where its tile fits in LDS
-    int opt_member_chunk = 0;      // 16-bit path: members per sub-batch (0 = whole ensemble)
-    int opt_half_nw = 8;           // 16-bit hidden layers: 4 waves x 2 workgroups per CU, or 8 x 1
-    int opt_first_h = 1;           // f16x3 path: first layer on the 16-bit cores too (0: exact-f32 MFMA first layer)
-    int opt_precision = 3;         // 0 = exact f32 MFMA, 1 = f16 MFMA, 3 = f16x3 split (f32-class accuracy; default
-                                   // wherever the ensemble fills the 8-wave tiles, see half_path_ok)
-    float opt_ascale = 1.f;        // power-of-two pre-scale of stored 16-bit activations (chosen by calibrate())
-    // f16x3 range guard (conv_half.hpp::range_guard): [0] sticky flags — bit l: layer l stored a value beyond the f16
-    // range, bit 31: non-finite forcing; [1] bits of the largest |network input| seen
-    unsigned *range_dev = nullptr;
-    unsigned *calib_dev = nullptr; // calibration only: per-layer max |activation| of the exact-f32 evaluation
-    float calib_max[10] = {0};     // [0..6] stored (post-BatchNorm) activations, [8] layer 1 before its BatchNorm
-    int auto_precision = 3, auto_fold = 1, auto_ascale_log2 = 0;   // what calibrate() decided
-    int prof_layer = -1;
-    int prof_every = 1;                 // bracket every n-th launch of the profiled layer ("prof_every" option)
-    long prof_seen = 0;
-    std::vector<hipEvent_t> prof_ev;    // pairs (start, stop)
-    size_t prof_used = 0;
-};
-
-namespace qgx {
-
 // hipFuncSetAttribute takes microseconds of host time; the single-member step is a chain of 5-15 us kernels whose
 // launches the host has to keep ahead of: the dynamic-LDS cap of a kernel is raised once per kernel, device and host
 // thread, not once per launch (rocprofv3: 14 launches / 116 us of kernels per step were taking 128 us of wall time)
@@ -1180,6 +909,21 @@ static int pack_layer(LayerHost &L, int li, const qgx_cnn_weights *w, bool plana
     return QGX_OK;
 }
 
+int cnn_pack_net(NetHost &net, const qgx_cnn_weights *w) {
+    net.n_in = w->n_in; net.n_out = w->n_out;
+    for (int li = 0; li < 8; ++li) {
+        LayerHost &L = net.L[li];
+        L.cin = li == 0 ? w->n_in : HID[li - 1];
+        L.cout = li == 7 ? w->n_out : HID[li];
+        L.ks = KSZ[li];
+        if (const int rc = pack_layer(L, li, w, li == 0)) return rc;
+    }
+    return QGX_OK;
+}
+void cnn_free_net(NetHost &net) {
+    for (LayerHost &L : net.L) L.free_device();
+}
+
 // Very small ensembles at 64 x 64 (a single member above all: BASELINE configs[1]) are chains of launch latencies; with 4-row
 // tiles a member is 16 workgroups, with 2-row tiles 32 with half the K loop each (bit-identical: the tile shape does not enter
 // the summation order).  Measured at one member: the 5x5 layer's split-K kernel + combine 23.6 -> 19.9 us, layer 3 12.1 -> 10.9.
@@ -1191,29 +935,37 @@ static int choose_rows(int N) {
     return 0;
 }
 
-static int prof_begin(qgx_generator *g, int layer, hipStream_t st, hipEvent_t &stop) {
-    stop = nullptr;
-    if (g->prof_layer != layer) return QGX_OK;
-    // an event pair costs ~6 us of idle GPU on each side of the kernel: bracket every prof_every-th launch only
-    if (g->prof_every > 1 && (g->prof_seen++ % g->prof_every) != 0) return QGX_OK;
-    if (g->prof_used + 2 > g->prof_ev.size()) {
-        for (int i = 0; i < 2; ++i) {
-            hipEvent_t e;
-            QGX_HIP(hipEventCreate(&e));
-            g->prof_ev.push_back(e);
+// The profiler's bracket around one launcher: begin() records the start event of a pair when `layer` is the profiled one,
+// and the stop event is recorded when the scope is left on ANY path, so that qgx_generator_profile_read never meets a
+// start event whose stop event was not recorded.
+struct ProfScope {
+    hipEvent_t stop = nullptr;
+    hipStream_t st = nullptr;
+    int begin(qgx_generator *g, int layer, hipStream_t stream) {
+        if (g->prof_layer != layer) return QGX_OK;
+        // an event pair costs ~6 us of idle GPU on each side of the kernel: bracket every prof_every-th launch only
+        if (g->prof_every > 1 && (g->prof_seen++ % g->prof_every) != 0) return QGX_OK;
+        if (g->prof_used + 2 > g->prof_ev.size()) {
+            for (int i = 0; i < 2; ++i) {
+                hipEvent_t e;
+                QGX_HIP(hipEventCreate(&e));
+                g->prof_ev.push_back(e);
+            }
         }
+        QGX_HIP(hipEventRecord(g->prof_ev[g->prof_used], stream));
+        stop = g->prof_ev[g->prof_used + 1];
+        st = stream;
+        g->prof_used += 2;
+        return QGX_OK;
     }
-    QGX_HIP(hipEventRecord(g->prof_ev[g->prof_used], st));
-    stop = g->prof_ev[g->prof_used + 1];
-    g->prof_used += 2;
-    return QGX_OK;
-}
+    ~ProfScope() { if (stop) (void)hipEventRecord(stop, st); }
+};
 
 template <int CIN, int COUT, int KS, int CC, bool PLANAR_IN, bool FINAL, int CSPLIT = 1, int OUTH = 0>
 static int launch_conv(qgx_generator *g, int layer, const LayerHost &L, const float *in, float *out, int B,
                        int N, int cout_real, hipStream_t st) {
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
     const int R = choose_rows(N);
     QGX_REQUIRE(R > 0 && N % R == 0, "generator: unsupported grid size N=%d", N);
     const int ntiles = R * N / 32;
@@ -1235,7 +987,6 @@ static int launch_conv(qgx_generator *g, int layer, const LayerHost &L, const fl
         hipLaunchKernelGGL(kern, grid, block, lds, st, a);
     }
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 
@@ -1261,17 +1012,13 @@ static int launch_conv_small(qgx_generator *g, int layer, const LayerHost &L, co
                              int N, hipStream_t st) {
     const int R = rows_small(N);                   // <= 4 M-tiles of 32 pixels
     const int nsplit = CIN >= 64 ? CIN / CC : 1;
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
     const size_t npix = (size_t)B * N * N;
-    if (nsplit > 1 && g->part_elems < npix * COUT * nsplit) {
-        if (g->part) (void)hipFree(g->part);
-        g->part = nullptr; g->part_elems = 0;
-        QGX_HIP(hipMalloc((void **)&g->part, npix * COUT * nsplit * sizeof(float)));
-        g->part_elems = npix * COUT * nsplit;
-    }
+    if (nsplit > 1) { if (const int rc = generator_reserve_part(g, npix * COUT * nsplit)) return rc; }
+    float *const part = g->work().part;
     ConvArgs a = {};
-    a.in = in; a.out = nsplit > 1 ? g->part : out; a.w = CC == 32 ? L.w32 : L.w; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
+    a.in = in; a.out = nsplit > 1 ? part : out; a.w = CC == 32 ? L.w32 : L.w; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
     a.N = N; a.R = R; a.cout_real = COUT; a.npix_total = npix;
     const size_t lds = (size_t)(R + KS - 1) * N * (CC + 4) * sizeof(float);
     dim3 grid(B * (N / R), nsplit), block(256);
@@ -1281,7 +1028,7 @@ static int launch_conv_small(qgx_generator *g, int layer, const LayerHost &L, co
         hipLaunchKernelGGL(kern, grid, block, lds, st, a);
         const size_t n4 = npix * COUT / 4;
         hipLaunchKernelGGL(k_conv_reduce<COUT>, dim3((unsigned)((n4 + 255) / 256 > 1024 ? 1024 : (n4 + 255) / 256)), dim3(256),
-                           0, st, (const float *)g->part, nsplit, npix, (const float *)L.bias, (const float *)L.scale,
+                           0, st, (const float *)part, nsplit, npix, (const float *)L.bias, (const float *)L.scale,
                            (const float *)L.shift, out);
     } else {
         auto kern = k_conv<CIN, COUT, KS, CC, 1, false, false, 1, false>;
@@ -1289,7 +1036,6 @@ static int launch_conv_small(qgx_generator *g, int layer, const LayerHost &L, co
         hipLaunchKernelGGL(kern, grid, block, lds, st, a);
     }
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 
@@ -1310,8 +1056,8 @@ static int launch_conv3(qgx_generator *g, int layer, const LayerHost &L, const f
     if (lds > 160 * 1024 - 256) return QGX_OK;
     const int PF4 = PR * N * (CC / 4);
     const int ppt = (((PF4 + NSL - 1) / NSL) + NW * 64 - 1) / (NW * 64);
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
     ConvArgs a = {};
     a.in = in; a.out = out; a.w = CC == 16 ? L.wl16 : L.wl8; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
     a.N = N; a.R = R; a.cout_real = COUT;
@@ -1334,7 +1080,6 @@ static int launch_conv3(qgx_generator *g, int layer, const LayerHost &L, const f
     else return QGX_OK;
 #undef QGX_L3
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     done = true;
     return QGX_OK;
 }
@@ -1379,8 +1124,8 @@ static int launch_conv_last(qgx_generator *g, const LayerHost &L, const float *i
                                                                  // load -> barrier -> compute -> store chain (-10..-20 %)
     if (g->opt_last_rows > 0 && N % g->opt_last_rows == 0) R = g->opt_last_rows;
     QGX_REQUIRE(R > 0 && N % R == 0, "generator: unsupported grid size N=%d", N);
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, 7, st, prof_stop); if (prc) return prc; }
+    ProfScope prof;
+    if (const int prc = prof.begin(g, 7, st)) return prc;
     ConvArgs a = {};
     a.in = in; a.out = out; a.w = nullptr; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
     a.N = N; a.R = R; a.cout_real = n_out;
@@ -1397,7 +1142,6 @@ static int launch_conv_last(qgx_generator *g, const LayerHost &L, const float *i
         hipLaunchKernelGGL(kern, dim3(B * (N / R)), dim3(256), lds, st, a, L.wv_host);
     }
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 
@@ -1437,6 +1181,17 @@ static bool half_path_ok(const qgx_generator *g, int B, int N) {
     return B * (N / R) >= g->opt_half_min_tiles;
 }
 
+// the fields every f16 / f16x3 hidden-layer launcher fills alike (the f16x3 weight layout unless the launcher says otherwise)
+static ConvHArgs convh_args(const qgx_generator *g, int layer, const LayerHost &L, const void *in, void *out, bool outf32, int N, int R) {
+    ConvHArgs a = {};
+    a.in = in; a.out = out; a.w = L.wh[1]; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
+    a.unscale = L.wh_unscale[1] / g->opt_ascale; a.ascale = outf32 ? 1.f : g->opt_ascale;
+    a.range = g->range_dev; a.range_bit = 1u << layer;
+    a.N = N; a.R = R;
+    a.stamps = layer == g->stamp_layer ? g->stamps : nullptr;
+    return a;
+}
+
 #ifdef QGX_AB
 template <int CIN, int COUT, int KS, int NS, bool OUTF32>
 static int launch_convh(qgx_generator *g, int layer, const LayerHost &L, const void *in, void *out, int B, int N,
@@ -1455,14 +1210,10 @@ static int launch_convh(qgx_generator *g, int layer, const LayerHost &L, const v
     const size_t lds = (size_t)PR * N * (four ? 64 : 80) + (size_t)2 * TPS * 4 * COUT * 16 + 3 * COUT * sizeof(float);
     QGX_REQUIRE(lds <= 160 * 1024 - 256 && (mtv == 2 || mtv == 3) && ntiles % nw == 0 && ppt <= 12,
                 "generator: 16-bit path tile shape unsupported for N=%d", N);
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
-    ConvHArgs a = {};
-    a.in = in; a.out = out; a.w = L.wh[NS - 1]; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
-    a.unscale = L.wh_unscale[NS - 1] / g->opt_ascale; a.ascale = OUTF32 ? 1.f : g->opt_ascale;
-    a.range = g->range_dev; a.range_bit = 1u << layer;
-    a.N = N; a.R = R;
-    a.stamps = layer == g->stamp_layer ? g->stamps : nullptr;
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
+    ConvHArgs a = convh_args(g, layer, L, in, out, OUTF32, N, R);
+    a.w = L.wh[NS - 1]; a.unscale = L.wh_unscale[NS - 1] / g->opt_ascale;
     const int total_tiles = B * (N / R);
     int grid = 256 * (lds * 2 <= 160 * 1024 ? 2 : 1);
     if (grid > total_tiles) grid = total_tiles;
@@ -1482,7 +1233,6 @@ static int launch_convh(qgx_generator *g, int layer, const LayerHost &L, const v
     }
 #undef QGX_LH
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 
@@ -1501,15 +1251,10 @@ static int launch_convh2_n(qgx_generator *g, int layer, const LayerHost &L, cons
     constexpr bool WDB = KS == 3;                                // double-buffered weight slice (3x3 layers)
     constexpr size_t lds = (size_t)PR * PW * 80 + (size_t)(WDB ? 2 : 1) * TPS * 4 * COUT * 16 + 3 * COUT * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS");
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
-    ConvHArgs a = {};
-    a.in = in; a.out = out; a.w = L.wh[1]; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
-    a.unscale = L.wh_unscale[1] / g->opt_ascale; a.ascale = OUTF32 ? 1.f : g->opt_ascale;
-    a.range = g->range_dev; a.range_bit = 1u << layer;
-    a.N = NN; a.R = R;
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
+    ConvHArgs a = convh_args(g, layer, L, in, out, OUTF32, NN, R);
     a.prio_alt = KS == 5 ? g->opt_prio_alt : (g->opt_prio_alt == 3 ? 3 : 0);      // measured: -2 % on the 5x5 layer, nothing on the 3x3 layers (3: by phase)
-    a.stamps = layer == g->stamp_layer ? g->stamps : nullptr;
     const int total_tiles = B * (NN / R);
     int grid = lds * 2 <= 160 * 1024 ? 512 : 256;
     if (g->opt_h2_grid > 0) grid = g->opt_h2_grid;
@@ -1520,7 +1265,6 @@ static int launch_convh2_n(qgx_generator *g, int layer, const LayerHost &L, cons
     { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, total_tiles);
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 
@@ -1534,20 +1278,13 @@ static int launch_convh2_part_n(qgx_generator *g, int layer, const LayerHost &L,
     constexpr bool WDB = KS == 3;
     constexpr size_t lds = (size_t)PR * PW * 80 + (size_t)(WDB ? 2 : 1) * TPS * 4 * COUT * 16 + 3 * COUT * sizeof(float);
     constexpr int nsplit = NCH >= 8 ? 8 : NCH;
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
     const size_t npix = (size_t)B * NN * NN;
-    if (g->part_elems < npix * COUT * nsplit) {
-        if (g->part) (void)hipFree(g->part);
-        g->part = nullptr; g->part_elems = 0;
-        QGX_HIP(hipMalloc((void **)&g->part, npix * COUT * nsplit * sizeof(float)));
-        g->part_elems = npix * COUT * nsplit;
-    }
-    ConvHArgs a = {};
-    a.in = in; a.out = g->part; a.w = L.wh[1]; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
-    a.unscale = L.wh_unscale[1] / g->opt_ascale; a.ascale = OUTF32 ? 1.f : g->opt_ascale;
-    a.range = g->range_dev; a.range_bit = 1u << layer;
-    a.N = NN; a.R = R; a.npix_total = npix;
+    if (const int rc = generator_reserve_part(g, npix * COUT * nsplit)) return rc;
+    float *const part = g->work().part;
+    ConvHArgs a = convh_args(g, layer, L, in, part, OUTF32, NN, R);
+    a.npix_total = npix; a.stamps = nullptr;
     const int total_tiles = B * (NN / R);
     constexpr bool TWO = lds * 2 <= 160 * 1024 && MT == 2;
     auto kern = k_convh2<CIN, COUT, KS, NN, MT, TPS, OUTF32, WDB, TWO, false, true>;
@@ -1555,10 +1292,9 @@ static int launch_convh2_part_n(qgx_generator *g, int layer, const LayerHost &L,
     hipLaunchKernelGGL(kern, dim3(total_tiles, nsplit), dim3(256), lds, st, a, total_tiles);
     const size_t n = npix * (COUT / 8);
     hipLaunchKernelGGL((k_convh_reduce<COUT, OUTF32>), dim3((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), dim3(256), 0, st,
-                       (const float *)g->part, nsplit, npix, (const float *)L.bias, (const float *)L.scale, (const float *)L.shift,
+                       (const float *)part, nsplit, npix, (const float *)L.bias, (const float *)L.scale, (const float *)L.shift,
                        a.unscale, a.ascale, out, a.range, a.range_bit);
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 
@@ -1587,14 +1323,9 @@ static int launch_convh2_w8(qgx_generator *g, int layer, const LayerHost &L, con
     constexpr int R = NW * MT * 32 / TW, PR = R + KS - 1, PW = TW + 4;
     constexpr size_t lds = (size_t)PR * PW * 80 + (size_t)2 * TPS * 4 * COUT * 16 + 3 * COUT * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS");
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
-    ConvHArgs a = {};
-    a.in = in; a.out = out; a.w = L.wh[1]; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
-    a.unscale = L.wh_unscale[1] / g->opt_ascale; a.ascale = g->opt_ascale;
-    a.range = g->range_dev; a.range_bit = 1u << layer;
-    a.N = NN; a.R = R;
-    a.stamps = layer == g->stamp_layer ? g->stamps : nullptr;
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
+    ConvHArgs a = convh_args(g, layer, L, in, out, false, NN, R);
     const int total_tiles = B * (NN / R) * (NN / TW);
     int grid = 256;
     if (grid > total_tiles) grid = total_tiles;
@@ -1602,7 +1333,6 @@ static int launch_convh2_w8(qgx_generator *g, int layer, const LayerHost &L, con
     { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a, total_tiles);
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 
@@ -1612,14 +1342,9 @@ static int launch_convh2_w8_3x3(qgx_generator *g, int layer, const LayerHost &L,
     constexpr int COUT = 32, KS = 3, MT = 2, TPS = 9;
     constexpr int R = NW * MT * 32 / TW, PR = R + KS - 1, PW = TW + 2;
     constexpr size_t lds = (size_t)PR * PW * 80 + (size_t)2 * TPS * 4 * COUT * 16 + 3 * COUT * sizeof(float);
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
-    ConvHArgs a = {};
-    a.in = in; a.out = out; a.w = L.wh[1]; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
-    a.unscale = L.wh_unscale[1] / g->opt_ascale; a.ascale = OUTF32 ? 1.f : g->opt_ascale;
-    a.range = g->range_dev; a.range_bit = 1u << layer;
-    a.N = NN; a.R = R;
-    a.stamps = layer == g->stamp_layer ? g->stamps : nullptr;
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
+    ConvHArgs a = convh_args(g, layer, L, in, out, OUTF32, NN, R);
     const int total_tiles = B * (NN / R) * (NN / TW);
     int grid = 256;
     if (grid > total_tiles) grid = total_tiles;
@@ -1627,7 +1352,6 @@ static int launch_convh2_w8_3x3(qgx_generator *g, int layer, const LayerHost &L,
     { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a, total_tiles);
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 
@@ -1682,14 +1406,9 @@ static int launch_convh_res(qgx_generator *g, int layer, const LayerHost &L, con
     const size_t lds = (size_t)(CIN / 16) * 9 * 4 * COUT * 16 + (size_t)PR * N * 128 + 3 * COUT * sizeof(float);
     const int ppt = (PR * N * 8 + 511) / 512;
     if (lds > 160 * 1024 || ntiles % 8 || (mtv != 2 && mtv != 3) || ppt > 14) return QGX_OK;
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
-    ConvHArgs a = {};
-    a.in = in; a.out = out; a.w = L.wh[1]; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
-    a.unscale = L.wh_unscale[1] / g->opt_ascale; a.ascale = OUTF32 ? 1.f : g->opt_ascale;
-    a.range = g->range_dev; a.range_bit = 1u << layer;
-    a.N = N; a.R = R;
-    a.stamps = layer == g->stamp_layer ? g->stamps : nullptr;
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
+    ConvHArgs a = convh_args(g, layer, L, in, out, OUTF32, N, R);
     const int total_tiles = B * (N / R);
     int grid = 256;
     if (grid > total_tiles) grid = total_tiles;
@@ -1703,7 +1422,6 @@ static int launch_convh_res(qgx_generator *g, int layer, const LayerHost &L, con
     else { if (ppt <= 10) QGX_LR(3, 10) else QGX_LR(3, 14) }
 #undef QGX_LR
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     done = true;
     return QGX_OK;
 }
@@ -1739,13 +1457,10 @@ static int launch_convh3(qgx_generator *g, int layer, const LayerHost &L, const 
     constexpr int NN = 64, R = 256 / NN, PR = R + 4, PW = NN + 4;
     constexpr size_t lds = (size_t)4 * PR * PW * 48 + (size_t)5 * 2 * 4 * 64 * 16 + 3 * 64 * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS");
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
-    ConvHArgs a = {};
-    a.in = in; a.out = out; a.w = L.wh16; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
-    a.unscale = L.wh_unscale[1] / g->opt_ascale; a.ascale = g->opt_ascale;
-    a.range = g->range_dev; a.range_bit = 1u << layer;
-    a.N = N; a.R = R;
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
+    ConvHArgs a = convh_args(g, layer, L, in, out, false, N, R);
+    a.w = L.wh16; a.stamps = nullptr;
     const int total_tiles = B * (N / R);
     int grid = 256;
     if (grid > total_tiles) grid = total_tiles;
@@ -1753,7 +1468,6 @@ static int launch_convh3(qgx_generator *g, int layer, const LayerHost &L, const 
     { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, total_tiles);
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     done = true;
     return QGX_OK;
 }
@@ -1764,13 +1478,10 @@ static int launch_convh4_n(qgx_generator *g, int layer, const LayerHost &L, cons
     constexpr int R = NW * MT * 32 / NN, PR = R + 4, PW = NN + 4;
     constexpr size_t lds = (size_t)PR * PW * 144 + (size_t)2 * 5 * 4 * 64 * 16 + 3 * 64 * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS");
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
-    ConvHArgs a = {};
-    a.in = in; a.out = out; a.w = L.wh[1]; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
-    a.unscale = L.wh_unscale[1] / g->opt_ascale; a.ascale = g->opt_ascale;
-    a.range = g->range_dev; a.range_bit = 1u << layer;
-    a.N = NN; a.R = R;
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
+    ConvHArgs a = convh_args(g, layer, L, in, out, false, NN, R);
+    a.stamps = nullptr;
     const int total_tiles = B * (NN / R);
     int grid = 256;
     if (grid > total_tiles) grid = total_tiles;
@@ -1778,7 +1489,6 @@ static int launch_convh4_n(qgx_generator *g, int layer, const LayerHost &L, cons
     { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a, total_tiles);
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 static int launch_convh4(qgx_generator *g, int layer, const LayerHost &L, const void *in, void *out, int B, int N,
@@ -1801,8 +1511,8 @@ static int launch_convh_pair(qgx_generator *g, int layerA, const LayerHost &LA, 
     constexpr size_t reg0 = (size_t)(R + 2) * PW * 144 > (size_t)(R + 4) * PW * 80 ? (size_t)(R + 2) * PW * 144 : (size_t)(R + 4) * PW * 80;
     constexpr size_t lds = reg0 + 3 * (9 * 4 * 32 * 16) + 2 * 96 * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS");
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layerA, st, prof_stop); if (prc) return prc; }
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layerA, st)) return prc;
     ConvPairArgs a = {};
     a.in = in; a.out = out; a.wA = LA.wh[1]; a.wB = LB.wh[1];
     a.biasA = LA.bias; a.scaleA = LA.scale; a.shiftA = LA.shift;
@@ -1821,7 +1531,6 @@ static int launch_convh_pair(qgx_generator *g, int layerA, const LayerHost &LA, 
     { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a, total_tiles);
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 
@@ -1844,8 +1553,8 @@ static int launch_convh_first(qgx_generator *g, const LayerHost &L, const float 
     const int ppt = (PR * NIN * (N / 4) + nw * 64 - 1) / (nw * 64);
     QGX_REQUIRE(lds <= 160 * 1024 - 256 && ppt <= 3 && (ntiles == 2 * nw || ntiles == 3 * nw || (half_rows && ntiles == nw)),
                 "generator: 16-bit first layer unsupported for N=%d", N);
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, 0, st, prof_stop); if (prc) return prc; }
+    ProfScope prof;
+    if (const int prc = prof.begin(g, 0, st)) return prc;
     ConvHFirstArgs a = {};
     a.stamps = g->stamp_layer == 0 ? g->stamps : nullptr;
     a.in = in; a.out = out; a.w = L.whf; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
@@ -1874,16 +1583,15 @@ static int launch_convh_first(qgx_generator *g, const LayerHost &L, const float 
 #undef QGX_LF
 #undef QGX_LF_KERN
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 
-// layer 2 as a 1-D Winograd convolution (conv_wino.hpp); done = false: no specialisation for this grid / ensemble size
+// layer 2 as a 1-D Winograd convolution (conv_wino.hpp); use2: as k_convw2 where that kernel is built for the tile shape
 template <int NN, int TW, int R, bool PL = false>
-static int launch_convw_n(qgx_generator *g, int layer, const LayerHost &L, int which, const void *in, void *out, int B,
+static int launch_convw_n(qgx_generator *g, int layer, const LayerHost &L, int which, bool use2, const void *in, void *out, int B,
                           hipStream_t st) {
-    hipEvent_t prof_stop;
-    { int prc = prof_begin(g, layer, st, prof_stop); if (prc) return prc; }
+    ProfScope prof;
+    if (const int prc = prof.begin(g, layer, st)) return prc;
     ConvWArgs a = {};
     a.in = in; a.out = out; a.w = L.ww[which]; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
     for (int p = 0; p < 8; ++p) a.pscale[p] = L.ww_unscale[which][p] / g->opt_ascale;
@@ -1892,14 +1600,10 @@ static int launch_convw_n(qgx_generator *g, int layer, const LayerHost &L, int w
     const int total_tiles = B * (NN / R) * (NN / TW);
     constexpr size_t lds = convw_lds_bytes(NN, TW, R, PL);
     static_assert(lds <= 160 * 1024 - 256, "k_convw: LDS");
-    if (!PL && g->opt_wino2 && g->opt_wino_exp == 0) {
+    if (!PL && use2) {
         bool done2 = false;
         const int rc2 = launch_convw2(NN, TW, R, a, total_tiles, st, &done2);
-        if (rc2) return rc2;
-        if (done2) {
-            if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
-            return QGX_OK;
-        }
+        if (rc2 || done2) return rc2;
     }
     const int grid = total_tiles < 256 ? total_tiles : 256;
     void (*kern)(ConvWArgs, int) = k_convw<NN, TW, R, 0, PL>;
@@ -1915,7 +1619,6 @@ static int launch_convw_n(qgx_generator *g, int layer, const LayerHost &L, int w
     { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a, total_tiles);
     QGX_HIP(hipGetLastError());
-    if (prof_stop) QGX_HIP(hipEventRecord(prof_stop, st));
     return QGX_OK;
 }
 // tiles of 512 pixels: 8 x 64 (64 x 64, 128 x 128), 16 x 32 (96 x 96, 32 x 32); 16 x 16 at 48 x 48
@@ -1929,8 +1632,6 @@ static int wino_tiles(int B, int N) {
         default: return 0;
     }
 }
-// does the 5x5 layer run as the Winograd form for this ensemble?  (decided BEFORE layer 1: its output layout — channel-planar
-// for the MFMA input transform — and its range guard depend on it)
 static int wino_size_index(int N) {
     switch (N) { case 32: return 0; case 48: return 1; case 64: return 2; case 96: return 3; case 128: return 4; default: return -1; }
 }
@@ -1951,72 +1652,101 @@ static bool wino_planar(const qgx_generator *g) {
     return false;
 #endif
 }
-static int launch_convw(qgx_generator *g, int layer, const LayerHost &L, int which, const void *in, void *out, int B, int N,
-                        hipStream_t st, bool &done) {
-    done = false;
-    if (!wino_applies(g, L, which, B, N)) return QGX_OK;
-    int rc;
+// The Winograd layer's tile rows for B members at N x N: the full shape of wino_tiles() or, at every size but 48 x 48, a
+// smaller one.  256 persistent workgroups take ceil(tiles / 256) rounds, so the shape is chosen by rounds x cost per tile:
+// the small shape pays while the large one leaves CUs idle.  Measured (layer time in us):
+//   64 x 64, 8-row tiles (8 per member) or 4-row tiles (16 per member, half the work each at a 2 x instead of 1.5 x row
+//     halo), 8 / 4 rows: 8 members 65 / 44, 16: 69 / 50, 24: 74 / 87, 31: 80 / 92, 48: 139 / 134 -> 0.66 per tile
+//   32 x 32, 16 x 32 tiles (2 per member) or 8 x 32 (4 per member): 32 / 64 members 63 -> 42 / 68 -> 49 us, 96 / 128 members
+//     stay (73 / 85, 83 / 95)
+//   128 x 128, 8 x 64 tiles (32 per member) or 4 x 64 (64 per member), as at 64 x 64: 2 / 4 members 67 -> 45 / 72 -> 53 us,
+//     6 / 8 members stay (78 / 89, 86 / 97), 12 members 155 -> 143
+//   96 x 96, 16 x 32 tiles (18 per member) or 12 x 32 (24 per member, 0.75 x the work each at a 1.33 x instead of 1.25 x row
+//     halo): at 32 members 3 x 1.0 against 3 x 0.79 (measured 215 -> 171 us), at 24 members 2 x 1.0 against 3 x 0.79
+//     (149 / 160 us), at 128 9 x 1.0 against 12 x 0.79 (690 / 749 us)
+static int wino_rows(const qgx_generator *g, int B, int N) {
+    if (N == 48) return 16;
+    if (N == 96) {
+        const int r16 = (B * 18 + 255) / 256, r12 = (B * 24 + 255) / 256;
+        return g->opt_wino_rows96 == 12 || (g->opt_wino_rows96 == 0 && 0.79 * r12 < 1.0 * r16) ? 12 : 16;
+    }
+    const int full = N == 32 ? 16 : 8, tiles = wino_tiles(B, N);      // the half-height shape has twice the tiles
+    const int rf = (tiles + 255) / 256, rh = (2 * tiles + 255) / 256;
+    return g->opt_wino_rows64 == 4 || (g->opt_wino_rows64 == 0 && 0.66 * rh < 1.0 * rf) ? full / 2 : full;
+}
+
+// ---- the plan for layer 2 (the 128 -> 64, 5x5 layer) -----------------------------------------------------------------
+// Everything about it that is decided BEFORE layer 1 is launched — layer 1's BatchNorm, its output layout and its range
+// guard depend on it — and decided here only: cnn_forward_half and launch_convw carry the plan out,
+// qgx_generator_layer2_kernel reports it.
+struct Layer2Plan {
+    bool fold = false;      // layer 1 stores its ReLU output (identity BatchNorm in the epilogue; 50 % exact zeros with the
+                            //   shipped weights) and layer 2 uses the weights / bias with that BatchNorm folded in
+    bool tiny = false;      // single members / tiny ensembles (fewer than "part_max_tiles" tiles): split K on the two wide layers,
+                            //   and no 8-row pair kernel for (7, 8) (8 tiles of 512 pixels would leave 248 CUs idle)
+    bool wino = false;      // the Winograd form runs (then layer 1's range guard covers its input transform too) ...
+    int which = 0;          //   ... with these weights of LayerHost::ww: 0 plain, 1 folded
+    bool planar = false;    //   ... on channel-planar rows (wino_planar)
+    int tw = 0, rows = 0;   //   ... on tiles of rows x tw pixels
+    bool wino2 = false;     //   ... as k_convw2
+    int kernel = 0;         // 0 exact-f32 MFMA, 1 the 25-tap f16x3 kernel, 2 its split-K form, 3 k_convw, 4 k_convw2
+};
+static Layer2Plan plan_layer2(const qgx_generator *g, const NetHost &net, int B, int N) {
+    Layer2Plan p;
+    const bool x3 = g->opt_precision == 3;
+    p.fold = x3 && g->opt_first_h && g->opt_fold && net.L[1].whF;
+    p.which = p.fold ? 1 : 0;
+    const int r2 = rows_h2(N);
+    if (!x3 || r2 <= 0) return p;
+    p.tiny = g->opt_h2 == 3 && B * (N / r2) < g->opt_part_max_tiles;
+    p.wino = !p.tiny && g->opt_first_h && wino_applies(g, net.L[1], p.which, B, N);
+    p.kernel = p.tiny ? 2 : 1;
+    if (!p.wino) return p;
+    p.planar = wino_planar(g);
+    p.rows = p.planar ? (N == 64 ? 8 : 16) : wino_rows(g, B, N);
+    p.tw = N == 48 ? 16 : (N == 64 || (N == 128 && !p.planar) ? 64 : 32);   // (planar 64-column tiles at 128 x 128: raw + transformed patch > 160 KB)
+    p.wino2 = !p.planar && g->opt_wino2 && g->opt_wino_exp == 0 && convw2_takes(N, p.tw, p.rows);
+    p.kernel = p.wino2 ? 4 : 3;
+    return p;
+}
+
+static int launch_convw(qgx_generator *g, int layer, const LayerHost &L, const Layer2Plan &p, const void *in, void *out, int B,
+                        int N, hipStream_t st) {
+#define QGX_LW(NN, TW, R, PL) \
+    if (N == NN && p.tw == TW && p.rows == R && p.planar == PL) return launch_convw_n<NN, TW, R, PL>(g, layer, L, p.which, p.wino2, in, out, B, st);
 #ifdef QGX_AB
-    if (wino_planar(g)) {
-        switch (N) {
-            case 32: rc = launch_convw_n<32, 32, 16, true>(g, layer, L, which, in, out, B, st); break;
-            case 48: rc = launch_convw_n<48, 16, 16, true>(g, layer, L, which, in, out, B, st); break;
-            case 64: rc = launch_convw_n<64, 64, 8, true>(g, layer, L, which, in, out, B, st); break;
-            case 96: rc = launch_convw_n<96, 32, 16, true>(g, layer, L, which, in, out, B, st); break;
-            default: rc = launch_convw_n<128, 32, 16, true>(g, layer, L, which, in, out, B, st); break;   // (64-column tiles: raw + transformed patch > 160 KB)
-        }
-        if (!rc) done = true;
-        return rc;
-    }
+    QGX_LW(32, 32, 16, true) QGX_LW(48, 16, 16, true) QGX_LW(64, 64, 8, true) QGX_LW(96, 32, 16, true) QGX_LW(128, 32, 16, true)
 #endif
-    switch (N) {
-        case 32: {       // 16 x 32 tiles (2 per member) or 8 x 32 (4 per member): 32 / 64 members 63 -> 42 / 68 -> 49 us, 96 / 128 members stay (73 / 85, 83 / 95)
-            const int r16 = (B * 2 + 255) / 256, r8 = (B * 4 + 255) / 256;
-            const bool rows8 = g->opt_wino_rows64 == 4 || (g->opt_wino_rows64 == 0 && 0.66 * r8 < 1.0 * r16);
-            rc = rows8 ? launch_convw_n<32, 32, 8>(g, layer, L, which, in, out, B, st)
-                       : launch_convw_n<32, 32, 16>(g, layer, L, which, in, out, B, st);
-            break;
-        }
-        case 48: rc = launch_convw_n<48, 16, 16>(g, layer, L, which, in, out, B, st); break;
-        case 64: {
-            // 8-row tiles (8 per member) or 4-row tiles (16 per member, half the work each at a 2 x instead of 1.5 x row halo): by
-            // rounds x cost per tile as at 96 x 96 — the small shape pays while the large one leaves CUs idle (measured, layer time in
-            // us, 8 / 4 rows: 8 members 65 / 44, 16: 69 / 50, 24: 74 / 87, 31: 80 / 92, 48: 139 / 134 -> 0.66 per tile)
-            const int r8 = (B * 8 + 255) / 256, r4 = (B * 16 + 255) / 256;
-            const bool rows4 = g->opt_wino_rows64 == 4 || (g->opt_wino_rows64 == 0 && 0.66 * r4 < 1.0 * r8);
-            rc = rows4 ? launch_convw_n<64, 64, 4>(g, layer, L, which, in, out, B, st)
-                       : launch_convw_n<64, 64, 8>(g, layer, L, which, in, out, B, st);
-            break;
-        }
-        case 96: {
-            // 16 x 32 tiles (18 per member) or 12 x 32 (24 per member, 0.75 x the work each at a 1.33 x instead of 1.25 x row halo):
-            // 256 persistent workgroups take ceil(tiles / 256) rounds, so the shape is chosen by rounds x cost per tile — at 32 members
-            // 3 x 1.0 against 3 x 0.79 (measured 215 -> 171 us), at 24 members 2 x 1.0 against 3 x 0.79 (149 / 160 us), at 128 9 x 1.0
-            // against 12 x 0.79 (690 / 749 us)
-            const int r16 = (B * 18 + 255) / 256, r12 = (B * 24 + 255) / 256;
-            const bool rows12 = g->opt_wino_rows96 == 12 || (g->opt_wino_rows96 == 0 && 0.79 * r12 < 1.0 * r16);
-            rc = rows12 ? launch_convw_n<96, 32, 12>(g, layer, L, which, in, out, B, st)
-                        : launch_convw_n<96, 32, 16>(g, layer, L, which, in, out, B, st);
-            break;
-        }
-        default: {       // 128 x 128: 8 x 64 tiles (32 per member) or 4 x 64 (64 per member), as at 64 x 64: 2 / 4 members 67 -> 45 / 72 -> 53 us,
-                         // 6 / 8 members stay (78 / 89, 86 / 97), 12 members 155 -> 143
-            const int r8 = (B * 32 + 255) / 256, r4 = (B * 64 + 255) / 256;
-            const bool rows4 = g->opt_wino_rows64 == 4 || (g->opt_wino_rows64 == 0 && 0.66 * r4 < 1.0 * r8);
-            rc = rows4 ? launch_convw_n<128, 64, 4>(g, layer, L, which, in, out, B, st)
-                       : launch_convw_n<128, 64, 8>(g, layer, L, which, in, out, B, st);
-            break;
-        }
+    QGX_LW(32, 32, 8, false) QGX_LW(32, 32, 16, false) QGX_LW(48, 16, 16, false) QGX_LW(64, 64, 4, false) QGX_LW(64, 64, 8, false)
+    QGX_LW(96, 32, 12, false) QGX_LW(96, 32, 16, false) QGX_LW(128, 64, 4, false) QGX_LW(128, 64, 8, false)
+#undef QGX_LW
+    QGX_REQUIRE(false, "generator: layer 1 was stored for the Winograd layer, which did not run (N=%d)", N);
+}
+
+// Layers 5-8 of the 16-bit path.  `pairs` bit 0: layers (5, 6), bit 1: layers (7, 8) as ONE launch of the pair kernel on R-row
+// strips of an NN x NN grid (the intermediate activation stays in LDS), else as two kernels.  `cur` holds layer 4's output,
+// `oth` takes a layer's output; which buffer ends up with which layer is what qgx_debug_read_act and "stop_layer" rely on.
+template <int NS, int NN, int R>
+static int layers_5_to_8(qgx_generator *g, const NetHost &net, int pairs, float *cur, float *oth, float *yc, int Bc, int N,
+                         hipStream_t st) {
+    int rc;
+    if (pairs & 1) {
+        if ((rc = launch_convh_pair<32, false, false, NN, R>(g, 4, net.L[4], net.L[5], cur, oth, Bc, N, 0, st))) return rc;
+        std::swap(cur, oth);
+    } else {
+        if ((rc = conv3x3_half<32, 32, NS, false>(g, 4, net.L[4], cur, oth, Bc, N, st))) return rc;
+        if ((rc = conv3x3_half<32, 32, NS, false>(g, 5, net.L[5], oth, cur, Bc, N, st))) return rc;
     }
-    if (!rc) done = true;
-    return rc;
+    if (pairs & 2) return launch_convh_pair<32, true, false, NN, R>(g, 6, net.L[6], net.L[7], cur, yc, Bc, N, net.n_out, st);
+    if ((rc = conv3x3_half<32, 32, NS, true>(g, 6, net.L[6], cur, oth, Bc, N, st))) return rc;
+    return launch_conv_last(g, net.L[7], oth, yc, Bc, N, net.n_out, st);
 }
 
 template <int NS>
 static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N,
                             hipStream_t st) {
     int rc;
-    float *A = g->actA, *Bb = g->actB;
+    float *A = g->work().actA, *Bb = g->work().actB;
     // optional member sub-batches ("member_chunk"): all layers of one sub-batch before the next, so that the
     // inter-layer activations of a sub-batch can stay in the 256 MB Infinity Cache
     const int mc = g->opt_member_chunk > 0 && g->opt_member_chunk < B ? g->opt_member_chunk : B;
@@ -2024,37 +1754,26 @@ static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x
         const int Bc = B - b0 < mc ? B - b0 : mc;
         const float *xc = x + (size_t)b0 * net.n_in * N * N;
         float *yc = y + (size_t)b0 * net.n_out * N * N;
-        // "fold": layer 1 stores its ReLU output (identity BatchNorm in the epilogue; 50 % exact zeros with the
-        // shipped weights) and layer 2 uses the weights / bias with that BatchNorm folded in
-        const bool fold = NS == 2 && g->opt_first_h && g->opt_fold && net.L[1].whF;
+        const Layer2Plan p = plan_layer2(g, net, Bc, N);
         LayerHost L0 = net.L[0], L1 = net.L[1];
-        if (fold) {
+        if (p.fold) {
             L0.scale = L0.ones; L0.shift = L0.zeros;
             L1.wh[1] = L1.whF; L1.wh_unscale[1] = L1.whF_unscale; L1.bias = L1.biasF; L1.wh16 = L1.wh16F;
         }
-        bool wino2 = false;
         if (NS == 2 && g->opt_first_h) {
-            // (will the 5x5 layer run as the Winograd form?  then layer 1's range guard covers its input transform too)
-            const int r2w = rows_h2(N);
-            wino2 = NS == 2 && wino_applies(g, L1, fold ? 1 : 0, Bc, N) &&
-                    !(g->opt_h2 == 3 && r2w > 0 && Bc * (N / r2w) < g->opt_part_max_tiles);
-            rc = net.n_in == 4 ? launch_convh_first<4>(g, L0, xc, A, Bc, N, st, wino2, wino2 && wino_planar(g))
-                               : launch_convh_first<2>(g, L0, xc, A, Bc, N, st, wino2, wino2 && wino_planar(g));
+            rc = net.n_in == 4 ? launch_convh_first<4>(g, L0, xc, A, Bc, N, st, p.wino, p.wino && p.planar)
+                               : launch_convh_first<2>(g, L0, xc, A, Bc, N, st, p.wino, p.wino && p.planar);
         } else if (net.n_in == 4) rc = launch_conv<4, 128, 5, 4, true, false, 2, NS>(g, 0, net.L[0], xc, A, Bc, N, 128, st);
         else rc = launch_conv<2, 128, 5, 2, true, false, 2, NS>(g, 0, net.L[0], xc, A, Bc, N, 128, st);
         if (rc) return rc;
 #ifdef QGX_AB
         if (g->opt_stop_layer == 1) return QGX_OK;
 #endif
-        // single members / tiny ensembles (fewer than "part_max_tiles" tiles): split K on the two wide layers and
-        // do not fuse (7, 8) (8 tiles of 512 pixels would leave 248 CUs idle)
-        const int r2 = rows_h2(N);
-        const bool tiny = NS == 2 && g->opt_h2 == 3 && r2 > 0 && Bc * (N / r2) < g->opt_part_max_tiles;
         bool done1 = false;
-        if (tiny && (rc = launch_convh2_part<128, 64, 5, false>(g, 1, L1, A, Bb, Bc, N, st, done1))) return rc;
-        if (!done1 && wino2) {
-            if ((rc = launch_convw(g, 1, L1, fold ? 1 : 0, A, Bb, Bc, N, st, done1))) return rc;
-            QGX_REQUIRE(done1, "generator: layer 1 was stored for the Winograd layer, which did not run (N=%d)", N);
+        if (p.tiny && (rc = launch_convh2_part<128, 64, 5, false>(g, 1, L1, A, Bb, Bc, N, st, done1))) return rc;
+        if (!done1 && p.wino) {
+            if ((rc = launch_convw(g, 1, L1, p, A, Bb, Bc, N, st))) return rc;
+            done1 = true;
         }
 #ifdef QGX_AB
         if (!done1 && NS == 2 && g->opt_h4 && (rc = launch_convh4(g, 1, L1, A, Bb, Bc, N, st, done1))) return rc;
@@ -2063,20 +1782,19 @@ static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x
         if (!done1 && NS == 2 && (g->opt_h2 & 2) && (rc = launch_convh2<128, 64, 5, false>(g, 1, L1, A, Bb, Bc, N, st, done1))) return rc;
 #ifdef QGX_AB
         if (!done1 && (rc = launch_convh<128, 64, 5, NS, false>(g, 1, L1, A, Bb, Bc, N, st))) return rc;
+        if (g->opt_stop_layer == 2) return QGX_OK;
 #else
         QGX_REQUIRE(done1, "generator: no f16x3 kernel for N=%d", N);
 #endif
-#ifdef QGX_AB
-        if (g->opt_stop_layer == 2) return QGX_OK;
-#endif
-        if (tiny) {
+        const bool pairs_ok = NS == 2 && net.n_out <= 2;      // the pair kernels: f16x3, and (7, 8) writes at most two channels
+        if (p.tiny) {
             // (local names: the 64-channel activation of layer 2 is in Bb; `cur` holds a layer's input, `oth` takes its output)
             float *cur = Bb, *oth = A;
             // Layers (3, 4), (5, 6) and (7, 8) each as ONE launch on 2-row strips ("tiny_pairs" bits 2, 1, 0): a single member is
             // a chain of launch latencies, and a strip's fixed costs — layer B's 36 KB of MFMA weights above all — are cheaper
             // than a kernel boundary there; for (3, 4) the one launch also replaces split-K and its combine kernel
-            const bool strips = NS == 2 && N == 64 && net.n_out <= 2;
-            if (strips && (g->opt_tiny_pairs & 4)) {
+            const int tp = pairs_ok && N == 64 ? g->opt_tiny_pairs : 0;
+            if (tp & 4) {
                 if ((rc = launch_convh_pair<64, false, false, 64, 2>(g, 2, net.L[2], net.L[3], cur, oth, Bc, N, 0, st))) return rc;
                 std::swap(cur, oth);
             } else {
@@ -2085,112 +1803,37 @@ static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x
                 if (!done2 && (rc = conv3x3_half<64, 32, NS, false>(g, 2, net.L[2], cur, oth, Bc, N, st))) return rc;
                 if ((rc = conv3x3_half<32, 32, NS, false>(g, 3, net.L[3], oth, cur, Bc, N, st))) return rc;
             }
-            if (strips && (g->opt_tiny_pairs & 2)) {
-                if ((rc = launch_convh_pair<32, false, false, 64, 2>(g, 4, net.L[4], net.L[5], cur, oth, Bc, N, 0, st))) return rc;
-                std::swap(cur, oth);
-            } else {
-                if ((rc = conv3x3_half<32, 32, NS, false>(g, 4, net.L[4], cur, oth, Bc, N, st))) return rc;
-                if ((rc = conv3x3_half<32, 32, NS, false>(g, 5, net.L[5], oth, cur, Bc, N, st))) return rc;
-            }
-            if (strips && (g->opt_tiny_pairs & 1)) {
-                if ((rc = launch_convh_pair<32, true, false, 64, 2>(g, 6, net.L[6], net.L[7], cur, yc, Bc, N, net.n_out, st))) return rc;
-                continue;
-            }
-            if ((rc = conv3x3_half<32, 32, NS, true>(g, 6, net.L[6], cur, oth, Bc, N, st))) return rc;
-            if ((rc = launch_conv_last(g, net.L[7], oth, yc, Bc, N, net.n_out, st))) return rc;
+            if ((rc = layers_5_to_8<NS, 64, 2>(g, net, ((tp >> 1) & 1) | ((tp & 1) << 1), cur, oth, yc, Bc, N, st))) return rc;
             continue;
         }
-        if (NS == 2 && g->opt_fuse && N == 64 && net.n_out <= 2) {
-            // 3x3 layers fused pairwise (the intermediate activation stays in LDS); "fuse" bits: 1 = layers
-            // (5, 6), 2 = layers (7, 8), 4 = layers (3, 4) — the 64-channel pair measured slower fused
-            if (g->opt_fuse & 4) {
-                if ((rc = launch_convh_pair<64, false, false>(g, 2, net.L[2], net.L[3], Bb, A, Bc, N, 0, st))) return rc;
-            } else {
-                if ((rc = conv3x3_half<64, 32, NS, false>(g, 2, net.L[2], Bb, A, Bc, N, st))) return rc;
-                if ((rc = conv3x3_half<32, 32, NS, false>(g, 3, net.L[3], A, Bb, Bc, N, st))) return rc;
-            }
-            // here the activation is in A (fused pair) or Bb (two kernels)
-            float *cur = (g->opt_fuse & 4) ? A : Bb, *oth = (g->opt_fuse & 4) ? Bb : A;
+        // 3x3 layers fused pairwise at 64 x 64; "fuse" bits: 1 = layers (5, 6), 2 = layers (7, 8), 4 = layers (3, 4) — the
+        // 64-channel pair measured slower fused
+        const int fuse = pairs_ok && N == 64 ? g->opt_fuse : 0;
+        if (fuse & 4) {
+            if ((rc = launch_convh_pair<64, false, false>(g, 2, net.L[2], net.L[3], Bb, A, Bc, N, 0, st))) return rc;
+        } else {
+            if ((rc = conv3x3_half<64, 32, NS, false>(g, 2, net.L[2], Bb, A, Bc, N, st))) return rc;
+            if ((rc = conv3x3_half<32, 32, NS, false>(g, 3, net.L[3], A, Bb, Bc, N, st))) return rc;
+        }
+        // here the activation is in A (fused pair) or Bb (two kernels)
+        float *cur = (fuse & 4) ? A : Bb, *oth = (fuse & 4) ? Bb : A;
+        if (fuse) {
             // (4-row strips for the pairs, as the Winograd layer's small shape, measured slower at 8 ... 48 members: 25.4 -> 30.8 us at
             // 16, 26.3 -> 47.4 at 24 — a strip's fixed costs, layer B's 36 KB of weights above all, do not halve with its rows)
-            if (g->opt_fuse & 1) {
-                if ((rc = launch_convh_pair<32, false, false>(g, 4, net.L[4], net.L[5], cur, oth, Bc, N, 0, st))) return rc;
-                std::swap(cur, oth);
-            } else {
-                if ((rc = conv3x3_half<32, 32, NS, false>(g, 4, net.L[4], cur, oth, Bc, N, st))) return rc;
-                if ((rc = conv3x3_half<32, 32, NS, false>(g, 5, net.L[5], oth, cur, Bc, N, st))) return rc;
-            }
-            if (g->opt_fuse & 2) {
-                if ((rc = launch_convh_pair<32, true, false>(g, 6, net.L[6], net.L[7], cur, yc, Bc, N, net.n_out, st))) return rc;
-            } else {
-                if ((rc = conv3x3_half<32, 32, NS, true>(g, 6, net.L[6], cur, oth, Bc, N, st))) return rc;
-                if ((rc = launch_conv_last(g, net.L[7], oth, yc, Bc, N, net.n_out, st))) return rc;
-            }
-            continue;
+            rc = layers_5_to_8<NS, 64, 8>(g, net, fuse & 3, cur, oth, yc, Bc, N, st);
+        } else {
+            // 96 x 96: the pair kernel on 4-row strips (a 6-row intermediate patch of 98 columns is 85 KB); "fuse96" bits as "fuse".
+            // Every other grid: two kernels per pair
+            const int fuse96 = pairs_ok && N == 96 && Bc * 24 >= 256 ? g->opt_fuse96 : 0;
+            rc = layers_5_to_8<NS, 96, 4>(g, net, fuse96 & 3, cur, oth, yc, Bc, N, st);
         }
-        if ((rc = conv3x3_half<64, 32, NS, false>(g, 2, net.L[2], Bb, A, Bc, N, st))) return rc;
-        if ((rc = conv3x3_half<32, 32, NS, false>(g, 3, net.L[3], A, Bb, Bc, N, st))) return rc;
-        if (NS == 2 && g->opt_fuse96 && N == 96 && net.n_out <= 2 && Bc * 24 >= 256) {
-            // 96 x 96: the pair kernel on 4-row strips (a 6-row intermediate patch of 98 columns is 85 KB); "fuse96" bits as "fuse"
-            float *cur = Bb, *oth = A;
-            if (g->opt_fuse96 & 1) {
-                if ((rc = launch_convh_pair<32, false, false, 96, 4>(g, 4, net.L[4], net.L[5], cur, oth, Bc, N, 0, st))) return rc;
-                std::swap(cur, oth);
-            } else {
-                if ((rc = conv3x3_half<32, 32, NS, false>(g, 4, net.L[4], cur, oth, Bc, N, st))) return rc;
-                if ((rc = conv3x3_half<32, 32, NS, false>(g, 5, net.L[5], oth, cur, Bc, N, st))) return rc;
-            }
-            if (g->opt_fuse96 & 2) {
-                if ((rc = launch_convh_pair<32, true, false, 96, 4>(g, 6, net.L[6], net.L[7], cur, yc, Bc, N, net.n_out, st))) return rc;
-            } else {
-                if ((rc = conv3x3_half<32, 32, NS, true>(g, 6, net.L[6], cur, oth, Bc, N, st))) return rc;
-                if ((rc = launch_conv_last(g, net.L[7], oth, yc, Bc, N, net.n_out, st))) return rc;
-            }
-            continue;
-        }
-        if ((rc = conv3x3_half<32, 32, NS, false>(g, 4, net.L[4], Bb, A, Bc, N, st))) return rc;
-        if ((rc = conv3x3_half<32, 32, NS, false>(g, 5, net.L[5], A, Bb, Bc, N, st))) return rc;
-        if ((rc = conv3x3_half<32, 32, NS, true>(g, 6, net.L[6], Bb, A, Bc, N, st))) return rc;
-        if ((rc = launch_conv_last(g, net.L[7], A, yc, Bc, N, net.n_out, st))) return rc;
+        if (rc) return rc;
     }
-    return QGX_OK;
-}
-
-int generator_select_workspace(qgx_generator *g, int idx) {
-    QGX_REQUIRE(g && (idx == 0 || idx == 1), "generator_select_workspace: bad argument");
-    if (idx == g->ws_active) return QGX_OK;
-    std::swap(g->cap_elems, g->ws_other.cap_elems);
-    std::swap(g->actA, g->ws_other.actA); std::swap(g->actB, g->ws_other.actB);
-    std::swap(g->X, g->ws_other.X); std::swap(g->Y0, g->ws_other.Y0); std::swap(g->Y1, g->ws_other.Y1);
-    std::swap(g->part, g->ws_other.part); std::swap(g->part_elems, g->ws_other.part_elems);
-    g->ws_active = idx;
-    return QGX_OK;
-}
-
-static int reserve(qgx_generator *g, int B, int N) {
-    const size_t need = (size_t)B * N * N;
-    if (need <= g->cap_elems) return QGX_OK;
-    float **bufs[] = {&g->actA, &g->actB, &g->X, &g->Y0, &g->Y1};
-    for (auto p : bufs) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    g->cap_elems = 0;
-    if (g->ann) {        // the ANN kernel reads q and writes its raw output (B, 2, N, N): no activations, no input buffer
-        QGX_HIP(hipMalloc((void **)&g->Y0, need * 2 * sizeof(float)));
-        g->cap_elems = need;
-        return QGX_OK;
-    }
-    const size_t actA = g->unet ? std::max(need * 128, unet_workspace_floats(B, N)) : need * 128;
-    QGX_HIP(hipMalloc((void **)&g->actA, actA * sizeof(float)));
-    QGX_HIP(hipMalloc((void **)&g->actB, need * 64 * sizeof(float)));
-    QGX_HIP(hipMalloc((void **)&g->X, need * 6 * sizeof(float)));    // (B, 4, N, N), and behind it (B, 2, N, N) for a regression net
-    QGX_HIP(hipMalloc((void **)&g->Y0, need * 2 * sizeof(float)));
-    QGX_HIP(hipMalloc((void **)&g->Y1, need * 2 * sizeof(float)));
-    g->cap_elems = need;
     return QGX_OK;
 }
 
 // AndrewCNN.forward: x planar (B,n_in,N,N) -> y planar (B,n_out,N,N)
-static int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N,
-                       hipStream_t st) {
+int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N, hipStream_t st) {
     int rc;
     if (g->opt_precision && half_path_ok(g, B, N))
 #ifdef QGX_AB
@@ -2198,7 +1841,7 @@ static int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, flo
 #else
         return cnn_forward_half<2>(g, net, x, y, B, N, st);
 #endif
-    float *A = g->actA, *Bb = g->actB;
+    float *A = g->work().actA, *Bb = g->work().actB;
     if (net.n_in == 4) rc = g->opt_first_split == 2 ? launch_conv<4, 128, 5, 4, true, false, 2>(g, 0, net.L[0], x, A, B, N, 128, st)
                        : g->opt_first_split == 4 ? launch_conv<4, 128, 5, 4, true, false, 4>(g, 0, net.L[0], x, A, B, N, 128, st)
                                                  : launch_conv<4, 128, 5, 4, true, false, 1>(g, 0, net.L[0], x, A, B, N, 128, st);
@@ -2206,11 +1849,10 @@ static int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, flo
             : g->opt_first_split == 4 ? launch_conv<2, 128, 5, 2, true, false, 4>(g, 0, net.L[0], x, A, B, N, 128, st)
                                       : launch_conv<2, 128, 5, 2, true, false, 1>(g, 0, net.L[0], x, A, B, N, 128, st);
     if (rc) return rc;
-    // calibration runs record the largest stored activation of every layer (k_absmax keeps a running maximum
+    // calibration runs record the largest stored activation of every layer (launch_absmax keeps a running maximum
     // in calib_dev[2 * layer + 1]: it updates word [1] of the pair it is given)
     auto rec = [&](int layer, const float *buf, int ch) {
-        if (g->calib_dev)
-            hipLaunchKernelGGL(k_absmax, dim3(256), dim3(256), 0, st, buf, (size_t)B * N * N * ch, g->calib_dev + 2 * layer);
+        if (g->calib_dev) launch_absmax(buf, (size_t)B * N * N * ch, g->calib_dev + 2 * layer, st);
     };
     rec(0, A, 128);
     if ((rc = conv_hidden<128, 64, 5>(g, 1, net.L[1], A, Bb, B, N, st))) return rc;
@@ -2314,8 +1956,9 @@ static int calibrate_wino(qgx_generator *g) {
         // with fewer than eight members the hot, the smooth and the constant ones come first
         static const int PAT8[8] = {0, 1, 2, 3, 4, 5, 6, 7}, PAT4[4] = {3, 5, 7, 0}, PAT2[2] = {3, 5};
         const int *pat = B == 8 ? PAT8 : (B == 4 ? PAT4 : PAT2);
-        rc = reserve(g, B, N);
+        rc = generator_reserve(g, B, N);
         if (rc) break;
+        const Workspace &w = g->work();
         float worst = 0.f;
         for (int n = 0; n < g->n_nets && !rc; ++n) {
             const NetHost &net = g->nets[n];
@@ -2340,15 +1983,15 @@ static int calibrate_wino(qgx_generator *g) {
                             x[(((size_t)b * net.n_in + c) * N + y) * N + xx] = v;
                         }
                 }
-            QGX_HIP(hipMemcpy(g->X, x.data(), x.size() * sizeof(float), hipMemcpyHostToDevice));
+            QGX_HIP(hipMemcpy(w.X, x.data(), x.size() * sizeof(float), hipMemcpyHostToDevice));
             g->opt_precision = 0;
-            rc = cnn_forward(g, net, g->X, g->Y0, B, N, nullptr);
+            rc = cnn_forward(g, net, w.X, w.Y0, B, N, nullptr);
             g->opt_precision = 3; g->opt_wino = 1; g->opt_wino_min_tiles = 1; g->opt_part_max_tiles = 0;
-            if (!rc) rc = cnn_forward(g, net, g->X, g->Y1, B, N, nullptr);
+            if (!rc) rc = cnn_forward(g, net, w.X, w.Y1, B, N, nullptr);
             g->opt_wino = 0; g->opt_wino_min_tiles = saved_min; g->opt_part_max_tiles = saved_part;
             if (rc) break;
             QGX_HIP(hipMemset(cd, 0, 2 * sizeof(unsigned)));
-            hipLaunchKernelGGL(k_absdiff_max, dim3(64), dim3(256), 0, nullptr, (const float *)g->Y1, (const float *)g->Y0,
+            hipLaunchKernelGGL(k_absdiff_max, dim3(64), dim3(256), 0, nullptr, (const float *)w.Y1, (const float *)w.Y0,
                                (size_t)B * net.n_out * npix, cd);
             float h[2];
             QGX_HIP(hipMemcpy(h, cd, sizeof(h), hipMemcpyDeviceToHost));
@@ -2366,11 +2009,10 @@ static int calibrate_wino(qgx_generator *g) {
 }
 
 static int calibrate(qgx_generator *g) {
-    QGX_HIP(hipMalloc((void **)&g->range_dev, 2 * sizeof(unsigned)));
-    QGX_HIP(hipMemset(g->range_dev, 0, 2 * sizeof(unsigned)));
     const int N = 32, B = 8, npix = N * N;
-    int rc = reserve(g, B, N);
+    int rc = generator_reserve(g, B, N);
     if (rc) return rc;
+    const Workspace &w = g->work();
     unsigned *cd = nullptr;
     QGX_HIP(hipMalloc((void **)&cd, 20 * sizeof(unsigned)));
     QGX_HIP(hipMemset(cd, 0, 20 * sizeof(unsigned)));
@@ -2393,18 +2035,18 @@ static int calibrate(qgx_generator *g) {
                         else v = (b == 6 ? 3.f : -3.f) * ((c & 1) ? -1.f : 1.f);         // constants
                         x[(((size_t)b * net.n_in + c) * N + y) * N + xx] = v;
                     }
-        QGX_HIP(hipMemcpy(g->X, x.data(), x.size() * sizeof(float), hipMemcpyHostToDevice));
+        QGX_HIP(hipMemcpy(w.X, x.data(), x.size() * sizeof(float), hipMemcpyHostToDevice));
         g->calib_dev = cd;
-        rc = cnn_forward(g, net, g->X, g->Y0, B, N, nullptr);
+        rc = cnn_forward(g, net, w.X, w.Y0, B, N, nullptr);
         g->calib_dev = nullptr;
         if (rc) break;
         // layer 1 with an identity BatchNorm = what the folded f16x3 variant stores
         LayerHost L0 = net.L[0];
         L0.scale = L0.ones; L0.shift = L0.zeros;
-        rc = net.n_in == 4 ? launch_conv<4, 128, 5, 4, true, false, 2>(g, 0, L0, g->X, g->actA, B, N, 128, nullptr)
-                           : launch_conv<2, 128, 5, 2, true, false, 2>(g, 0, L0, g->X, g->actA, B, N, 128, nullptr);
+        rc = net.n_in == 4 ? launch_conv<4, 128, 5, 4, true, false, 2>(g, 0, L0, w.X, w.actA, B, N, 128, nullptr)
+                           : launch_conv<2, 128, 5, 2, true, false, 2>(g, 0, L0, w.X, w.actA, B, N, 128, nullptr);
         if (rc) break;
-        hipLaunchKernelGGL(k_absmax, dim3(256), dim3(256), 0, nullptr, (const float *)g->actA, (size_t)B * npix * 128, cd + 16);
+        launch_absmax(w.actA, (size_t)B * npix * 128, cd + 16, nullptr);
     }
     g->opt_precision = saved_precision;
     unsigned h[20];
@@ -2437,102 +2079,12 @@ static int calibrate(qgx_generator *g) {
     return QGX_OK;
 }
 
-bool generator_noise_is_double(const qgx_generator *g) { return g->kind == QGX_GEN_GZ; }
-bool generator_takes_noise(const qgx_generator *g) { return g->kind != QGX_GEN_OLS && g->kind != QGX_GEN_ANN; }
-bool generator_reads_q(const qgx_generator *g) { return g->ann != nullptr; }
-
-int generator_input_info(qgx_generator *g, int B, int N, GenFuse *gf) {
-    QGX_REQUIRE(g && gf && g->kind != QGX_GEN_GZ && !g->ann, "generator_input_info: bad argument");
-    int rc = reserve(g, B, N);
-    if (rc) return rc;
-    gf->X = g->X; gf->xs[0] = g->x_std[0]; gf->xs[1] = g->x_std[1]; gf->range = g->range_dev;
-    // OLS: X = float(q)/x_std alone, (B, 2, N, N) as k_prep_input lays it out with n_in = 2
-    gf->xc = g->kind == QGX_GEN_OLS ? 2 : 4;
-    gf->no_noise = g->kind == QGX_GEN_OLS;
-    return QGX_OK;
+int cnn_calibrate(qgx_generator *g) {
+    if (const int rc = calibrate(g)) return rc;
+    return calibrate_wino(g);
 }
-
-// net 0 of a GAN / VAE handle: the AndrewCNN generator / decoder, or the U-Net of qgx_generator_create_unet
-static int net0_forward(qgx_generator *g, const float *x, float *y, int B, int N, hipStream_t st) {
-    if (g->unet) return unet_forward(g->unet, x, y, g->actA, B, N, st);
-    return cnn_forward(g, g->nets[0], x, y, B, N, st);
-}
-
-int generator_forward(qgx_generator *g, const double *q, const void *z, double *S, int B, int N,
-                      int demean, hipStream_t st, const NoiseUpdate *nu, GenFuse *defer, bool input_ready) {
-    QGX_REQUIRE(g && q && (z || !generator_takes_noise(g)) && S && B > 0, "generator_forward: bad argument");
-    QGX_REQUIRE(!g->unet || unet_size_ok(N), "U-Net generator: N = %d is not supported (32, 48, 64, 96 or 128)", N);
-    int rc = reserve(g, B, N);
-    if (rc) return rc;
-    const int npix = N * N;
-    QGX_REQUIRE(npix % 4 == 0, "generator_forward: N*N must be a multiple of 4");
-    dim3 pg((npix + 255) / 256, B), pb(256);
-    if (g->ann) {
-        // ANNModel.predict_snapshot (ann_model.py:82-93): y = net(stencil(float32(q)) / x_scale) per point of each (member,
-        // layer) image, read from q by the kernel itself; S = double(float32(y_scale * y)) is k_finish<FIN_PLAIN> with
-        // ys0 = ys1 = y_scale, or the step kernel's prologue (GenFuse::y).  No latent noise, no input to assemble.
-        if ((rc = ann_forward_q(g->ann, q, g->x_std[0], g->Y0, 2 * (int64_t)B, N, st))) return rc;
-        if (defer) {
-            defer->y = g->Y0; defer->y1 = nullptr;
-            defer->ys[0] = g->y_std[0]; defer->ys[1] = g->y_std[1]; defer->demean = demean;
-            defer->range = g->range_dev;
-        } else {
-            hipLaunchKernelGGL(k_finish<FIN_PLAIN>, dim3(2 * B), dim3(1024), 0, st, (const float *)g->Y0, (const float *)nullptr,
-                               (const double *)nullptr, S, npix, g->y_std[0], g->y_std[1], demean, g->range_dev);
-        }
-    } else if (g->kind == QGX_GEN_GZ) {
-        if (nu && (rc = noise_update(const_cast<void *>(z), nu->xi_ext, true, B, 2 * npix, nu->seed, nu->member_offset,
-                                     nu->step, nu->a, nu->b, st))) return rc;
-        hipLaunchKernelGGL(k_prep_input, pg, pb, 0, st, q, (const float *)nullptr, g->X, 2, npix, g->x_std[0], g->x_std[1], g->range_dev);
-        if ((rc = cnn_forward(g, g->nets[0], g->X, g->Y0, B, N, st))) return rc;
-        if ((rc = cnn_forward(g, g->nets[1], g->X, g->Y1, B, N, st))) return rc;
-        hipLaunchKernelGGL(k_finish<FIN_GZ>, dim3(2 * B), dim3(1024), 0, st, (const float *)g->Y0, (const float *)g->Y1,
-                           (const double *)z, S, npix, g->y_std[0], g->y_std[1], demean, g->range_dev);
-    } else if (g->kind == QGX_GEN_OLS) {
-        // OLSModel.predict_snapshot (ols_model.py:68-75): S = y_std * net(float(q)/x_std); no latent noise, z is never read
-        if (!input_ready)      // (else the previous step kernel wrote X: GenFuse::X with xc = 2, no_noise)
-            hipLaunchKernelGGL(k_prep_input, pg, pb, 0, st, q, (const float *)nullptr, g->X, 2, npix, g->x_std[0], g->x_std[1], g->range_dev);
-        if ((rc = cnn_forward(g, g->nets[0], g->X, g->Y0, B, N, st))) return rc;
-        if (defer) {
-            defer->y = g->Y0; defer->y1 = nullptr;
-            defer->ys[0] = g->y_std[0]; defer->ys[1] = g->y_std[1]; defer->demean = demean;
-            defer->range = g->range_dev;
-        } else {
-            hipLaunchKernelGGL(k_finish<FIN_PLAIN>, dim3(2 * B), dim3(1024), 0, st, (const float *)g->Y0, (const float *)nullptr,
-                               (const double *)nullptr, S, npix, g->y_std[0], g->y_std[1], demean, g->range_dev);
-        }
-    } else {
-        if (input_ready) {
-            // the previous step kernel wrote X and z (GenFuse::X)
-        } else if (nu) {
-            dim3 qg((2 * npix / 4 + 255) / 256, B);
-            hipLaunchKernelGGL(k_prep_noise, qg, pb, 0, st, q, (float *)const_cast<void *>(z), (const float *)nu->xi_ext,
-                               g->X, npix, g->x_std[0], g->x_std[1], nu->seed, nu->member_offset, nu->step,
-                               (float)nu->a, (float)nu->b, g->range_dev);
-        } else {
-            hipLaunchKernelGGL(k_prep_input, pg, pb, 0, st, q, (const float *)z, g->X, 4, npix, g->x_std[0], g->x_std[1], g->range_dev);
-        }
-        const bool regression = g->n_nets == 2;     // regression != 'None': Y += net_mean(X) on the normalised PV alone
-        if (regression) {
-            float *X2 = g->X + (size_t)B * 4 * npix;
-            hipLaunchKernelGGL(k_take2, dim3((2 * npix / 4 + 255) / 256, B), pb, 0, st, (const float *)g->X, X2, 2 * npix);
-            if ((rc = cnn_forward(g, g->nets[1], X2, g->Y1, B, N, st))) return rc;
-        }
-        if ((rc = net0_forward(g, g->X, g->Y0, B, N, st))) return rc;
-        if (defer) {
-            defer->y = g->Y0; defer->y1 = regression ? g->Y1 : nullptr;
-            defer->ys[0] = g->y_std[0]; defer->ys[1] = g->y_std[1]; defer->demean = demean;
-            defer->range = g->range_dev;
-        } else if (regression) {
-            hipLaunchKernelGGL(k_finish<FIN_SUM>, dim3(2 * B), dim3(1024), 0, st, (const float *)g->Y0, (const float *)g->Y1,
-                               (const double *)nullptr, S, npix, g->y_std[0], g->y_std[1], demean, g->range_dev);
-        } else {
-            hipLaunchKernelGGL(k_finish<FIN_PLAIN>, dim3(2 * B), dim3(1024), 0, st, (const float *)g->Y0, (const float *)nullptr,
-                               (const double *)nullptr, S, npix, g->y_std[0], g->y_std[1], demean, g->range_dev);
-        }
-    }
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+void cnn_exact_f32_only(qgx_generator *g) {
+    g->opt_precision = g->auto_precision = 0; g->opt_fold = g->auto_fold = 0; g->opt_wino = 0;
 }
 
 }  // namespace qgx
@@ -2546,117 +2098,6 @@ using namespace qgx;
         QGX_REQUIRE(!(g)->unet, UNET_REFUSE, what);                 \
         QGX_REQUIRE(!(g)->ann, ANN_REFUSE, what);                   \
     } while (0)
-
-extern "C" int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n_nets, const float x_std[2],
-                                    const float y_std[2], int device, qgx_generator **out) {
-    QGX_REQUIRE(nets && out && x_std && y_std, "qgx_generator_create: null argument");
-    QGX_REQUIRE(kind == QGX_GEN_GAN || kind == QGX_GEN_VAE || kind == QGX_GEN_GZ || kind == QGX_GEN_OLS,
-                "unknown generator kind %d", kind);
-    // GAN / VAE: the generator or decoder, and optionally (regression != 'None', cgan_regression.py:59-60) the 2-channel net_mean;
-    // OLS: the one AndrewCNN(2, 2) of OLSModel (ols_model.py:29-31)
-    QGX_REQUIRE(kind == QGX_GEN_GZ ? n_nets == 2 : kind == QGX_GEN_OLS ? n_nets == 1 : (n_nets == 1 || n_nets == 2),
-                "generator kind %d needs %s nets, not %d", kind,
-                kind == QGX_GEN_GZ ? "2" : kind == QGX_GEN_OLS ? "1" : "1 or 2", n_nets);
-    for (int n = 0; n < n_nets; ++n) {      // every net's shape before anything is allocated
-        const int want_in = kind == QGX_GEN_GZ || kind == QGX_GEN_OLS || n == 1 ? 2 : 4;
-        QGX_REQUIRE(nets[n].n_in == want_in && nets[n].n_out == 2, "net %d: n_in=%d n_out=%d, expected %d and 2", n,
-                    nets[n].n_in, nets[n].n_out, want_in);
-    }
-    QGX_HIP(hipSetDevice(device));
-    qgx_generator *g = new (std::nothrow) qgx_generator();
-    if (!g) { set_error("out of host memory"); return QGX_ERR_NOMEM; }
-    g->kind = kind; g->device = device; g->n_nets = n_nets;
-    for (int i = 0; i < 2; ++i) { g->x_std[i] = x_std[i]; g->y_std[i] = y_std[i]; }
-    for (int n = 0; n < n_nets; ++n) {
-        const qgx_cnn_weights *w = &nets[n];
-        NetHost &net = g->nets[n];
-        net.n_in = w->n_in; net.n_out = w->n_out;
-        for (int li = 0; li < 8; ++li) {
-            LayerHost &L = net.L[li];
-            L.cin = li == 0 ? w->n_in : HID[li - 1];
-            L.cout = li == 7 ? w->n_out : HID[li];
-            L.ks = KSZ[li];
-            int rc = pack_layer(L, li, w, li == 0);
-            if (rc) { qgx_generator_destroy(g); return rc; }
-        }
-    }
-    {
-        int rc = calibrate(g);
-        if (!rc) rc = calibrate_wino(g);
-        if (rc) { qgx_generator_destroy(g); return rc; }
-    }
-    *out = g;
-    return QGX_OK;
-}
-
-extern "C" int qgx_generator_create_unet(const qgx_unet_weights *w, const qgx_cnn_weights *net_mean, const float x_std[2],
-                                         const float y_std[2], int device, qgx_generator **out) {
-    QGX_REQUIRE(w && out && x_std && y_std, "qgx_generator_create_unet: null argument");
-    QGX_REQUIRE(!net_mean || (net_mean->n_in == 2 && net_mean->n_out == 2),
-                "qgx_generator_create_unet: net_mean must be an AndrewCNN(2, 2) (n_in=%d n_out=%d)", net_mean->n_in, net_mean->n_out);
-    QGX_HIP(hipSetDevice(device));
-    qgx_generator *g = new (std::nothrow) qgx_generator();
-    if (!g) { set_error("out of host memory"); return QGX_ERR_NOMEM; }
-    g->kind = QGX_GEN_GAN; g->device = device; g->n_nets = net_mean ? 2 : 1;
-    for (int i = 0; i < 2; ++i) { g->x_std[i] = x_std[i]; g->y_std[i] = y_std[i]; }
-    // exact f32 throughout: the U-Net has no f16x3 path, and net_mean takes the exact-f32 AndrewCNN kernels
-    g->opt_precision = g->auto_precision = 0; g->opt_fold = g->auto_fold = 0; g->opt_wino = 0;
-    g->nets[0].n_in = 4; g->nets[0].n_out = 2;
-    int rc = unet_create(w, &g->unet);
-    if (!rc && net_mean) {
-        NetHost &net = g->nets[1];
-        net.n_in = 2; net.n_out = 2;
-        for (int li = 0; li < 8 && !rc; ++li) {
-            LayerHost &L = net.L[li];
-            L.cin = li == 0 ? 2 : HID[li - 1];
-            L.cout = li == 7 ? 2 : HID[li];
-            L.ks = KSZ[li];
-            rc = pack_layer(L, li, net_mean, li == 0);
-        }
-    }
-    if (!rc) {
-        hipError_t e = hipMalloc((void **)&g->range_dev, 2 * sizeof(unsigned));
-        if (e == hipSuccess) e = hipMemset(g->range_dev, 0, 2 * sizeof(unsigned));
-        if (e != hipSuccess) { set_error("qgx_generator_create_unet: %s", hipGetErrorString(e)); rc = QGX_ERR_HIP; }
-    }
-    if (rc) { qgx_generator_destroy(g); return rc; }
-    *out = g;
-    return QGX_OK;
-}
-
-extern "C" int qgx_generator_create_ann(const qgx_ann_weights *w, float x_scale, float y_scale, int device,
-                                        qgx_generator **out) {
-    QGX_REQUIRE(w && out, "qgx_generator_create_ann: null argument");
-    if (int rc = ann_check(w)) return rc;        // every shape before the device is touched
-    QGX_HIP(hipSetDevice(device));
-    qgx_generator *g = new (std::nothrow) qgx_generator();
-    if (!g) { set_error("out of host memory"); return QGX_ERR_NOMEM; }
-    g->kind = QGX_GEN_ANN; g->device = device; g->n_nets = 1;
-    for (int i = 0; i < 2; ++i) { g->x_std[i] = x_scale; g->y_std[i] = y_scale; }   // scalars: one net for both layers
-    g->opt_precision = g->auto_precision = 0; g->opt_fold = g->auto_fold = 0; g->opt_wino = 0;
-    g->nets[0].n_in = 1; g->nets[0].n_out = 1;
-    int rc = ann_create(w, &g->ann);
-    if (!rc) {
-        hipError_t e = hipMalloc((void **)&g->range_dev, 2 * sizeof(unsigned));
-        if (e == hipSuccess) e = hipMemset(g->range_dev, 0, 2 * sizeof(unsigned));
-        if (e != hipSuccess) { set_error("qgx_generator_create_ann: %s", hipGetErrorString(e)); rc = QGX_ERR_HIP; }
-    }
-    if (rc) { qgx_generator_destroy(g); return rc; }
-    *out = g;
-    return QGX_OK;
-}
-
-extern "C" int qgx_generator_range_read(qgx_generator *g, unsigned *flags, float *input_absmax, void *stream) {
-    QGX_REQUIRE(g && flags && input_absmax, "qgx_generator_range_read: null argument");
-    unsigned h[2] = {0, 0};
-    QGX_HIP(hipMemcpyAsync(h, g->range_dev, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    QGX_HIP(hipMemsetAsync(g->range_dev, 0, sizeof(h), (hipStream_t)stream));
-    QGX_HIP(hipStreamSynchronize((hipStream_t)stream));
-    *flags = h[0];
-    memcpy(input_absmax, &h[1], sizeof(float));
-    return QGX_OK;
-}
-
 extern "C" int qgx_generator_wino_info_n(const qgx_generator *g, int N, int *enabled, int *chosen_by_calibration, float *calibration_error) {
     QGX_REQUIRE(g, "qgx_generator_wino_info_n: null generator");
     REFUSE_NON_ANDREW(g, "qgx_generator_wino_info_n");
@@ -2668,28 +2109,13 @@ extern "C" int qgx_generator_wino_info_n(const qgx_generator *g, int N, int *ena
 }
 
 // which kernel the 5x5 layer (layer 2) of net `inet` takes for an ensemble of B members at N x N with the options in
-// force: 0 exact-f32 MFMA, 1 the 25-tap f16x3 kernel, 2 its split-K form (tiny ensembles), 3 1-D Winograd (k_convw),
-// 4 1-D Winograd with the transform under the MFMAs (k_convw2).  Mirrors cnn_forward_half / launch_convw.
+// force (Layer2Plan::kernel): 0 exact-f32 MFMA, 1 the 25-tap f16x3 kernel, 2 its split-K form (tiny ensembles), 3 1-D
+// Winograd (k_convw), 4 1-D Winograd with the transform under the MFMAs (k_convw2)
 extern "C" int qgx_generator_layer2_kernel(const qgx_generator *g, int inet, int B, int N, int *kernel) {
     QGX_REQUIRE(g && kernel, "qgx_generator_layer2_kernel: null argument");
     REFUSE_NON_ANDREW(g, "qgx_generator_layer2_kernel");
     QGX_REQUIRE(inet >= 0 && inet < g->n_nets, "qgx_generator_layer2_kernel: net %d of %d", inet, g->n_nets);
-    const NetHost &net = g->nets[inet];
-    *kernel = 0;
-    if (g->opt_precision != 3 || rows_h2(N) <= 0) return QGX_OK;
-    const bool fold = g->opt_first_h && g->opt_fold && net.L[1].whF;
-    const int r2 = rows_h2(N);
-    const bool tiny = g->opt_h2 == 3 && r2 > 0 && B * (N / r2) < g->opt_part_max_tiles;
-    if (tiny) { *kernel = 2; return QGX_OK; }
-    *kernel = 1;
-    if (g->opt_first_h && wino_applies(g, net.L[1], fold ? 1 : 0, B, N)) {
-        *kernel = 3;
-        if (g->opt_wino2 && !wino_planar(g) && g->opt_wino_exp == 0) {
-            bool rows_full = true;       // the full-height shape of launch_convw (k_convw2 exists for it at 64 x 64 and as 12 rows at 96 x 96)
-            if (N == 64) { const int r8 = (B * 8 + 255) / 256, r4 = (B * 16 + 255) / 256; rows_full = !(g->opt_wino_rows64 == 4 || (g->opt_wino_rows64 == 0 && 0.66 * r4 < 1.0 * r8)); if (rows_full) *kernel = 4; }
-            else if (N == 96) { const int r16 = (B * 18 + 255) / 256, r12 = (B * 24 + 255) / 256; if (g->opt_wino_rows96 == 12 || (g->opt_wino_rows96 == 0 && 0.79 * r12 < 1.0 * r16)) *kernel = 4; }
-        }
-    }
+    *kernel = plan_layer2(g, g->nets[inet], B, N).kernel;
     return QGX_OK;
 }
 
@@ -2710,51 +2136,6 @@ extern "C" int qgx_generator_info(const qgx_generator *g, int *precision, int *a
     if (fold) *fold = g->opt_fold;
     if (layer_absmax) memcpy(layer_absmax, g->calib_max, sizeof(g->calib_max));
     return QGX_OK;
-}
-
-extern "C" int qgx_generator_destroy(qgx_generator *g) {
-    if (!g) return QGX_OK;
-    (void)hipSetDevice(g->device);
-    for (int n = 0; n < 2; ++n)
-        for (int li = 0; li < 8; ++li) {
-            LayerHost &L = g->nets[n].L[li];
-            float *ptrs[] = {L.w, L.w32, L.wl16, L.wl8, L.bias, L.scale, L.shift};
-            for (float *p : ptrs) if (p) (void)hipFree(p);
-            for (void *p : L.wh) if (p) (void)hipFree(p);
-            if (L.whf) (void)hipFree(L.whf);
-            if (L.wh16) (void)hipFree(L.wh16);
-            if (L.whF) (void)hipFree(L.whF);
-            for (void *pw_ : L.ww) if (pw_) (void)hipFree(pw_);
-            if (L.wh16F) (void)hipFree(L.wh16F);
-            for (float *p : {L.biasF, L.ones, L.zeros}) if (p) (void)hipFree(p);
-        }
-    float *bufs[] = {g->actA, g->actB, g->X, g->Y0, g->Y1, g->part,
-                     g->ws_other.actA, g->ws_other.actB, g->ws_other.X, g->ws_other.Y0, g->ws_other.Y1, g->ws_other.part};
-    for (float *p : bufs) if (p) (void)hipFree(p);
-    if (g->range_dev) (void)hipFree(g->range_dev);
-    unet_destroy(g->unet);
-    ann_destroy(g->ann);
-    for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
-    delete g;
-    return QGX_OK;
-}
-
-extern "C" int qgx_generator_forward(qgx_generator *g, const double *q_dev, const void *z_dev, double *S_dev,
-                                     int B, int N, int demean, void *stream) {
-    return generator_forward(g, q_dev, z_dev, S_dev, B, N, demean, (hipStream_t)stream, nullptr);
-}
-
-extern "C" int qgx_cnn_forward(qgx_generator *g, int inet, const float *x_dev, float *y_dev, int B, int N,
-                               void *stream) {
-    QGX_REQUIRE(g && x_dev && y_dev && inet >= 0 && inet < g->n_nets && B > 0, "qgx_cnn_forward: bad argument");
-    QGX_REQUIRE(!(g->unet && inet == 0) || unet_size_ok(N), "U-Net generator: N = %d is not supported (32, 48, 64, 96 or 128)", N);
-    int rc = reserve(g, B, N);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_absmax, dim3(256), dim3(256), 0, (hipStream_t)stream, x_dev,
-                       (size_t)B * g->nets[inet].n_in * N * N, g->range_dev);
-    if (g->ann) return ann_forward_x(g->ann, x_dev, y_dev, B, N, (hipStream_t)stream);   // (B, 1, N, N) -> (B, 1, N, N)
-    if (inet == 0) return net0_forward(g, x_dev, y_dev, B, N, (hipStream_t)stream);
-    return cnn_forward(g, g->nets[inet], x_dev, y_dev, B, N, (hipStream_t)stream);
 }
 
 extern "C" int qgx_generator_profile(qgx_generator *g, int layer) {
@@ -2848,7 +2229,7 @@ extern "C" int qgx_generator_set_option(qgx_generator *g, const char *name, int 
 // A/B library, debugging: copy the first nbytes of activation buffer `which` (0: the odd layers' outputs, 1: the even layers')
 extern "C" int qgx_debug_read_act(qgx_generator *g, int which, void *dst_dev, size_t nbytes, void *stream) {
     QGX_REQUIRE(g && dst_dev, "qgx_debug_read_act: null argument");
-    QGX_HIP(hipMemcpyAsync(dst_dev, which ? (const void *)g->actB : (const void *)g->actA, nbytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    QGX_HIP(hipMemcpyAsync(dst_dev, which ? (const void *)g->work().actB : (const void *)g->work().actA, nbytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return QGX_OK;
 }
 #endif
@@ -2860,12 +2241,3 @@ extern "C" int qgx_debug_set_stamps(qgx_generator *g, void *buf, int layer) {
     return QGX_OK;
 }
 #endif
-
-extern "C" int qgx_moments_accumulate(const float *y_dev, double *sum_dev, double *sumsq_dev, size_t n, void *stream) {
-    QGX_REQUIRE(y_dev && sum_dev && sumsq_dev && n > 0, "qgx_moments_accumulate: bad argument");
-    const size_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(k_moments, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, (hipStream_t)stream,
-                       y_dev, sum_dev, sumsq_dev, n);
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
-}

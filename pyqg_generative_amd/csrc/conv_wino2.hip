@@ -35,12 +35,22 @@ static int launch_convw2_n(const ConvWArgs &a, int total_tiles, hipStream_t st) 
     return QGX_OK;
 }
 
-// the tile shapes this kernel is built for (those where it measured faster than k_convw: bench_tools/wino2_dev.hip);
-// *done = false: not one of them, the caller takes k_convw
+// the tile shapes this kernel is built for (those where it measured faster than k_convw: bench_tools/wino2_dev.hip)
+#define QGX_CONVW2_SHAPES(X) X(64, 64, 8) X(96, 32, 12)
+
+bool convw2_takes(int N, int TW, int R) {
+#define QGX_W2_IS(NN, TWV, RV) if (N == NN && TW == TWV && R == RV) return true;
+    QGX_CONVW2_SHAPES(QGX_W2_IS)
+#undef QGX_W2_IS
+    return false;
+}
+
+// *done = false: not one of the shapes, the caller takes k_convw
 int launch_convw2(int N, int TW, int R, const ConvWArgs &a, int total_tiles, hipStream_t st, bool *done) {
     *done = true;
-    if (N == 64 && TW == 64 && R == 8) return launch_convw2_n<64, 64, 8>(a, total_tiles, st);
-    if (N == 96 && TW == 32 && R == 12) return launch_convw2_n<96, 32, 12>(a, total_tiles, st);
+#define QGX_W2_LAUNCH(NN, TWV, RV) if (N == NN && TW == TWV && R == RV) return launch_convw2_n<NN, TWV, RV>(a, total_tiles, st);
+    QGX_CONVW2_SHAPES(QGX_W2_LAUNCH)
+#undef QGX_W2_LAUNCH
     *done = false;
     return QGX_OK;
 }

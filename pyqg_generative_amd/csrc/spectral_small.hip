@@ -194,7 +194,7 @@ __global__ void k_step_small(SpecDev d, StepArgs a) {
     if (fside && a.has_S) {
         const double *S0 = a.S + ro, *S1 = S0 + rz;
         if (LSPLIT && a.gf.y) {
-            // the generator's output kernel folded in (k_finish<FIN_PLAIN>, conv.hip: same arithmetic, same summation order —
+            // the generator's output kernel folded in (k_finish<FIN_PLAIN>, generator.hip: same arithmetic, same summation order —
             // 1024 threads, per-thread partial sums over u, wave shuffles, waves in order): S = double(y * y_std) - mean
             constexpr int KEEP = 16;
             __shared__ double fin_sm[16];
@@ -427,7 +427,7 @@ __global__ void k_step_small(SpecDev d, StepArgs a) {
         const double2 w = Z[y * LD + x];
         if (LSPLIT) {
             a.q[ro + kown * rz + idx] = w.x;
-            if (a.gf.X) {       // the next step's network input, channel kown: float(q) / x_std (k_prep_noise / k_prep_input, conv.hip)
+            if (a.gf.X) {       // the next step's network input, channel kown: float(q) / x_std (k_prep_noise / k_prep_input, generator.hip)
                 const float xq = (float)w.x / a.gf.xs[kown];
                 a.gf.X[((size_t)b * a.gf.xc + kown) * rz + idx] = xq;
                 in_max = fmaxf(in_max, xq != xq ? __uint_as_float(0x7f800000u) : fabsf(xq));
@@ -438,7 +438,7 @@ __global__ void k_step_small(SpecDev d, StepArgs a) {
         }
     }
     if (LSPLIT && a.gf.X) {
-        // largest |network input| for the f16x3 range guard (input_absmax, conv.hip)
+        // largest |network input| for the f16x3 range guard (input_absmax, generator.hip)
         for (int o = 32; o > 0; o >>= 1) in_max = fmaxf(in_max, __shfl_down(in_max, o));
         if ((threadIdx.x & 63) == 0 && __float_as_uint(in_max) > __builtin_nontemporal_load(a.gf.range + 1))
             atomicMax(a.gf.range + 1, __float_as_uint(in_max));

@@ -213,11 +213,21 @@ typedef struct qgx_cnn_weights {      /* host pointers, float32, PyTorch layouts
  * OLS — the deterministic AndrewCNN(2, 2) `net` of OLSModel (ols_model.py:29-31), S = y_std * net(q/x_std) (:68-75): n_nets 1,
  * n_in 2.  It takes no latent noise: qgx_generator_forward ignores z (NULL allowed), qgx_step draws none and writes no z,
  * and refuses z_external_dev; the sampler still decides when the forcing is recomputed (generate_latent_noise returns 0,
- * parameterization.py:23-34).  Any other n_nets, n_in or n_out is refused (QGX_ERR_INVALID) before any allocation. */
+ * parameterization.py:23-34).  Any other n_nets, n_in or n_out is refused (QGX_ERR_INVALID) before any allocation.
+ * Grid sizes: the AndrewCNN kernels of such a handle run N = 16, 32, 48, 64, 96 and 128 (every member count).  The
+ * other sizes qgx_create admits have no whole number of the kernels' row tiles (8, 12, 24 and every size that divides
+ * neither 256 nor 384) or a 5x5-layer patch beyond the LDS (192, 256, 384).  qgx_generator_forward, qgx_cnn_forward and
+ * qgx_step refuse them with QGX_ERR_INVALID and a message naming N BEFORE anything is launched or changed: after a refused qgx_step the model (step count, state, latent noise, sampler) is bitwise where it was and
+ * the generator handle stays usable (tests/test_gpu_grid_sizes.py records the admitted set;
+ * qgx_generator_size_ok asks without running anything, for the options in force: with "chunk" = 16 the patch fits at 192
+ * and 256 as well, sizes no test runs the nets at). */
 int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n_nets,
                          const float x_std[2], const float y_std[2], int device,
                          qgx_generator **out);
 int qgx_generator_destroy(qgx_generator *g);
+/* QGX_OK if the kernels of the handle's nets (inet >= 0: of that net alone; -1: of all of them) run B members at N x N
+ * under the options in force, else QGX_ERR_INVALID with the message the three entry points above give.  No device call. */
+int qgx_generator_size_ok(const qgx_generator *g, int inet, int B, int N);
 
 /* The DeepInversion U-Net generator of CGANRegression(generator='DeepInversion') (cgan_regression.py:50-53): the
  * DeepInversionGenerator(4, 2) of tools/deep_inversion.py:44-94, blocks res_unit / down / up at :104-160, as the forecast

@@ -240,6 +240,8 @@ struct NoiseUpdate {
 // (GenFuse::y ...); input_ready: the previous step kernel already assembled the network input (GenFuse::X ...)
 int generator_forward(qgx_generator *g, const double *q, const void *z, double *S, int B, int N,
                       int demean, hipStream_t st, const NoiseUpdate *nu, GenFuse *defer = nullptr, bool input_ready = false);
+// QGX_OK if the handle's nets (inet >= 0: that net alone) run B members at N x N, else QGX_ERR_INVALID naming N; no HIP call
+int generator_size_ok(const qgx_generator *g, int B, int N, int inet = -1);
 // the generator's input buffer, input scales and range words for the GenFuse::X part (after reserve)
 int generator_input_info(qgx_generator *g, int B, int N, GenFuse *gf);
 bool small_layer_split(const SpecDev &d, const ModelOpts &o);

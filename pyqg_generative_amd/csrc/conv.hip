@@ -1116,21 +1116,31 @@ static int conv_hidden(qgx_generator *g, int layer, const LayerHost &L, const fl
     return launch_conv<CIN, COUT, KS, 16, false, false>(g, layer, L, in, out, B, N, COUT, st);
 }
 
-static int launch_conv_last(qgx_generator *g, const LayerHost &L, const float *in, float *out, int B, int N,
-                            int n_out, hipStream_t st) {
+// rows per workgroup of the VALU last layer
+static int last_rows(const qgx_generator *g, int B, int N) {
     int R = choose_rows(N);
     if (g->opt_small && R > 0 && B * (N / R) <= 192) R = 1;      // small ensembles: one row per workgroup
     else if (R > 2 && N % 2 == 0) R = 2;                         // 37-55 KB of LDS: 2-4 workgroups per CU hide the
                                                                  // load -> barrier -> compute -> store chain (-10..-20 %)
     if (g->opt_last_rows > 0 && N % g->opt_last_rows == 0) R = g->opt_last_rows;
+    return R;
+}
+static size_t last_lds_bytes(int R, int N) {
+    const bool split = R * N == 64;                        // one wave of pixels: the waves split the channels
+    return (size_t)(R + 2) * N * 36 * sizeof(float) + (split ? 4 * 64 * 2 * sizeof(float) : 0);
+}
+
+static int launch_conv_last(qgx_generator *g, const LayerHost &L, const float *in, float *out, int B, int N,
+                            int n_out, hipStream_t st) {
+    const int R = last_rows(g, B, N);
     QGX_REQUIRE(R > 0 && N % R == 0, "generator: unsupported grid size N=%d", N);
     ProfScope prof;
     if (const int prc = prof.begin(g, 7, st)) return prc;
     ConvArgs a = {};
     a.in = in; a.out = out; a.w = nullptr; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
     a.N = N; a.R = R; a.cout_real = n_out;
-    const bool split = R * N == 64;                        // one wave of pixels: the waves split the channels
-    const size_t lds = (size_t)(R + 2) * N * 36 * sizeof(float) + (split ? 4 * 64 * 2 * sizeof(float) : 0);
+    const bool split = R * N == 64;
+    const size_t lds = last_lds_bytes(R, N);
     QGX_REQUIRE(lds <= 160 * 1024, "generator: LDS patch %zu B too large for N=%d", lds, N);
     if (split) {
         auto kern = k_conv_last<32, 3, 4>;
@@ -1873,6 +1883,37 @@ int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, float *y, 
     return QGX_OK;
 }
 
+// Whether cnn_forward takes B members at N x N under the options in force: the conditions its launchers assert, gathered so
+// that every entry point (qgx_generator_forward, qgx_cnn_forward, qgx_step) refuses a grid BEFORE its first launch and before
+// the stepper touches the sampler state; the launchers' own QGX_REQUIREs stay as backstops.  k_conv3 is an optimisation that
+// hands a layer back when its tile does not fit, so the exact-f32 conditions are those of k_conv (or of the split-K form of
+// small ensembles) and of the last layer.  With the shipped options: N = 16, 32, 48, 64, 96, 128 — 8, 12 and 24 have no
+// whole number of row tiles, and from 192 on the 5x5 layer's 32-channel patch (R + 4 rows of N pixels) exceeds the LDS.
+bool cnn_size_ok(const qgx_generator *g, const NetHost &net, int B, int N) {
+    const int R = choose_rows(N);
+    if (B < 1 || R <= 0 || N % R) return false;
+    if (g->opt_precision && half_path_ok(g, B, N)) {
+#ifdef QGX_AB
+        if (rows_h2(N) <= 0) return true;      // kernels of the A/B library's experiments: their launchers decide
+#endif
+        return rows_h2(N) > 0 && N % 4 == 0;
+    }
+    constexpr size_t LIM = 160 * 1024;
+    auto patch = [&](int rows, int ks, int stride) { return (size_t)(rows + ks - 1) * N * stride * sizeof(float); };
+    if (patch(R, 5, net.n_in) > LIM) return false;                                        // layer 1: planar input
+    const bool small = g->opt_small && small_ensemble(B, N);
+    for (int l = 1; l < 7; ++l) {
+        const int cin = l == 1 ? 128 : (l == 2 ? 64 : 32), ks = l == 1 ? 5 : 3;
+        const size_t lds = small ? patch(rows_small(N), ks, (cin >= 64 ? 16 : 32) + 4)
+                                 : patch(R, ks, (g->opt_cc == 32 ? 32 : 16) + 4);
+        if (lds > LIM) return false;
+    }
+    if (g->opt_last_valu) {
+        const int Rl = last_rows(g, B, N);
+        return Rl > 0 && N % Rl == 0 && last_lds_bytes(Rl, N) <= LIM;
+    }
+    return patch(R, 3, 16 + 4) <= LIM;
+}
 
 // ---- f16x3 range calibration (run once by qgx_generator_create) ------------------------------------------------
 // The f16x3 arithmetic stores every activation x as hi = f16(s x), lo = f16(s x - hi) with ONE power-of-two scale s

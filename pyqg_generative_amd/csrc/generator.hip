@@ -258,10 +258,28 @@ static void finish(qgx_generator *g, GenFuse *defer, int mode, const float *y1, 
     else launch_finish<FIN_PLAIN>(g, y1, z, S, B, npix, demean, st);
 }
 
+// The one grid-size rule of a handle, asked by qgx_generator_forward, qgx_cnn_forward (inet >= 0: that net alone) and
+// qgx_step before anything is launched or any sampler state is touched: net 0 of a U-Net handle takes unet_size_ok's grids,
+// every AndrewCNN what its launchers take (cnn_size_ok), the ANN every N its own launcher admits (ann.hip, before its launch).
+int generator_size_ok(const qgx_generator *g, int B, int N, int inet) {
+    QGX_REQUIRE(g && B > 0, "generator: bad argument");
+    if (g->ann) return QGX_OK;
+    for (int n = 0; n < g->n_nets; ++n) {
+        if (inet >= 0 && n != inet) continue;
+        if (g->unet && n == 0) {
+            QGX_REQUIRE(unet_size_ok(N), "U-Net generator: N = %d is not supported (32, 48, 64, 96 or 128)", N);
+            continue;
+        }
+        QGX_REQUIRE(cnn_size_ok(g, g->nets[n], B, N),
+                    "generator: N = %d is not supported by the AndrewCNN kernels (B = %d; with the shipped options 16, 32, 48, 64, 96 or 128)", N, B);
+    }
+    return QGX_OK;
+}
+
 int generator_forward(qgx_generator *g, const double *q, const void *z, double *S, int B, int N,
                       int demean, hipStream_t st, const NoiseUpdate *nu, GenFuse *defer, bool input_ready) {
     QGX_REQUIRE(g && q && (z || !generator_takes_noise(g)) && S && B > 0, "generator_forward: bad argument");
-    QGX_REQUIRE(!g->unet || unet_size_ok(N), "U-Net generator: N = %d is not supported (32, 48, 64, 96 or 128)", N);
+    if (const int src = generator_size_ok(g, B, N)) return src;
     int rc = generator_reserve(g, B, N);
     if (rc) return rc;
     const int npix = N * N;
@@ -422,10 +440,15 @@ extern "C" int qgx_generator_forward(qgx_generator *g, const double *q_dev, cons
     return generator_forward(g, q_dev, z_dev, S_dev, B, N, demean, (hipStream_t)stream, nullptr);
 }
 
+extern "C" int qgx_generator_size_ok(const qgx_generator *g, int inet, int B, int N) {
+    QGX_REQUIRE(g && inet >= -1 && inet < g->n_nets, "qgx_generator_size_ok: bad argument");
+    return generator_size_ok(g, B, N, inet);
+}
+
 extern "C" int qgx_cnn_forward(qgx_generator *g, int inet, const float *x_dev, float *y_dev, int B, int N,
                                void *stream) {
     QGX_REQUIRE(g && x_dev && y_dev && inet >= 0 && inet < g->n_nets && B > 0, "qgx_cnn_forward: bad argument");
-    QGX_REQUIRE(!(g->unet && inet == 0) || unet_size_ok(N), "U-Net generator: N = %d is not supported (32, 48, 64, 96 or 128)", N);
+    if (const int src = generator_size_ok(g, B, N, inet)) return src;
     int rc = generator_reserve(g, B, N);
     if (rc) return rc;
     launch_absmax(x_dev, (size_t)B * g->nets[inet].n_in * N * N, g->range_dev, (hipStream_t)stream);

@@ -141,6 +141,8 @@ int cnn_calibrate(qgx_generator *g);          // range calibration, then the Win
 void cnn_exact_f32_only(qgx_generator *g);    // U-Net and ANN handles: a net_mean beside them takes the exact-f32 kernels
 // AndrewCNN.forward: x planar (B,n_in,N,N) -> y planar (B,n_out,N,N)
 int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N, hipStream_t st);
+// whether cnn_forward's launchers take B members at N x N under the options in force (no HIP call)
+bool cnn_size_ok(const qgx_generator *g, const NetHost &net, int B, int N);
 
 // ---- generator.hip, called by conv.hip ----
 int generator_reserve(qgx_generator *g, int B, int N);       // the active workspace's activation buffers for B members at N x N

@@ -712,6 +712,12 @@ extern "C" int qgx_step(qgx_model *m, int nsteps, const qgx_param *p, int refres
     QGX_NEEDS_STATE(m, "qgx_step");
     QGX_REQUIRE(m && nsteps >= 0, "qgx_step: bad argument");
     hipStream_t st = (hipStream_t)stream;
+    // a grid the generator's kernels do not take is refused here: before any launch, and before step_core touches the
+    // sampler state (the halves of an ensemble stepped on two streams ask the kernels for B / 2 members)
+    if (p && p->gen && nsteps > 0) {
+        if (int src = generator_size_ok(p->gen, m->B, m->N)) return src;
+        if (step_in_halves(m, p)) { if (int src = generator_size_ok(p->gen, m->B / 2, m->N)) return src; }
+    }
     { int trc = team_settle(m, st); if (trc) return trc; }
     if (p && p->gen && nsteps > 0) { int arc = step_adv_ensure(m); if (arc) return arc; }
     if (p && (p->gen || p->forcing_dev) && nsteps > 0) { int src = step_sib_ensure(m); if (src) return src; }

@@ -903,6 +903,8 @@ int large_step(qgx_model *m, const StepArgs &a, hipStream_t st) {
 #endif
         if (!generic && N == 256) QGX_L3(256, 2, 512, 8, 1024, 4, 512)
         else if (!generic && N == 128) QGX_L3(128, 2, 512, 8, 1024, 4, 512)
+        // (512: not reached by the product library — lines_per_block(512) is 2, so the test above hands every 512 x 512 step
+        // to large_step_unfused; only the A/B library with QGX_LARGE_LPB=4 in the environment arrives here.  DESIGN 3.1)
         else if (!generic && N == 512) QGX_L3(512, 1, 256, 4, 512, 2, 256)
         else {
             static const int t1 = tune_env("QGX_LARGE_T1", 256);   // tuning aids (A/B library): threads

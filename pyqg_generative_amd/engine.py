@@ -42,6 +42,7 @@ class Generator:
         self.x_std = np.asarray(x_std, np.float32).reshape(-1)
         self.y_std = np.asarray(y_std, np.float32).reshape(-1)
         self.unet = bool(nets) and is_unet(nets[0])
+        self.n_nets = len(nets)
         if kind == 'ann':
             # ANNModel's stencil network: nets = [weights.ann_from_state_dict dict], x_std / y_std the scalars x_scale, y_scale
             if len(nets) != 1 or self.x_std.size != 1 or self.y_std.size != 1:
@@ -216,6 +217,15 @@ class Generator:
             del self.check_range            # back to the class default
         return out
 
+    def check_size(self, B, N, inet=-1):
+        """ValueError for a grid the kernels of this handle (inet >= 0: of that net alone) do not run — the library's own
+        rule (qgx_generator_size_ok: the AndrewCNN kernels take 16, 32, 48, 64, 96, 128 with the shipped options, the U-Net
+        32 ... 128), asked here before any buffer is allocated"""
+        if inet not in range(-1, self.n_nets) or B < 1:
+            return                          # not a question of the grid: the call itself refuses it (QgxError)
+        if lib.qgx_generator_size_ok(self._h, int(inet), int(B), int(N)) != 0:
+            raise ValueError(lib.qgx_last_error().decode())
+
     def forward(self, q, z=None, demean=True, out=None):
         """q: (B,2,N,N) float64 cuda; z: (B,2,N,N) float32 (float64 for gz; 'ols' and 'ann' take none) -> S (B,2,N,N) float64."""
         assert q.is_cuda and q.dtype == torch.float64 and q.is_contiguous() and q.dim() == 4
@@ -226,8 +236,7 @@ class Generator:
         else:
             assert z is not None and z.is_cuda and z.dtype == self.noise_dtype and z.is_contiguous()
             assert z.numel() == q.numel()
-        if self.unet and N not in (32, 48, 64, 96, 128):
-            raise ValueError(f'the U-Net generator runs on N = 32, 48, 64, 96 or 128, not {N}')
+        self.check_size(B, N)
         S = out if out is not None else torch.empty_like(q)
 
         def launch():
@@ -241,8 +250,7 @@ class Generator:
         n_in = 2 if (self.kind in ('gz', 'ols') or inet == 1) else 4   # net 1 of a GAN / VAE generator: the regression net
         n_in, n_out = (1, 1) if self.kind == 'ann' else (n_in, 2)
         B, _, N, _ = x.shape
-        if self.unet and inet == 0 and N not in (32, 48, 64, 96, 128):
-            raise ValueError(f'the U-Net generator runs on N = 32, 48, 64, 96 or 128, not {N}')
+        self.check_size(B, N, inet)
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == n_in
         B, _, N, _ = x.shape
         y = torch.empty((B, n_out, N, N), dtype=torch.float32, device=x.device)
@@ -418,6 +426,8 @@ class EnsembleEngine:
         if generator is not None or forcing is not None:
             p = _lib.qgx_param()
             p.gen = generator._h if generator is not None else None
+            if generator is not None:
+                generator.check_size(self.B, self.N)
             if generator is not None and generator not in self._generators:
                 self._generators.append(generator)
             p.sampling = {'AR1': _lib.SAMPLING_AR1, 'constant': _lib.SAMPLING_CONSTANT}[sampling]

@@ -88,6 +88,26 @@ def test_forward_matches_reference_golden(tag):
     assert g.range_ok() is None
 
 
+@pytest.mark.parametrize('tag', ['a', 'c'])
+def test_forward_matches_restatement_beyond_the_golden_sizes(tag):
+    """the ANN kernel takes every N up to 512; the golden vectors stop at 128.  24, 72, 162 and 512 against the test-side
+    restatement (tests/ann_restatement.py, held to the reference's vectors in tests/test_ann_cpu.py): 2e-5 of max|S| as above"""
+    from ann_restatement import ANNRef
+    g = _gpu_ann(tag)
+    ora = ANNRef.from_fixture(tag)
+    worst = 0.0
+    for N in (24, 72, 162, 512):
+        for B in ((1, 3) if N < 512 else (1,)):       # (the restatement holds every stencil feature of a batch in memory)
+            q = _eddy_like_q(np.random.RandomState(N + B), B, N)
+            out = g.forward(torch.as_tensor(q).cuda(), demean=False).cpu().numpy()
+            ref = ora.predict_snapshot(q, 0)
+            err = max(_rel(out[b], ref[b]) for b in range(B))
+            worst = max(worst, err)
+            assert err < 2e-5, (N, B, err)
+    print(f'\nANN net {tag}: max error {worst:.2e} of max|S| over N = 24, 72, 162, 512')
+    assert g.range_ok() is None
+
+
 def test_zero_norm_stencils_give_nan_as_the_reference():
     """scale_invariant: a stencil of norm 0 is 0/0 = NaN in torch, and ReLU keeps it NaN: the zero lower layer of
     the reference's initial condition gives a NaN forcing there, the upper layer is finite"""

@@ -93,7 +93,7 @@ def test_paramspec_and_dataset_export():
     m.close()
 
 
-@pytest.mark.parametrize('N,fused', [(128, 1), (128, 0), (256, 1)])
+@pytest.mark.parametrize('N,fused', [(128, 1), (128, 0), (256, 1), (192, 1)])      # 192: the composed increment by default
 def test_large_grid_increment_with_a_forcing_matches_oracle(N, fused):
     """large grids: the three-launch increment (four packed fields through fused row / column kernels, xi eliminated through
     q = xi + F (p_2 - p_1)) and the composed one (option large_fused = 0: one launch per transform) with an external forcing

@@ -52,7 +52,11 @@ def _eddy_like_q(rs, B, N):
     return np.fft.irfftn(qh, axes=(-2, -1)) * 3.0
 
 
-@pytest.mark.parametrize('N', [32, 48, 64, 96, 128, 192, 256])
+# every size qgx_create admits (tests/test_gpu_grid_sizes.py asserts that these are all of them)
+ALL_SIZES = [8, 12, 16, 18, 24, 32, 36, 48, 54, 64, 72, 96, 108, 128, 144, 162, 192, 216, 256, 288, 324, 384, 432, 486, 512]
+
+
+@pytest.mark.parametrize('N', ALL_SIZES)
 def test_q_qh_roundtrip_and_invert(N):
     import pyqg_generative_amd._lib as L
     B = 3

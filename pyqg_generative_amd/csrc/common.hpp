@@ -75,7 +75,7 @@ struct ModelOpts {
     int step_fault = 0;          //   A/B library only: half-ensemble (1 | 2) of a two-stream qgx_step refuses its second chunk (test hook)
     int large_fused = 1;         // large grids: fused row / column kernels (0: one launch per pass and pointwise phase)
     int large_lazy_q = 1;        // large grids: unparameterized steps keep no real-space q
-    int large_specialised = 1;   // large grids: compile-time-N kernels at 128 / 256 / 512
+    int large_specialised = 1;   // large grids: compile-time-N kernels at 128 / 256; diagnostics also 512
 };
 
 // Tile-shape tuning aids read from the environment exist in the A/B library only (make ab); the product library

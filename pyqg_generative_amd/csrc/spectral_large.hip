@@ -4,22 +4,25 @@
 // row-line kernel plus a column-line kernel that stage lines through LDS.
 // Global fields are always in natural order; the digit-reversal of the in-place DIF/DIT passes
 // is absorbed when a line is staged into / out of LDS.
+// The per-element arithmetic (inversion, Hermitian extension, pack / unpack, tendency, AB3 + filter) is that of
+// spectral_elem.hpp, shared with spectral_small.hip; the compile-time-N kernels of 128 / 256 (step and diagnostics
+// increment) and 512 (increment only) take their tile shapes from the one table LargeTiles.
 //
 // Restates pyqg 0.7.2 kernel.pyx::{_invert,_do_advection,_do_friction,
 // _do_q_subgrid_parameterization,_forward_timestep} (reference call sites:
 // pyqg_generative/tools/simulate.py:83-88 — the 256^2 forcing-dataset runs).
 #include "common.hpp"
 #include "fft_lds.hpp"
+#include "spectral_elem.hpp"
 #include "diag_acc.hpp"
 #include <cstdlib>
 
 namespace qgx {
 
 constexpr int ZF = 3;   // complex N x N work fields per member in zbuf: layers 0,1 and one scratch (S / q pair)
+constexpr int DZF = 4;  // complex work fields per member of the fused diagnostics increment (dg_z)
 
 extern __shared__ __attribute__((aligned(16))) char lg_smem[];
-
-__device__ __forceinline__ int neg_mod_l(int j, int N) { return j == 0 ? 0 : N - j; }
 
 // ---- batched 1-D FFT along x (ALONG_Y = false) or y (true) of `nf` complex N x N fields -------
 // The fields are zbuf[b][k0 .. k0+nfpm) for every member b.  One workgroup transforms LPB lines.
@@ -58,16 +61,11 @@ __global__ void k_lines_fft(SpecDev d, double2 *base, int k0, int nfpm, int LPB)
 }
 
 // ---- pointwise kernels (grid: x over elements, y over member) --------------------------------
-__device__ __forceinline__ double2 invert_l(const SpecDev &d, int k, int idx, double2 q0, double2 q1) {
-    const int sz = d.N * d.NK;
-    const double a0 = d.a[(2 * k) * sz + idx], a1 = d.a[(2 * k + 1) * sz + idx];
-    return make_double2(a0 * q0.x + a1 * q1.x, a0 * q0.y + a1 * q1.y);
-}
-
-__device__ __forceinline__ void pack_store_l(double2 *Z, int N, int j, int i, double2 Ah, double2 Bh, double s) {
-    Z[(size_t)j * N + i] = make_double2((Ah.x - Bh.y) * s, (Ah.y + Bh.x) * s);
-    if (i != 0 && 2 * i != N)
-        Z[(size_t)neg_mod_l(j, N) * N + (N - i)] = make_double2((Ah.x + Bh.y) * s, (Bh.x - Ah.y) * s);
+// natural-order store of the Hermitian extension of (Ah + i Bh) at (j, i) [and its mirror]; the caller has symmetrised
+// the self-conjugate columns
+__device__ __forceinline__ void pack_store_nat(double2 *Z, int N, int j, int i, double2 Ah, double2 Bh, double s) {
+    Z[(size_t)j * N + i] = pack_self(Ah, Bh, s);
+    if (i != 0 && 2 * i != N) Z[(size_t)neg_mod(j, N) * N + (N - i)] = pack_mirror(Ah, Bh, s);
 }
 
 // zbuf[b][k] <- spectrum of (u_k + i v_k) / N^2 for both layers; optional ph store
@@ -79,23 +77,19 @@ __global__ void k_l_build_uv(SpecDev d, const double2 *qh, double2 *zbuf, double
         const double2 q0 = qh0[idx], q1 = qh1[idx];
         const double kx = d.kk[i], ly = d.ll[j];
         const bool selfc = (i == 0 || 2 * i == N);
-        const int jm = neg_mod_l(j, N), idm = jm * NK + i;
+        const int jm = neg_mod(j, N), idm = jm * NK + i;
         double2 q0m, q1m;
         if (selfc) { q0m = qh0[idm]; q1m = qh1[idm]; }
         for (int k = 0; k < 2; ++k) {
-            const double2 ph = invert_l(d, k, idx, q0, q1);
+            const double2 ph = invert_layer(d, k, idx, q0, q1);
             if (ph_out) ph_out[(size_t)b * 2 * sz + k * sz + idx] = ph;
-            double2 uh = make_double2(ly * ph.y, -ly * ph.x);
-            double2 vh = make_double2(-kx * ph.y, kx * ph.x);
+            double2 uh = u_hat(ly, ph), vh = v_hat(kx, ph);
             if (selfc) {
-                const double2 pm = invert_l(d, k, idm, q0m, q1m);
-                const double lm = d.ll[jm];
-                const double2 um = make_double2(lm * pm.y, -lm * pm.x);
-                const double2 vm = make_double2(-kx * pm.y, kx * pm.x);
-                uh = make_double2(0.5 * (uh.x + um.x), 0.5 * (uh.y - um.y));
-                vh = make_double2(0.5 * (vh.x + vm.x), 0.5 * (vh.y - vm.y));
+                const double2 pm = invert_layer(d, k, idm, q0m, q1m);
+                uh = herm_mean(uh, u_hat(d.ll[jm], pm));
+                vh = herm_mean(vh, v_hat(kx, pm));
             }
-            pack_store_l(zbuf + ((size_t)b * ZF + k) * N * N, N, j, i, uh, vh, d.invN2);
+            pack_store_nat(zbuf + ((size_t)b * ZF + k) * N * N, N, j, i, uh, vh, d.invN2);
         }
     }
 }
@@ -108,12 +102,11 @@ __global__ void k_l_build_pair(SpecDev d, const double2 *src, double2 *zbuf) {
         const int j = idx / NK, i = idx - j * NK;
         double2 a = Ah[idx], bb = Bh[idx];
         if (i == 0 || 2 * i == N) {
-            const int idm = neg_mod_l(j, N) * NK + i;
-            const double2 am = Ah[idm], bm = Bh[idm];
-            a = make_double2(0.5 * (a.x + am.x), 0.5 * (a.y - am.y));
-            bb = make_double2(0.5 * (bb.x + bm.x), 0.5 * (bb.y - bm.y));
+            const int idm = neg_mod(j, N) * NK + i;
+            a = herm_mean(a, Ah[idm]);
+            bb = herm_mean(bb, Bh[idm]);
         }
-        pack_store_l(zbuf + (size_t)b * ZF * N * N, N, j, i, a, bb, d.invN2);
+        pack_store_nat(zbuf + (size_t)b * ZF * N * N, N, j, i, a, bb, d.invN2);
     }
 }
 
@@ -141,9 +134,9 @@ __global__ void k_l_unpack_pair(SpecDev d, const double2 *zbuf, double2 *dst, in
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < sz; idx += gridDim.x * blockDim.x) {
         const int j = idx / NK, i = idx - j * NK;
         const double2 a = Z[(size_t)j * N + i];
-        const double2 c = Z[(size_t)neg_mod_l(j, N) * N + neg_mod_l(i, N)];
-        double2 s0 = make_double2(0.5 * (a.x + c.x), 0.5 * (a.y - c.y));
-        double2 s1 = make_double2(0.5 * (a.y + c.y), -0.5 * (a.x - c.x));
+        const double2 c = Z[(size_t)neg_mod(j, N) * N + neg_mod(i, N)];
+        double2 s0, s1;
+        unpack_half(a, c, s0, s1);
         if (zero_mean && idx == 0) { s0 = make_double2(0., 0.); s1 = s0; }
         dst[(size_t)b * 2 * sz + idx] = s0;
         dst[(size_t)b * 2 * sz + sz + idx] = s1;
@@ -169,31 +162,22 @@ __global__ void k_l_tendency(SpecDev d, StepArgs a, const double2 *zbuf) {
     const double2 *qh0 = a.qh_in + (size_t)b * 2 * sz, *qh1 = qh0 + sz;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < sz; idx += gridDim.x * blockDim.x) {
         const int j = idx / NK, i = idx - j * NK;
-        const int jm = neg_mod_l(j, N), im = neg_mod_l(i, N);
+        const int jm = neg_mod(j, N), im = neg_mod(i, N);
         const double2 q0 = qh0[idx], q1 = qh1[idx];
         const double kx = d.kk[i], ly = d.ll[j];
         for (int k = 0; k < 2; ++k) {
             const double2 *Z = zbuf + ((size_t)b * ZF + k) * N * N;
             const double2 A = Z[(size_t)j * N + i], C = Z[(size_t)jm * N + im];
-            const double2 uqh = make_double2(0.5 * (A.x + C.x), 0.5 * (A.y - C.y));
-            const double2 vqh = make_double2(0.5 * (A.y + C.y), -0.5 * (A.x - C.x));
-            const double2 ph = invert_l(d, k, idx, q0, q1);
-            const double kq = kx * d.Qy[k];
-            double tx = (kx * uqh.y + ly * vqh.y + kq * ph.y);
-            double ty = -(kx * uqh.x + ly * vqh.x + kq * ph.x);
-            if (k == 1 && d.rek != 0.0) {
-                const double f = d.rek * d.wv2[idx];
-                tx += f * ph.x;
-                ty += f * ph.y;
-            }
+            double2 uqh, vqh;
+            unpack_half(A, C, uqh, vqh);
+            const double2 ph = invert_layer(d, k, idx, q0, q1);
+            double2 t = tendency_elem(k, kx, ly, d.Qy[k], d.rek, d.wv2 + idx, uqh, vqh, ph);
             const size_t o = (size_t)b * 2 * sz + k * sz + idx;
-            if (a.has_S) { const double2 s = a.dqh[o]; tx += s.x; ty += s.y; }
+            if (a.has_S) { const double2 s = a.dqh[o]; t.x += s.x; t.y += s.y; }
             const double2 p = a.dq_p[o], pp = a.dq_pp[o];
-            const double2 qk = k == 0 ? q0 : q1;
             const double f = d.filtr[idx];
-            a.dq_new[o] = make_double2(tx, ty);
-            a.qh_out[o] = make_double2(f * (qk.x + a.dt1 * tx + a.dt2 * p.x + a.dt3 * pp.x),
-                                       f * (qk.y + a.dt1 * ty + a.dt2 * p.y + a.dt3 * pp.y));
+            a.dq_new[o] = t;
+            a.qh_out[o] = ab3_filter(f, k == 0 ? q0 : q1, t, p, pp, a.dt1, a.dt2, a.dt3);
         }
     }
 }
@@ -213,6 +197,8 @@ __device__ __forceinline__ int pair_row(int p, int which, int N) {      // p in 
 // MODE 1: lines = rows of the pair (A,B) = (src[b][0], src[b][1]) -> zbuf[b][2]
 // MODE 3: MODE 0 and MODE 1 of the same qh in one pass (three lines per row): the unparameterized step derives
 //         q = irfft2(qh) beside (u, v) instead of keeping a real-space copy of q between steps
+// MODE 4: MODE 3 with the pair (p_1 + i p_2) as a fourth line, DZF fields per member in zbuf and psi always stored: the
+//         first kernel of the fused diagnostics increment (below)
 // NN > 0: grid size, pairs per workgroup (PPWT) and thread count (NT) are compile-time constants: the index arithmetic
 // folds, the FFT plan is unrolled and — above all — the staging loops unroll, so that all of a thread's global loads
 // are in flight together (with run-time trip counts each thread waits for one 16-byte load at a time: 60-70 % of the
@@ -220,8 +206,10 @@ __device__ __forceinline__ int pair_row(int p, int which, int N) {      // p in 
 template <int MODE, int NN = 0, int PPWT = 0, int NT = 0>
 __global__ __launch_bounds__(NT > 0 ? NT : 1024) void k_l_rows_build_inv(SpecDev d, const double2 *src, double2 *zbuf,
                                                                          double2 *ph_out, int PPW_, int ZP) {
-    constexpr int NF = MODE == 0 ? 2 : (MODE == 3 ? 3 : 1);
+    constexpr int NF = MODE == 0 ? 2 : (MODE == 3 ? 3 : (MODE == 4 ? 4 : 1));
+    constexpr int MF = MODE == 4 ? DZF : ZF;            // work fields per member of the destination
     constexpr bool CT = NN > 0;
+    static_assert(MODE != 4 || CT, "the diagnostics increment has compile-time shapes only");
     double2 *L = reinterpret_cast<double2 *>(lg_smem);
     const int N = CT ? NN : d.N, NK = N / 2 + 1, LD = N + 1, sz = N * NK;
     const int PPW = CT ? PPWT : PPW_;
@@ -237,41 +225,44 @@ __global__ __launch_bounds__(NT > 0 ? NT : 1024) void k_l_rows_build_inv(SpecDev
 #pragma unroll
     for (int t = threadIdx.x; t < PPW * 2 * NK; t += nthr) {
         const int i = t % NK, r = t / NK;                 // r = local row: pair r>>1, member r&1
-        const int j = pair_row(p0 + (r >> 1), r & 1, N), jm = neg_mod_l(j, N);
+        const int j = pair_row(p0 + (r >> 1), r & 1, N), jm = neg_mod(j, N);
         const int rm = (p0 + (r >> 1)) == 0 ? r : (r ^ 1);   // local row holding row -j
         const int idx = j * NK + i, idm = jm * NK + i;
         const bool selfc = (i == 0 || 2 * i == N);
         const double2 q0 = s0[idx], q1 = s1[idx];
         double2 q0m = q0, q1m = q1;
         if (selfc) { q0m = s0[idm]; q1m = s1[idm]; }
-        if constexpr (MODE == 0 || MODE == 3) {
+        double2 phk[2], phm[2];                          // psi of the element and of its mirror row (MODE 4)
+        if constexpr (MODE != 1) {
             const double kx = d.kk[i], ly = d.ll[j], lm = d.ll[jm];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                const double2 ph = invert_l(d, k, idx, q0, q1);
-                if (ph_out) ph_out[(size_t)b * 2 * sz + k * sz + idx] = ph;
-                double2 uh = make_double2(ly * ph.y, -ly * ph.x);
-                double2 vh = make_double2(-kx * ph.y, kx * ph.x);
+                const double2 ph = invert_layer(d, k, idx, q0, q1);
+                if constexpr (MODE == 4) { phk[k] = ph; phm[k] = ph; }
+                if (MODE == 4 || ph_out) ph_out[(size_t)b * 2 * sz + k * sz + idx] = ph;
+                double2 uh = u_hat(ly, ph), vh = v_hat(kx, ph);
                 if (selfc) {
-                    const double2 pm = invert_l(d, k, idm, q0m, q1m);
-                    const double2 um = make_double2(lm * pm.y, -lm * pm.x);
-                    const double2 vm = make_double2(-kx * pm.y, kx * pm.x);
-                    uh = make_double2(0.5 * (uh.x + um.x), 0.5 * (uh.y - um.y));
-                    vh = make_double2(0.5 * (vh.x + vm.x), 0.5 * (vh.y - vm.y));
+                    const double2 pm = invert_layer(d, k, idm, q0m, q1m);
+                    if constexpr (MODE == 4) phm[k] = pm;
+                    uh = herm_mean(uh, u_hat(lm, pm));
+                    vh = herm_mean(vh, v_hat(kx, pm));
                 }
-                L[(r * NF + k) * LD + pos[i]] = make_double2((uh.x - vh.y) * d.invN2, (uh.y + vh.x) * d.invN2);
-                if (!selfc) L[(rm * NF + k) * LD + pos[N - i]] = make_double2((uh.x + vh.y) * d.invN2, (vh.x - uh.y) * d.invN2);
+                L[(r * NF + k) * LD + pos[i]] = pack_self(uh, vh, d.invN2);
+                if (!selfc) L[(rm * NF + k) * LD + pos[N - i]] = pack_mirror(uh, vh, d.invN2);
             }
         }
-        if constexpr (MODE == 1 || MODE == 3) {
-            constexpr int KQ = MODE == 3 ? 2 : 0;
+        if constexpr (MODE != 0) {                       // the pair (q_1 + i q_2)
             double2 a = q0, bb = q1;
-            if (selfc) {
-                a = make_double2(0.5 * (a.x + q0m.x), 0.5 * (a.y - q0m.y));
-                bb = make_double2(0.5 * (bb.x + q1m.x), 0.5 * (bb.y - q1m.y));
-            }
-            L[(r * NF + KQ) * LD + pos[i]] = make_double2((a.x - bb.y) * d.invN2, (a.y + bb.x) * d.invN2);
-            if (!selfc) L[(rm * NF + KQ) * LD + pos[N - i]] = make_double2((a.x + bb.y) * d.invN2, (bb.x - a.y) * d.invN2);
+            if (selfc) { a = herm_mean(a, q0m); bb = herm_mean(bb, q1m); }
+            constexpr int KQ = MODE == 1 ? 0 : 2;
+            L[(r * NF + KQ) * LD + pos[i]] = pack_self(a, bb, d.invN2);
+            if (!selfc) L[(rm * NF + KQ) * LD + pos[N - i]] = pack_mirror(a, bb, d.invN2);
+        }
+        if constexpr (MODE == 4) {                       // the pair (p_1 + i p_2)
+            double2 a = phk[0], bb = phk[1];
+            if (selfc) { a = herm_mean(a, phm[0]); bb = herm_mean(bb, phm[1]); }
+            L[(r * NF + 3) * LD + pos[i]] = pack_self(a, bb, d.invN2);
+            if (!selfc) L[(rm * NF + 3) * LD + pos[N - i]] = pack_mirror(a, bb, d.invN2);
         }
     }
     __syncthreads();
@@ -282,7 +273,7 @@ __global__ __launch_bounds__(NT > 0 ? NT : 1024) void k_l_rows_build_inv(SpecDev
         const int e = t % N, line = t / N;
         const int r = line / NF, k = line - r * NF;
         const int j = pair_row(p0 + (r >> 1), r & 1, N);
-        zbuf[((size_t)b * ZF + (MODE == 1 ? 2 : k)) * ZP * N + (size_t)j * ZP + e] = L[line * LD + e];
+        zbuf[((size_t)b * MF + (MODE == 1 ? 2 : k)) * ZP * N + (size_t)j * ZP + e] = L[line * LD + e];
     }
 }
 
@@ -465,42 +456,30 @@ __global__ __launch_bounds__(NT > 0 ? NT : 1024) void k_l_rows_fwd_tend(SpecDev 
 #pragma unroll
     for (int t = threadIdx.x; t < PPW * 2 * NK; t += nthr) {
         const int i = t % NK, r = t / NK;
-        const int j = pair_row(p0 + (r >> 1), r & 1, N), jm = neg_mod_l(j, N), im = neg_mod_l(i, N);
+        const int j = pair_row(p0 + (r >> 1), r & 1, N), jm = neg_mod(j, N), im = neg_mod(i, N);
         const int rm = (p0 + (r >> 1)) == 0 ? r : (r ^ 1);
         const int idx = j * NK + i;
         const double2 q0 = qh0[idx], q1 = qh1[idx];
         const double kx = d.kk[i], ly = d.ll[j];
         double2 s0 = make_double2(0., 0.), s1 = s0;
         if (a.has_S) {
-            const double2 A = ZS[(size_t)j * ZP + i], C = ZS[(size_t)jm * ZP + im];
-            s0 = make_double2(0.5 * (A.x + C.x), 0.5 * (A.y - C.y));
-            s1 = make_double2(0.5 * (A.y + C.y), -0.5 * (A.x - C.x));
+            unpack_half(ZS[(size_t)j * ZP + i], ZS[(size_t)jm * ZP + im], s0, s1);
             if (a.demean && idx == 0) { s0 = make_double2(0., 0.); s1 = s0; }
             if (a.diag) { a.dqh[(size_t)b * 2 * sz + idx] = s0; a.dqh[(size_t)b * 2 * sz + sz + idx] = s1; }
         }
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const double2 A = L[(r * 2 + k) * LD + pos[i]], C = L[(rm * 2 + k) * LD + pos[im]];
-            const double2 uqh = make_double2(0.5 * (A.x + C.x), 0.5 * (A.y - C.y));
-            const double2 vqh = make_double2(0.5 * (A.y + C.y), -0.5 * (A.x - C.x));
-            const double2 ph = invert_l(d, k, idx, q0, q1);
-            const double kq = kx * d.Qy[k];
-            double tx = (kx * uqh.y + ly * vqh.y + kq * ph.y);
-            double ty = -(kx * uqh.x + ly * vqh.x + kq * ph.x);
-            if (k == 1 && d.rek != 0.0) {
-                const double f = d.rek * d.wv2[idx];
-                tx += f * ph.x;
-                ty += f * ph.y;
-            }
+            double2 uqh, vqh;
+            unpack_half(L[(r * 2 + k) * LD + pos[i]], L[(rm * 2 + k) * LD + pos[im]], uqh, vqh);
+            const double2 ph = invert_layer(d, k, idx, q0, q1);
+            double2 tn = tendency_elem(k, kx, ly, d.Qy[k], d.rek, d.wv2 + idx, uqh, vqh, ph);
             const double2 s = k == 0 ? s0 : s1;
-            tx += s.x; ty += s.y;
+            tn.x += s.x; tn.y += s.y;
             const size_t o = (size_t)b * 2 * sz + k * sz + idx;
             const double2 p = a.dq_p[o], pp = a.dq_pp[o];
-            const double2 qk = k == 0 ? q0 : q1;
             const double f = d.filtr[idx];
-            a.dq_new[o] = make_double2(tx, ty);
-            a.qh_out[o] = make_double2(f * (qk.x + a.dt1 * tx + a.dt2 * p.x + a.dt3 * pp.x),
-                                       f * (qk.y + a.dt1 * ty + a.dt2 * p.y + a.dt3 * pp.y));
+            a.dq_new[o] = tn;
+            a.qh_out[o] = ab3_filter(f, k == 0 ? q0 : q1, tn, p, pp, a.dt1, a.dt2, a.dt3);
         }
     }
 }
@@ -520,72 +499,6 @@ __global__ __launch_bounds__(NT > 0 ? NT : 1024) void k_l_rows_fwd_tend(SpecDev 
 // del_1 (u_1 d) + del_2 (u_2 d): four forward transforms carry the five product pairs of the composed form (rounding
 // differs at 1e-14 relative: cancellation by at most 1 + F / K_min^2 ~ 90).
 // ================================================================================================
-constexpr int DZF = 4;       // complex work fields per member of the fused increment
-
-template <int NN, int PPWT, int NT>
-__global__ __launch_bounds__(NT) void k_l_rows_diag_inv(SpecDev d, const double2 *src, double2 *dz, double2 *ph_out, int ZP) {
-    constexpr int NF = DZF, N = NN, NK = N / 2 + 1, LD = N + 1, sz = N * NK, PPW = PPWT, nlines = PPW * 2 * NF;
-    double2 *L = reinterpret_cast<double2 *>(lg_smem);
-    int *pos = reinterpret_cast<int *>(L + (size_t)nlines * LD);
-    double2 *twl = reinterpret_cast<double2 *>(pos + ((N + 3) & ~3));
-    for (int t = threadIdx.x; t < N; t += NT) { pos[t] = d.pos[t]; twl[t] = d.tw[t]; }
-    constexpr int groups = (N / 2) / PPW;
-    const int b = blockIdx.x / groups, p0 = (blockIdx.x - b * groups) * PPW;
-    const double2 *s0 = src + (size_t)b * 2 * sz, *s1 = s0 + sz;
-    __syncthreads();
-#pragma unroll
-    for (int t = threadIdx.x; t < PPW * 2 * NK; t += NT) {
-        const int i = t % NK, r = t / NK;
-        const int j = pair_row(p0 + (r >> 1), r & 1, N), jm = neg_mod_l(j, N);
-        const int rm = (p0 + (r >> 1)) == 0 ? r : (r ^ 1);
-        const int idx = j * NK + i, idm = jm * NK + i;
-        const bool selfc = (i == 0 || 2 * i == N);
-        const double2 q0 = s0[idx], q1 = s1[idx];
-        double2 q0m = q0, q1m = q1;
-        if (selfc) { q0m = s0[idm]; q1m = s1[idm]; }
-        const double kx = d.kk[i], ly = d.ll[j], lm = d.ll[jm];
-        double2 phk[2], phm[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const double2 ph = invert_l(d, k, idx, q0, q1);
-            phk[k] = ph; phm[k] = ph;
-            ph_out[(size_t)b * 2 * sz + k * sz + idx] = ph;
-            double2 uh = make_double2(ly * ph.y, -ly * ph.x);
-            double2 vh = make_double2(-kx * ph.y, kx * ph.x);
-            if (selfc) {
-                const double2 pm = invert_l(d, k, idm, q0m, q1m);
-                phm[k] = pm;
-                const double2 um = make_double2(lm * pm.y, -lm * pm.x);
-                const double2 vm = make_double2(-kx * pm.y, kx * pm.x);
-                uh = make_double2(0.5 * (uh.x + um.x), 0.5 * (uh.y - um.y));
-                vh = make_double2(0.5 * (vh.x + vm.x), 0.5 * (vh.y - vm.y));
-            }
-            L[(r * NF + k) * LD + pos[i]] = make_double2((uh.x - vh.y) * d.invN2, (uh.y + vh.x) * d.invN2);
-            if (!selfc) L[(rm * NF + k) * LD + pos[N - i]] = make_double2((uh.x + vh.y) * d.invN2, (vh.x - uh.y) * d.invN2);
-        }
-#pragma unroll
-        for (int f = 2; f < 4; ++f) {            // the pairs (q_1 + i q_2) and (p_1 + i p_2)
-            double2 a = f == 2 ? q0 : phk[0], bb = f == 2 ? q1 : phk[1];
-            if (selfc) {
-                const double2 am = f == 2 ? q0m : phm[0], bm = f == 2 ? q1m : phm[1];
-                a = make_double2(0.5 * (a.x + am.x), 0.5 * (a.y - am.y));
-                bb = make_double2(0.5 * (bb.x + bm.x), 0.5 * (bb.y - bm.y));
-            }
-            L[(r * NF + f) * LD + pos[i]] = make_double2((a.x - bb.y) * d.invN2, (a.y + bb.x) * d.invN2);
-            if (!selfc) L[(rm * NF + f) * LD + pos[N - i]] = make_double2((a.x + bb.y) * d.invN2, (bb.x - a.y) * d.invN2);
-        }
-    }
-    __syncthreads();
-    fft_lines_inv_t<NN, NN>(L, nlines, LD, 1, twl);
-#pragma unroll
-    for (int t = threadIdx.x; t < nlines * N; t += NT) {
-        const int e = t % N, line = t / N;
-        const int r = line / NF, f = line - r * NF;
-        const int j = pair_row(p0 + (r >> 1), r & 1, N);
-        dz[((size_t)b * DZF + f) * ZP * N + (size_t)j * ZP + e] = L[line * LD + e];
-    }
-}
-
 template <int NN, int CPBT, int NT>
 __global__ __launch_bounds__(NT) void k_l_cols_diag(SpecDev d, double2 *dz, int ZP) {
     constexpr int N = NN, LD = N + 1, CPB = CPBT;
@@ -650,16 +563,12 @@ __global__ __launch_bounds__(NT) void k_l_rows_diag_acc(SpecDev d, DiagConst c, 
 #pragma unroll
     for (int t = threadIdx.x; t < PPW * 2 * NK; t += NT) {
         const int i = t % NK, r = t / NK;
-        const int j = pair_row(p0 + (r >> 1), r & 1, N), im = neg_mod_l(i, N);
+        const int j = pair_row(p0 + (r >> 1), r & 1, N), im = neg_mod(i, N);
         const int rm = (p0 + (r >> 1)) == 0 ? r : (r ^ 1);
         const int idx = j * NK + i;
         double2 A[NF], Bv[NF];
 #pragma unroll
-        for (int f = 0; f < NF; ++f) {
-            const double2 X = L[(r * NF + f) * LD + pos[i]], C = L[(rm * NF + f) * LD + pos[im]];
-            A[f] = make_double2(0.5 * (X.x + C.x), 0.5 * (X.y - C.y));
-            Bv[f] = make_double2(0.5 * (X.y + C.y), -0.5 * (X.x - C.x));
-        }
+        for (int f = 0; f < NF; ++f) unpack_half(L[(r * NF + f) * LD + pos[i]], L[(rm * NF + f) * LD + pos[im]], A[f], Bv[f]);
         // (ub d, vb d) = del_1 (u_1 d) + del_2 (u_2 d);  (u_1 xi_1) = (u_1 q_1) + F_1 (u_1 d);  (u_2 xi_2) = (u_2 q_2) - F_2 (u_2 d)
         const double2 A3 = make_double2(c.del1 * A[2].x + c.del2 * A[3].x, c.del1 * A[2].y + c.del2 * A[3].y);
         const double2 B3 = make_double2(c.del1 * Bv[2].x + c.del2 * Bv[3].x, c.del1 * Bv[2].y + c.del2 * Bv[3].y);
@@ -708,33 +617,110 @@ int large_zpad() {
     return pad < 0 ? 0 : pad;
 }
 
+// Tile shapes of the compile-time-N kernels, from a sweep at 256 x 256, 64 members (bench_tools/large_sweep.sh over
+// instances compiled for the purpose).  Step: mirror pairs of rows per workgroup and threads of k_l_rows_build_inv<3> /
+// columns and threads of k_l_cols3 / pairs and threads of k_l_rows_fwd_tend.  Diagnostics increment: pairs and threads of
+// the two row kernels / columns and threads of k_l_cols_diag.  A grid size is specialised exactly where it has an entry.
+template <int NN> struct LargeTiles { static constexpr bool step = false, diag = false; };
+template <> struct LargeTiles<128> {
+    static constexpr bool step = true, diag = true;
+    static constexpr int P1 = 2, T1 = 512, C2 = 8, T2 = 1024, P3 = 4, T3 = 512;
+    static constexpr int DP = 4, DT1 = 512, DC = 8, DT2 = 1024;
+};
+template <> struct LargeTiles<256> {
+    static constexpr bool step = true, diag = true;
+    static constexpr int P1 = 2, T1 = 512, C2 = 8, T2 = 1024, P3 = 4, T3 = 512;
+    static constexpr int DP = 2, DT1 = 512, DC = 8, DT2 = 1024;
+};
+// (no step at 512: lines_per_block(512) is 2, and large_step hands every grid with fewer than four lines per workgroup
+// to large_step_unfused)
+template <> struct LargeTiles<512> {
+    static constexpr bool step = false, diag = true;
+    static constexpr int DP = 1, DT1 = 512, DC = 4, DT2 = 1024;
+};
+
+constexpr int LARGE_LDS_CAP = 160 * 1024 - 512;      // dynamic LDS any large-grid kernel may ask for
+
+// L_HAS_*: 1 if the grid size has that specialisation (no launch); L_CAPS: raise the dynamic-LDS cap of its kernels
+enum LargeOp { L_HAS_STEP, L_HAS_DIAG, L_CAPS, L_STEP, L_DIAG };
+struct LargeCall {           // arguments of the launches: L_STEP reads a, L_DIAG the rest
+    const StepArgs *a = nullptr;
+    const DiagConst *c = nullptr;
+    const double2 *qh = nullptr, *Sh = nullptr, *dq_p = nullptr, *dq_pp = nullptr;
+    const DiagAcc *acc = nullptr;
+};
+
+// The specialised kernels of grid size NN are instantiated from LargeTiles<NN> here and nowhere else, so the shapes
+// whose cap is raised are the shapes that are launched (a launch with more dynamic LDS than the cap fails).
+template <int NN>
+static int large_tiles_run(LargeOp op, qgx_model *m, const LargeCall &x, hipStream_t st) {
+    using T = LargeTiles<NN>;
+    if (op == L_HAS_STEP) return T::step;
+    if (op == L_HAS_DIAG) return T::diag;
+    if ((op == L_STEP && !T::step) || (op == L_DIAG && !T::diag)) return QGX_ERR_INVALID;
+    const int zp = NN + large_zpad();
+    if constexpr (T::step) {
+        const auto k1 = k_l_rows_build_inv<3, NN, T::P1, T::T1>;
+        const auto k2 = k_l_cols3<NN, T::C2, T::T2>;
+        const auto k3 = k_l_rows_fwd_tend<NN, T::P3, T::T3>;
+        if (op == L_CAPS)
+            for (const void *f : {(const void *)k1, (const void *)k2, (const void *)k3})
+                QGX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LARGE_LDS_CAP));
+        if (op == L_STEP) {
+            const SpecDev &d = m->d;
+            const StepArgs &a = *x.a;
+            const int B = d.B;
+            hipLaunchKernelGGL(k1, dim3(B * (NN / 2 / T::P1)), dim3(T::T1), lines_lds(NN, 6 * T::P1), st, d, a.qh_in, m->zbuf,
+                               a.diag ? a.ph : (double2 *)nullptr, T::P1, zp);
+            hipLaunchKernelGGL(k2, dim3(B * (NN / T::C2)), dim3(T::T2), lines_lds(NN, 3 * T::C2), st, d, m->zbuf,
+                               a.diag ? a.u : (double *)nullptr, a.diag ? a.v : (double *)nullptr, T::C2, zp);
+            hipLaunchKernelGGL(k3, dim3(B * (NN / 2 / T::P3)), dim3(T::T3), lines_lds(NN, 4 * T::P3), st, d, a,
+                               (const double2 *)m->zbuf, T::P3, zp);
+        }
+    }
+    if constexpr (T::diag) {
+        const auto k1 = k_l_rows_build_inv<4, NN, T::DP, T::DT1>;
+        const auto k2 = k_l_cols_diag<NN, T::DC, T::DT2>;
+        const auto k3 = k_l_rows_diag_acc<NN, T::DP, T::DT1>;
+        if (op == L_CAPS)
+            for (const void *f : {(const void *)k1, (const void *)k2, (const void *)k3})
+                QGX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LARGE_LDS_CAP));
+        if (op == L_DIAG) {
+            const SpecDev &d = m->d;
+            const int B = d.B;
+            hipLaunchKernelGGL(k1, dim3(B * (NN / 2 / T::DP)), dim3(T::DT1), lines_lds(NN, 2 * DZF * T::DP), st, d, x.qh, m->dg_z,
+                               m->ph, T::DP, zp);
+            hipLaunchKernelGGL(k2, dim3(B * (NN / T::DC)), dim3(T::DT2), lines_lds(NN, DZF * T::DC), st, d, m->dg_z, zp);
+            hipLaunchKernelGGL(k3, dim3(B * (NN / 2 / T::DP)), dim3(T::DT1), lines_lds(NN, 2 * DZF * T::DP), st, d, *x.c,
+                               (const double2 *)m->dg_z, x.qh, (const double2 *)m->ph, x.Sh, x.dq_p, x.dq_pp, *x.acc, zp);
+        }
+    }
+    QGX_HIP(hipGetLastError());
+    return QGX_OK;
+}
+
+// the one place where a grid size meets its specialisation
+static int large_tiles(int N, LargeOp op, qgx_model *m = nullptr, const LargeCall &x = LargeCall(), hipStream_t st = nullptr) {
+    switch (N) {
+    case 128: return large_tiles_run<128>(op, m, x, st);
+    case 256: return large_tiles_run<256>(op, m, x, st);
+    case 512: return large_tiles_run<512>(op, m, x, st);
+    default: return op <= L_CAPS ? 0 : QGX_ERR_INVALID;      // no specialisation: nothing to have, nothing to raise
+    }
+}
+
 int large_prepare(const SpecDev &d) {
-    // the attribute is a per-kernel cap shared by every model of the process (models of different N coexist:
-    // hires run + coarse-grained forcing models), so it is set once to the most any grid may ask for
-    (void)d;
-    const int cap = 160 * 1024 - 512;
+    // the attribute is a per-kernel cap shared by every model of the process (models of different N coexist: hires run +
+    // coarse-grained forcing models), so it is always set to the most any grid may ask for: on the run-time-N kernels,
+    // and on the kernels specialised for this model's grid
     const void *kernels[] = {(const void *)k_lines_fft<true, false>, (const void *)k_lines_fft<true, true>,
                              (const void *)k_lines_fft<false, false>, (const void *)k_lines_fft<false, true>,
                              (const void *)k_l_rows_build_inv<0>, (const void *)k_l_rows_build_inv<1>,
                              (const void *)k_l_rows_build_inv<3>, (const void *)k_l_rows_S, (const void *)k_l_cols<0>,
                              (const void *)k_l_cols<1>, (const void *)k_l_cols<2>, (const void *)k_l_cols<3>, (const void *)k_l_cols3<>,
-                             (const void *)k_l_rows_fwd_tend<>,
-#define QGX_L3(NN, P1, T1, C2, T2, P3, T3) (const void *)k_l_rows_build_inv<3, NN, P1, T1>, \
-                   (const void *)k_l_cols3<NN, C2, T2>, (const void *)k_l_rows_fwd_tend<NN, P3, T3>
-                             QGX_L3(128, 2, 512, 8, 1024, 4, 512), QGX_L3(256, 2, 512, 8, 1024, 4, 512),
-                             QGX_L3(512, 1, 256, 4, 512, 2, 256),
-#ifdef QGX_L3_SWEEP
-                             (const void *)k_l_cols3<256, 8, 512>, (const void *)k_l_cols3<256, 8, 1024>, (const void *)k_l_cols3<256, 4, 512>,
-                             (const void *)k_l_cols3<256, 4, 128>, (const void *)k_l_cols3<256, 2, 128>, (const void *)k_l_cols3<256, 2, 256>,
-                             (const void *)k_l_rows_build_inv<3, 256, 2, 512>, (const void *)k_l_rows_build_inv<3, 256, 2, 256>,
-                             (const void *)k_l_rows_build_inv<3, 256, 1, 128>, (const void *)k_l_rows_fwd_tend<256, 4, 512>,
-                             (const void *)k_l_rows_fwd_tend<256, 4, 256>, (const void *)k_l_rows_fwd_tend<256, 2, 128>,
-                             (const void *)k_l_rows_fwd_tend<256, 1, 128>, (const void *)k_l_rows_fwd_tend<256, 1, 256>,
-#endif
-                             };
-#undef QGX_L3
-    for (const void *f : kernels) QGX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-    return QGX_OK;
+                             (const void *)k_l_rows_fwd_tend<>};
+    for (const void *f : kernels) QGX_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LARGE_LDS_CAP));
+    return large_tiles(d.N, L_CAPS);
 }
 
 // 2-D FFT of the work fields [k0, k0+nfpm) of every member
@@ -873,52 +859,25 @@ int large_step(qgx_model *m, const StepArgs &a, hipStream_t st) {
     const int c3 = cols3_cpb(N), ppw = rows3_ppw(N);
     const int zp = N + large_zpad();
     if (!a.has_S && !eager && c3 > 0) {
-        const size_t lds1 = lines_lds(N, 6 * ppw), lds2 = lines_lds(N, 3 * c3);
-        const bool generic = !m->opts.large_specialised;      // run-time-N kernels
-        double2 *const ph_o = a.diag ? a.ph : (double2 *)nullptr;
-        double *const u_o = a.diag ? a.u : (double *)nullptr, *const v_o = a.diag ? a.v : (double *)nullptr;
-        // compile-time specialisations; tiles (mirror pairs of rows / columns / pairs per workgroup) and thread counts
-        // from a sweep at 256 x 256, 64 members (bench_tools/large_sweep.sh with a -DQGX_L3_SWEEP build)
-#define QGX_L3(NN, P1, T1, C2, T2, P3, T3)                                                                             \
-    {                                                                                                                 \
-        hipLaunchKernelGGL((k_l_rows_build_inv<3, NN, P1, T1>), dim3(B * (NN / 2 / P1)), dim3(T1), lines_lds(NN, 6 * P1), \
-                           st, d, a.qh_in, m->zbuf, ph_o, P1, zp);                                                    \
-        hipLaunchKernelGGL((k_l_cols3<NN, C2, T2>), dim3(B * (NN / C2)), dim3(T2), lines_lds(NN, 3 * C2), st, d, m->zbuf, \
-                           u_o, v_o, C2, zp);                                                                         \
-        hipLaunchKernelGGL((k_l_rows_fwd_tend<NN, P3, T3>), dim3(B * (NN / 2 / P3)), dim3(T3), lines_lds(NN, 4 * P3), st, \
-                           d, a, (const double2 *)m->zbuf, P3, zp);                                                   \
-    }
-#ifdef QGX_L3_SWEEP      // tuning build: tile / thread variants of the 256 x 256 kernels, picked by environment variables
-        static const int v1 = tune_env("QGX_V1", 0), v2 = tune_env("QGX_V2", 0), v3 = tune_env("QGX_V3", 0);
-        if (!generic && N == 256 && (v1 || v2 || v3)) {
-#define QGX_K1(P, T) hipLaunchKernelGGL((k_l_rows_build_inv<3, 256, P, T>), dim3(B * (128 / P)), dim3(T), lines_lds(256, 6 * P), st, d, a.qh_in, m->zbuf, ph_o, P, zp)
-#define QGX_K2(C, T) hipLaunchKernelGGL((k_l_cols3<256, C, T>), dim3(B * (256 / C)), dim3(T), lines_lds(256, 3 * C), st, d, m->zbuf, u_o, v_o, C, zp)
-#define QGX_K3(P, T) hipLaunchKernelGGL((k_l_rows_fwd_tend<256, P, T>), dim3(B * (128 / P)), dim3(T), lines_lds(256, 4 * P), st, d, a, (const double2 *)m->zbuf, P, zp)
-            if (v1 == 1) QGX_K1(2, 512); else if (v1 == 2) QGX_K1(2, 256); else if (v1 == 3) QGX_K1(1, 128); else QGX_K1(1, 256);
-            if (v2 == 1) QGX_K2(8, 512); else if (v2 == 2) QGX_K2(8, 1024); else if (v2 == 3) QGX_K2(4, 512); else if (v2 == 4) QGX_K2(4, 128);
-            else if (v2 == 5) QGX_K2(2, 128); else if (v2 == 6) QGX_K2(2, 256); else QGX_K2(4, 256);
-            if (v3 == 1) QGX_K3(4, 512); else if (v3 == 2) QGX_K3(4, 256); else if (v3 == 3) QGX_K3(2, 128); else if (v3 == 4) QGX_K3(1, 128);
-            else if (v3 == 5) QGX_K3(1, 256); else QGX_K3(2, 256);
-        } else
-#endif
-        if (!generic && N == 256) QGX_L3(256, 2, 512, 8, 1024, 4, 512)
-        else if (!generic && N == 128) QGX_L3(128, 2, 512, 8, 1024, 4, 512)
-        // (512: not reached by the product library — lines_per_block(512) is 2, so the test above hands every 512 x 512 step
-        // to large_step_unfused; only the A/B library with QGX_LARGE_LPB=4 in the environment arrives here.  DESIGN 3.1)
-        else if (!generic && N == 512) QGX_L3(512, 1, 256, 4, 512, 2, 256)
-        else {
+        if (m->opts.large_specialised && large_tiles(N, L_HAS_STEP)) {     // compile-time-N kernels (LargeTiles)
+            LargeCall x;
+            x.a = &a;
+            int rc = large_tiles(N, L_STEP, m, x, st);
+            if (rc) return rc;
+        } else {                                                            // run-time-N kernels
             static const int t1 = tune_env("QGX_LARGE_T1", 256);   // tuning aids (A/B library): threads
             static const int t2 = tune_env("QGX_LARGE_T2", 256);
             static const int t3 = tune_env("QGX_LARGE_T3", 256);
             static const int p4 = tune_env("QGX_LARGE_P4", 0);     // row pairs of the tendency kernel
             const int ppw4 = p4 > 0 && (N / 2) % p4 == 0 ? p4 : lpb / 4;
-            hipLaunchKernelGGL(k_l_rows_build_inv<3>, dim3(B * ((N / 2) / ppw)), dim3(t1), lds1, st, d, a.qh_in, m->zbuf,
-                               ph_o, ppw, zp);
-            hipLaunchKernelGGL(k_l_cols3<>, dim3(B * (N / c3)), dim3(t2), lds2, st, d, m->zbuf, u_o, v_o, c3, zp);
+            double2 *const ph_o = a.diag ? a.ph : (double2 *)nullptr;
+            double *const u_o = a.diag ? a.u : (double *)nullptr, *const v_o = a.diag ? a.v : (double *)nullptr;
+            hipLaunchKernelGGL(k_l_rows_build_inv<3>, dim3(B * ((N / 2) / ppw)), dim3(t1), lines_lds(N, 6 * ppw), st, d, a.qh_in,
+                               m->zbuf, ph_o, ppw, zp);
+            hipLaunchKernelGGL(k_l_cols3<>, dim3(B * (N / c3)), dim3(t2), lines_lds(N, 3 * c3), st, d, m->zbuf, u_o, v_o, c3, zp);
             hipLaunchKernelGGL(k_l_rows_fwd_tend<>, dim3(B * ((N / 2) / ppw4)), dim3(t3), lines_lds(N, 4 * ppw4), st, d, a,
                                (const double2 *)m->zbuf, ppw4, zp);
         }
-#undef QGX_L3
         QGX_HIP(hipGetLastError());
         m->q_stale = true;
         return QGX_OK;
@@ -949,36 +908,15 @@ int large_step(qgx_model *m, const StepArgs &a, hipStream_t st) {
 
 
 // the three launches of one diagnostics increment (kernels above); false: no specialisation for this grid size
-bool large_diag_fused_ok(const qgx_model *m) { return m->opts.large_fused && (m->N == 128 || m->N == 256 || m->N == 512); }
+bool large_diag_fused_ok(const qgx_model *m) { return m->opts.large_fused && large_tiles(m->N, L_HAS_DIAG); }
 
 int large_diag_fused(qgx_model *m, const DiagConst &c, const double2 *qh, const double2 *Sh, const double2 *dq_p, const double2 *dq_pp,
                      const DiagAcc &acc, hipStream_t st) {
     const SpecDev &d = m->d;
-    const int B = d.B, N = d.N, ZP = N + large_zpad();
-    if (!m->dg_z) {
-        QGX_HIP(hipMalloc((void **)&m->dg_z, (size_t)B * DZF * ZP * N * sizeof(double2)));
-        const int cap = 160 * 1024 - 512;
-#define QGX_DG(NN, P, T1, C, T2)                                                                                               \
-        QGX_HIP(hipFuncSetAttribute((const void *)k_l_rows_diag_inv<NN, P, T1>, hipFuncAttributeMaxDynamicSharedMemorySize, cap)); \
-        QGX_HIP(hipFuncSetAttribute((const void *)k_l_cols_diag<NN, C, T2>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));     \
-        QGX_HIP(hipFuncSetAttribute((const void *)k_l_rows_diag_acc<NN, P, T1>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-        QGX_DG(128, 4, 512, 8, 1024) QGX_DG(256, 2, 512, 8, 1024) QGX_DG(512, 1, 512, 4, 1024)
-#undef QGX_DG
-    }
-#define QGX_DG(NN, P, T1, C, T2)                                                                                               \
-    {                                                                                                                          \
-        hipLaunchKernelGGL((k_l_rows_diag_inv<NN, P, T1>), dim3(B * (NN / 2 / P)), dim3(T1), lines_lds(NN, 2 * DZF * P), st, d, qh,  \
-                           m->dg_z, m->ph, ZP);                                                                                \
-        hipLaunchKernelGGL((k_l_cols_diag<NN, C, T2>), dim3(B * (NN / C)), dim3(T2), lines_lds(NN, DZF * C), st, d, m->dg_z, ZP); \
-        hipLaunchKernelGGL((k_l_rows_diag_acc<NN, P, T1>), dim3(B * (NN / 2 / P)), dim3(T1), lines_lds(NN, 2 * DZF * P), st, d, c, \
-                           (const double2 *)m->dg_z, qh, (const double2 *)m->ph, Sh, dq_p, dq_pp, acc, ZP);                    \
-    }
-    if (N == 128) QGX_DG(128, 4, 512, 8, 1024)
-    else if (N == 256) QGX_DG(256, 2, 512, 8, 1024)
-    else QGX_DG(512, 1, 512, 4, 1024)
-#undef QGX_DG
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    if (!m->dg_z) QGX_HIP(hipMalloc((void **)&m->dg_z, (size_t)d.B * DZF * (d.N + large_zpad()) * d.N * sizeof(double2)));
+    LargeCall x;
+    x.c = &c; x.qh = qh; x.Sh = Sh; x.dq_p = dq_p; x.dq_pp = dq_pp; x.acc = &acc;
+    return large_tiles(d.N, L_DIAG, m, x, st);
 }
 
 // ================================================================================================
@@ -1139,6 +1077,8 @@ __global__ __launch_bounds__(TEAM_NT) void k_l_team_steps(SpecDev d, TeamArgs a)
     if (tid < RW) lll[tid] = d.ll[pair_row(p0 + (tid >> 1), tid & 1, N)];
     __syncthreads();
 
+    // (the formulas of the two lambdas are those of spectral_elem.hpp, written out: calling them there changes this
+    // kernel's register allocation and schedule)
     // one element of the build phase: spectra of (u_k + i v_k) and (q_1 + i q_2), Hermitian-extended, into the LDS lines
     auto build = [&](const TeamState &st, int i, int rl, int te) {
         const int rm = (p0 + (rl >> 1)) == 0 ? rl : (rl ^ 1);

@@ -7,15 +7,16 @@
 // executed as six complex N x N transforms of packed pairs
 //   (u_k + i v_k), ((u_k+U_k) q_k + i v_k q_k), (S_1 + i S_2), (q_1 + i q_2)
 // entirely inside one CU's LDS (N <= 96: N*(N+1)*16 B <= 149 KB).
+// The per-element arithmetic is that of spectral_elem.hpp, shared with spectral_large.hip; the functions here add the
+// addressing of the digit-reversed LDS field to it.
 #include "common.hpp"
 #include "fft_lds.hpp"
+#include "spectral_elem.hpp"
 #include "philox.hpp"
 #include "diag_acc.hpp"
 #include <cstdlib>
 
 namespace qgx {
-
-__device__ __forceinline__ int neg_mod(int j, int N) { return j == 0 ? 0 : N - j; }
 
 struct Grid {
     int N, NK, LD, nrad;
@@ -28,30 +29,15 @@ struct Grid {
 __device__ __forceinline__ void unpack_pair(const double2 *Z, const Grid &g, int j, int i,
                                             double2 &A, double2 &Bv) {
     const int jm = neg_mod(j, g.N), im = neg_mod(i, g.N);
-    const double2 a = Z[g.pos[j] * g.LD + g.pos[i]];
-    const double2 b = cconj(Z[g.pos[jm] * g.LD + g.pos[im]]);
-    A = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y + b.y));
-    // -i/2 * (a - b)
-    Bv = make_double2(0.5 * (a.y - b.y), -0.5 * (a.x - b.x));
+    unpack_half(Z[g.pos[j] * g.LD + g.pos[i]], Z[g.pos[jm] * g.LD + g.pos[im]], A, Bv);
 }
 
 // store the Hermitian extension of (Ah + i Bh) at (j,i) [and its mirror], DIT-input order.
 // For the self-conjugate columns the caller passes already symmetrised values.
 __device__ __forceinline__ void pack_store(double2 *Z, const Grid &g, int j, int i, double2 Ah,
                                            double2 Bh, double scale) {
-    Z[g.pos[j] * g.LD + g.pos[i]] = make_double2((Ah.x - Bh.y) * scale, (Ah.y + Bh.x) * scale);
-    if (i != 0 && 2 * i != g.N) {
-        const int jm = neg_mod(j, g.N);
-        // conj(Ah) + i conj(Bh)
-        Z[g.pos[jm] * g.LD + g.pos[g.N - i]] =
-            make_double2((Ah.x + Bh.y) * scale, (Bh.x - Ah.y) * scale);
-    }
-}
-
-__device__ __forceinline__ double2 invert_layer(const SpecDev &d, int k, int idx, double2 q0, double2 q1) {
-    const int sz = d.N * d.NK;
-    const double a0 = d.a[(2 * k) * sz + idx], a1 = d.a[(2 * k + 1) * sz + idx];
-    return make_double2(a0 * q0.x + a1 * q1.x, a0 * q0.y + a1 * q1.y);
+    Z[g.pos[j] * g.LD + g.pos[i]] = pack_self(Ah, Bh, scale);
+    if (i != 0 && 2 * i != g.N) Z[g.pos[neg_mod(j, g.N)] * g.LD + g.pos[g.N - i]] = pack_mirror(Ah, Bh, scale);
 }
 
 // Build the packed spectrum of (u_k + i v_k) from qh; optionally store ph_k.
@@ -63,18 +49,13 @@ __device__ __forceinline__ void build_uv(double2 *Z, const Grid &g, const SpecDe
         const double2 ph = invert_layer(d, k, idx, qh0[idx], qh1[idx]);
         if (ph_out) ph_out[idx] = ph;
         const double kx = d.kk[i], ly = d.ll[j];
-        // uh = -i l ph ; vh = i k ph
-        double2 uh = make_double2(ly * ph.y, -ly * ph.x);
-        double2 vh = make_double2(-kx * ph.y, kx * ph.x);
+        double2 uh = u_hat(ly, ph), vh = v_hat(kx, ph);
         if (i == 0 || 2 * i == N) {
             const int jm = neg_mod(j, N);
             const int idm = jm * NK + i;
             const double2 pm = invert_layer(d, k, idm, qh0[idm], qh1[idm]);
-            const double lm = d.ll[jm];
-            const double2 um = make_double2(lm * pm.y, -lm * pm.x);
-            const double2 vm = make_double2(-kx * pm.y, kx * pm.x);
-            uh = make_double2(0.5 * (uh.x + um.x), 0.5 * (uh.y - um.y));
-            vh = make_double2(0.5 * (vh.x + vm.x), 0.5 * (vh.y - vm.y));
+            uh = herm_mean(uh, u_hat(d.ll[jm], pm));
+            vh = herm_mean(vh, v_hat(kx, pm));
         }
         pack_store(Z, g, j, i, uh, vh, d.invN2);
     }
@@ -89,9 +70,8 @@ __device__ __forceinline__ void build_pair(double2 *Z, const Grid &g, const doub
         double2 a = Ah[idx], b = Bh ? Bh[idx] : make_double2(0., 0.);
         if (i == 0 || 2 * i == N) {
             const int idm = neg_mod(j, N) * NK + i;
-            const double2 am = Ah[idm], bm = Bh ? Bh[idm] : make_double2(0., 0.);
-            a = make_double2(0.5 * (a.x + am.x), 0.5 * (a.y - am.y));
-            b = make_double2(0.5 * (b.x + bm.x), 0.5 * (b.y - bm.y));
+            a = herm_mean(a, Ah[idm]);
+            b = herm_mean(b, Bh ? Bh[idm] : make_double2(0., 0.));
         }
         pack_store(Z, g, j, i, a, b, scale);
     }
@@ -359,16 +339,8 @@ __global__ void k_step_small(SpecDev d, StepArgs a) {
                 double2 uqh, vqh;
                 unpack_pair(Z, g, j, i, uqh, vqh);
                 const double2 ph = invert_layer(d, k, idx, q0, q1);
-                const double kx = d.kk[i], ly = d.ll[j];
-                const double kq = kx * d.Qy[k];
-                // -(ik uqh + il vqh + ik Qy ph)
-                tx = (kx * uqh.y + ly * vqh.y + kq * ph.y);
-                ty = -(kx * uqh.x + ly * vqh.x + kq * ph.x);
-                if (k == 1 && d.rek != 0.0) {
-                    const double f = d.rek * d.wv2[idx];
-                    tx += f * ph.x;
-                    ty += f * ph.y;
-                }
+                const double2 t = tendency_elem(k, d.kk[i], d.ll[j], d.Qy[k], d.rek, d.wv2 + idx, uqh, vqh, ph);
+                tx = t.x; ty = t.y;
             } else {
                 const double2 t = a.dq_new[o];      // what half 1 stored
                 tx = t.x; ty = t.y;
@@ -385,8 +357,7 @@ __global__ void k_step_small(SpecDev d, StepArgs a) {
                 const double2 qk = k == 0 ? q0 : q1;
                 const double f = d.filtr[idx];
                 a.dq_new[o] = make_double2(tx, ty);
-                double2 qn = make_double2(f * (qk.x + a.dt1 * tx + a.dt2 * p.x + a.dt3 * pp.x),
-                                          f * (qk.y + a.dt1 * ty + a.dt2 * p.y + a.dt3 * pp.y));
+                double2 qn = ab3_filter(f, qk, make_double2(tx, ty), p, pp, a.dt1, a.dt2, a.dt3);
                 if (SIB && sib_lost) qn = make_double2(__longlong_as_double(0x7ff8000000000000ll), 0.);   // never a silently wrong state
                 a.qh_out[o] = qn;
                 if constexpr (PF) {
@@ -411,9 +382,8 @@ __global__ void k_step_small(SpecDev d, StepArgs a) {
                 double2 av = qnew[r], bv = make_double2(0., 0.);
                 if (i == 0 || 2 * i == N) {
                     const int idm = neg_mod(j, N) * NK + i;
-                    const double2 am = Ah[idm], bm = make_double2(0., 0.);
-                    av = make_double2(0.5 * (av.x + am.x), 0.5 * (av.y - am.y));
-                    bv = make_double2(0.5 * (bv.x + bm.x), 0.5 * (bv.y - bm.y));
+                    av = herm_mean(av, Ah[idm]);
+                    bv = herm_mean(bv, make_double2(0., 0.));
                 }
                 pack_store(Z, g, j, i, av, bv, d.invN2);
             }
@@ -694,8 +664,8 @@ __global__ __launch_bounds__(1024) void k_diag_small_reg(SpecDev d, DiagConst c,
                 const int idm = neg_mod(j, N) * NK + i;
                 double2 am = ph0[idm], bm = ph1[idm];
                 if (XIH) { const double w = -d.wv2[idm]; am = make_double2(w * am.x, w * am.y); bm = make_double2(w * bm.x, w * bm.y); }
-                a = make_double2(0.5 * (a.x + am.x), 0.5 * (a.y - am.y));
-                bb = make_double2(0.5 * (bb.x + bm.x), 0.5 * (bb.y - bm.y));
+                a = herm_mean(a, am);
+                bb = herm_mean(bb, bm);
             }
             pack_store(Z, g, j, i, a, bb, d.invN2);
         }

@@ -448,6 +448,19 @@ def test_sixteen_diagnostics_match_oracle(N, B, forced, opts):
     print(f'\nGRID diagnostics N={N} B={B} forcing={forced} {opts}: worst error {worst:.2e} of the maximum')
 
 
+# ------------------------------------------------------------------------------------------------ large-grid step options
+@pytest.mark.parametrize('opt', ['large_fused', 'large_lazy_q', 'large_specialised'])
+@pytest.mark.parametrize('N', [128, 144])
+def test_large_step_options_match_oracle(N, opt):
+    """each step option switched off where it does select another path: 128 is the smallest grid with compile-time-N
+    kernels, 144 the smallest run-time-N grid with four lines per workgroup.  large_specialised = 0: the run-time-N
+    kernels at a size that has a specialisation; large_lazy_q = 0: the eager unparameterized step; large_fused = 0: the
+    unfused step at a size that normally fuses"""
+    e, worst, _ = _steps_against_oracle(N, 2, 6, _step_params(N), {opt: 0})
+    e.close()
+    print(f'\nGRID large options N={N} {opt}=0: worst q / qh error {worst * F64_TOL:.2e} per step')
+
+
 # ------------------------------------------------------------------------------------------------ 512 x 512
 @pytest.mark.parametrize('opt', ['large_fused', 'large_lazy_q', 'large_specialised'])
 @pytest.mark.parametrize('value', [0, 1])

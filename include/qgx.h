@@ -107,7 +107,16 @@ int qgx_invert(qgx_model *m, void *stream);
  * Replaces pyqg Model._step_forward driven by run_with_snapshots
  * (simulate.py:137) including the plugin call of parameterization.py:23-34 and
  * the samplers of stochastic_pyqg.py:30-72. */
-enum qgx_sampling { QGX_SAMPLING_AR1 = 0, QGX_SAMPLING_CONSTANT = 1 };
+/* QGX_SAMPLING_DETERMINISTIC (parameterization.py:27-28 -> predict_mean_snapshot, cgan_regression.py:164-171,
+ * cvae_regression.py:138-145, mean_var_model.py:111-115): every step applies the de-meaned mean of `n_mean` generator
+ * realisations for the current PV (GZ: the mean net alone, n_mean is not used).  Realisation j (0-based) of global member
+ * `member_offset + b` at the t-th deterministic step of the handle draws the Philox stream
+ * (seed, member, t + ((uint64_t)(j + 1) << 32)): the high word of the step is 0 on every AR1 / constant draw, so the streams
+ * never collide with those.  The sampler state (the latent noise QGX_F_Z, the constant sampler's counter) is neither read
+ * nor written; `nsteps` is ignored.  Refused with QGX_ERR_INVALID before anything is launched or changed: n_mean < 1 or
+ * > 65536, z_external_dev, an OLS or ANN generator (the reference defines no predict_mean_snapshot for them), a grid the
+ * nets do not take for the pseudo-batch launched (qgx_generator_forward_mean). */
+enum qgx_sampling { QGX_SAMPLING_AR1 = 0, QGX_SAMPLING_CONSTANT = 1, QGX_SAMPLING_DETERMINISTIC = 2 };
 
 typedef struct qgx_param {
     qgx_generator *gen;      /* NULL: use `forcing_dev` as S (or no forcing if that is NULL too) */
@@ -122,7 +131,7 @@ typedef struct qgx_param {
     const double *forcing_dev;  /* gen == NULL: externally supplied S (B,2,N,N), used as is
                                    (plain pyqg q_parameterization semantics)             */
     int32_t  demean;         /* subtract the per-layer spatial mean of S (parameterization.py:25) */
-    int32_t  reserved;
+    int32_t  n_mean;         /* QGX_SAMPLING_DETERMINISTIC: realisations M averaged per step (reference: 100); not read otherwise */
 } qgx_param;
 
 /* advance `nsteps_to_run` steps; `p` may be NULL (unparameterized, simulate.py:121).
@@ -140,6 +149,7 @@ typedef struct qgx_param {
  * step kernel that needs nothing of the forcing runs as a kernel of its own on an internal side stream, forked from and
  * joined into `stream` inside every step; bit-identical, and measured slower on this stack. */
 int qgx_step(qgx_model *m, int nsteps_to_run, const qgx_param *p, int refresh_diag, void *stream);
+/* (QGX_SAMPLING_DETERMINISTIC never steps in halves: qgx_step_streams returns 1.) */
 /* Small grids with a generator attached: an even ensemble may advance as two halves on two internal streams that fork from
  * and join `stream` inside the call (members are independent — the reference runs them as separate processes,
  * scripts/run_parameterized.py:55-63 — and the halves fill the idle phases of each other's launch chain); option "streams" of
@@ -158,7 +168,9 @@ int qgx_reset_time(qgx_model *m);
  * "diag_wide" (-1 auto|0|1: its transforms as (member, transform) workgroups),
  * "lsplit" (-1 auto|0|1: one workgroup per member and layer), "spec_threads" (0 auto|256|512|1024), "team" (0|1:
  * XCD-resident runs at 256 x 256), "team_min" (shortest such run), "large_fused", "large_lazy_q",
- * "large_specialised" (0|1: the large-grid kernel variants).  The library reads NO environment variable. */
+ * "large_specialised" (0|1: the large-grid kernel variants), "mean_chunk" (QGX_SAMPLING_DETERMINISTIC: pseudo-members
+ * (member x realisation) per launch of the generator, the `chunk` of qgx_generator_forward_mean; 0 = automatic; a value
+ * below the member count is refused by the step).  The library reads NO environment variable. */
 int qgx_set_option(qgx_model *m, const char *name, int value);
 
 /* status reductions of pyqg's _print_status: out_dev[2*b+0] = KE, [2*b+1] = CFL (of ph,u,v as the last step stored
@@ -291,6 +303,19 @@ int qgx_generator_create_ann(const qgx_ann_weights *w, float x_scale, float y_sc
  * z is float for GAN/VAE, double for GZ, unused (may be NULL) for OLS and ANN. */
 int qgx_generator_forward(qgx_generator *g, const double *q_dev, const void *z_dev,
                           double *S_dev, int B, int N, int demean, void *stream);
+/* The forcing of predict_mean_snapshot for each of B members (cgan_regression.py:164-171, cvae_regression.py:138-145,
+ * mean_var_model.py:111-115): S (B,2,N,N) = y_std * (mean_j G([q/x_std, xi_j]) [+ net_mean(q/x_std)]) over M realisations,
+ * the mean accumulated in float64 in realisation order, rounded to float32, summed with the regression net's output and
+ * scaled in float32; demean != 0 also applies parameterization.py:25.  xi_j of member b is the Philox stream
+ * (seed, member_offset + b, step + ((uint64_t)(j + 1) << 32)), drawn inside the input kernel.  Realisations are evaluated
+ * as pseudo-members p = b * R + r of one batched forward, R per launch with B * R <= chunk (0 = automatic: 256; the last
+ * launch takes the remainder); the regression net is evaluated once on the B inputs.  Results are bitwise repeatable and
+ * depend on `chunk` only through the kernels a pseudo-batch of that size takes.  GZ: S = y_std * net_mean(q/x_std), no
+ * draws, net_var is not evaluated, M is not used beyond its check.  OLS / ANN: QGX_ERR_INVALID.
+ * Checked before any HIP call (QGX_ERR_INVALID): null pointers, B < 1, M < 1, M > 65536, step >= 2^32, 0 < chunk < B,
+ * a grid the nets do not take for the pseudo-batches launched. */
+int qgx_generator_forward_mean(qgx_generator *g, const double *q_dev, double *S_dev, int B, int N, int M, int chunk,
+                               int demean, uint64_t seed, uint64_t member_offset, uint64_t step, void *stream);
 /* raw CNN forward of net `inet`: x (B,n_in,N,N) float -> y (B,n_out,N,N) float
  * (AndrewCNN.forward in eval mode; used by predict_mean_snapshot / offline sampling) */
 int qgx_cnn_forward(qgx_generator *g, int inet, const float *x_dev, float *y_dev,

@@ -26,7 +26,7 @@ class qgx_param(C.Structure):
     _fields_ = [('gen', C.c_void_p), ('sampling', C.c_int32), ('nsteps', C.c_int32),
                 ('weight', C.c_double), ('seed', C.c_uint64), ('member_offset', C.c_uint64),
                 ('z_external_dev', C.c_void_p), ('forcing_dev', C.c_void_p),
-                ('demean', C.c_int32), ('reserved', C.c_int32)]
+                ('demean', C.c_int32), ('n_mean', C.c_int32)]
 
 
 class qgx_cnn_weights(C.Structure):
@@ -58,7 +58,7 @@ class qgx_ann_weights(C.Structure):
 # enum mirrors (include/qgx.h)
 F_Q, F_QH, F_PH, F_U, F_V, F_DQHDT, F_DQHDT_P, F_DQHDT_PP, F_S, F_Z, F_P = range(11)
 T_FILTR, T_WV2, T_A, T_KK, T_LL = range(5)
-SAMPLING_AR1, SAMPLING_CONSTANT = 0, 1
+SAMPLING_AR1, SAMPLING_CONSTANT, SAMPLING_DETERMINISTIC = 0, 1, 2
 DIAGS = ['KEspec', 'Ensspec', 'entspec', 'APEflux', 'KEflux', 'APEgenspec', 'KEfrictionspec', 'paramspec',
          'paramspec_APEflux', 'paramspec_KEflux', 'Dissspec', 'ENSDissspec', 'ENSflux', 'ENSgenspec', 'ENSfrictionspec',
          'ENSparamspec']
@@ -101,6 +101,8 @@ SYMBOLS = [
     ('qgx_generator_destroy', C.c_int, [C.c_void_p]),
     ('qgx_generator_forward', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_int, C.c_int, C.c_void_p]),
+    ('qgx_generator_forward_mean', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
     ('qgx_cnn_forward', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                   C.c_void_p]),
     ('qgx_rfft2', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -73,6 +73,7 @@ struct ModelOpts {
     int team_min = 2;            //   shortest run handed to that kernel
     int team_fault = 0;          //   A/B library only: raise the run kernel's flag at the end of the next run (test hook)
     int step_fault = 0;          //   A/B library only: half-ensemble (1 | 2) of a two-stream qgx_step refuses its second chunk (test hook)
+    int mean_chunk = 0;          // deterministic sampling: pseudo-members (member x realisation) per generator launch (0 auto: 256)
     int large_fused = 1;         // large grids: fused row / column kernels (0: one launch per pass and pointwise phase)
     int large_lazy_q = 1;        // large grids: unparameterized steps keep no real-space q
     int large_specialised = 1;   // large grids: compile-time-N kernels at 128 / 256; diagnostics also 512
@@ -240,6 +241,13 @@ struct NoiseUpdate {
 // (GenFuse::y ...); input_ready: the previous step kernel already assembled the network input (GenFuse::X ...)
 int generator_forward(qgx_generator *g, const double *q, const void *z, double *S, int B, int N,
                       int demean, hipStream_t st, const NoiseUpdate *nu, GenFuse *defer = nullptr, bool input_ready = false);
+// Deterministic sampling (predict_mean_snapshot for every member): S = y_std * (mean of M realisations of net 0 [+ net_mean]),
+// realisation j of member b on the Philox stream (seed, member_offset + b, step + ((j + 1) << 32)); GZ: the mean net alone.
+// generator_mean_check: everything generator_forward_mean refuses apart from null pointers, with no HIP call (qgx_step asks
+// it before it touches anything)
+int generator_forward_mean(qgx_generator *g, const double *q, double *S, int B, int N, int M, int chunk, int demean,
+                           uint64_t seed, uint64_t member_offset, uint64_t step, hipStream_t st);
+int generator_mean_check(const qgx_generator *g, int B, int N, int M, int chunk, uint64_t step);
 // QGX_OK if the handle's nets (inet >= 0: that net alone) run B members at N x N, else QGX_ERR_INVALID naming N; no HIP call
 int generator_size_ok(const qgx_generator *g, int B, int N, int inet = -1);
 // the generator's input buffer, input scales and range words for the GenFuse::X part (after reserve)

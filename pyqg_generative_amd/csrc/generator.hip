@@ -1,6 +1,6 @@
 // The generator handle: lifecycle and workspaces, the model-independent kernels around a net (network input from q and the
 // latent noise, output scaling + de-mean, range words, Monte-Carlo moments), generator_forward with its dispatch over the
-// model kinds, and the C ABI that is not AndrewCNN-specific.
+// model kinds, generator_forward_mean (deterministic sampling: the mean of M realisations per member), and the C ABI that is not AndrewCNN-specific.
 //
 // Replaces the model wrappers models/cgan_regression.py:157-162, cvae_regression.py:131-136, mean_var_model.py:105-109,
 // ols_model.py:68-75, ann_model.py:82-93 and the per-layer de-mean of models/parameterization.py:25.  The nets themselves
@@ -95,6 +95,69 @@ __global__ void k_prep_noise(const double *q, float *z, const float *xi_ext, flo
         }
     }
     input_absmax(m, range);
+}
+
+// Deterministic sampling, input assembly of one chunk of R realisations (first_real .. first_real + R - 1) of every member:
+//   X[p] = [float(q_b)/x_std, xi],  p = b R + r,  xi = Philox(seed, member, step + ((first_real + r + 1) << 32))
+// One thread per quad of the (2,N,N) member field; the q channels are converted once per thread and stored for every
+// realisation the thread writes (r = blockIdx.z, blockIdx.z + gridDim.z, ...); the draw goes straight into X, there is no z.
+__global__ void k_prep_mean(const double *q, float *X, int npix, int R, int first_real, float xs0, float xs1, uint64_t seed,
+                            uint64_t member_offset, uint64_t step, unsigned *range) {
+    const int member = blockIdx.y;
+    const int quads = 2 * npix / 4;
+    const int quad = blockIdx.x * blockDim.x + threadIdx.x;
+    float m = 0.f;
+    if (quad < quads) {
+        const size_t o = (size_t)member * 2 * npix + 4 * (size_t)quad;
+        const int i = 4 * quad;                          // flat index in (2, npix); npix % 4 == 0
+        const float xs = i < npix ? xs0 : xs1;
+        f32x4 xq;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            xq[e] = (float)q[o + e] / xs;
+            m = fmaxf(m, abs_or_inf(xq[e]));
+        }
+        for (int r = blockIdx.z; r < R; r += gridDim.z) {
+            float x[4];
+            philox_normal4(seed, member_offset + member, step + ((uint64_t)(first_real + r + 1) << 32), (uint32_t)quad, x);
+            float *Xp = X + ((size_t)member * R + r) * 4 * npix;
+            *reinterpret_cast<f32x4 *>(Xp + i) = xq;
+            f32x4 xi;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                xi[e] = x[e];
+                m = fmaxf(m, abs_or_inf(x[e]));
+            }
+            *reinterpret_cast<f32x4 *>(Xp + 2 * (size_t)npix + i) = xi;
+        }
+    }
+    input_absmax(m, range);
+}
+
+// ... and the sum over them: acc (B,2,N,N) float64 <- [acc +] the chunk's R outputs y (B R, 2, N, N) in realisation order
+// (first: the first chunk overwrites, no memset); after the last chunk mean (B,2,N,N) <- float(acc / M)
+// (predict_mean_snapshot: .mean(0) — here in float64, rounded once).  One thread per 4 elements, no atomics: bitwise repeatable.
+__global__ void k_mean_accumulate(const float *y, double *acc, float *mean, int n4_member, int B, int R, int first, int last,
+                                  double M) {
+    typedef double f64x2 __attribute__((ext_vector_type(2)));
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)B * n4_member) return;
+    const size_t b = idx / n4_member, i4 = idx % n4_member;
+    f64x2 *a = reinterpret_cast<f64x2 *>(acc) + 2 * idx;
+    f64x2 lo = {0.0, 0.0}, hi = {0.0, 0.0};
+    if (!first) { lo = a[0]; hi = a[1]; }
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(y) + b * R * n4_member + i4;
+    for (int r = 0; r < R; ++r) {
+        const f32x4 v = src[(size_t)r * n4_member];
+        lo[0] += (double)v[0]; lo[1] += (double)v[1];
+        hi[0] += (double)v[2]; hi[1] += (double)v[3];
+    }
+    if (last) {
+        const f32x4 mu = {(float)(lo[0] / M), (float)(lo[1] / M), (float)(hi[0] / M), (float)(hi[1] / M)};
+        reinterpret_cast<f32x4 *>(mean)[idx] = mu;
+    } else {
+        a[0] = lo; a[1] = hi;
+    }
 }
 
 // Fused output scaling + per-layer de-mean: one workgroup per (member, layer).
@@ -330,6 +393,81 @@ int generator_forward(qgx_generator *g, const double *q, const void *z, double *
     return QGX_OK;
 }
 
+// ---- deterministic sampling: predict_mean_snapshot for every member ------------------------------------------------------
+// realisations per launch of net 0: the largest R with B R <= chunk (0: 256, a measured default — DESIGN.md, "Deterministic
+// sampling"), at least 1, at most M
+static int mean_chunk_R(int B, int M, int chunk) {
+    const int cap = chunk > 0 ? chunk : 256;
+    return std::max(1, std::min(M, cap / B));
+}
+
+int generator_mean_check(const qgx_generator *g, int B, int N, int M, int chunk, uint64_t step) {
+    QGX_REQUIRE(g && B > 0, "generator_forward_mean: bad argument");
+    QGX_REQUIRE(M >= 1 && M <= 65536, "generator_forward_mean: M = %d realisations (1 ... 65536)", M);
+    QGX_REQUIRE(step < (1ull << 32), "generator_forward_mean: step must be below 2^32 (its high word numbers the realisation)");
+    QGX_REQUIRE(chunk == 0 || chunk >= B, "generator_forward_mean: chunk = %d is below the member count %d (0 = automatic)", chunk, B);
+    QGX_REQUIRE(generator_takes_noise(g),
+                "deterministic sampling: the reference defines no predict_mean_snapshot for an OLS or ANN parameterization");
+    QGX_REQUIRE(N > 0 && (N * N) % 4 == 0, "generator_forward_mean: N*N must be a multiple of 4");
+    if (g->kind == QGX_GEN_GZ) return generator_size_ok(g, B, N, 0);          // the mean net alone
+    // net 0 on the pseudo-batches actually launched (full chunks and the remainder), the regression net on the B members
+    const int R = mean_chunk_R(B, M, chunk);
+    QGX_REQUIRE((int64_t)B * R <= INT32_MAX / 8, "generator_forward_mean: pseudo-batch %d x %d is too large", B, R);
+    if (const int rc = generator_size_ok(g, B * R, N, 0)) return rc;
+    if (M % R) { if (const int rc = generator_size_ok(g, B * (M % R), N, 0)) return rc; }
+    if (g->n_nets == 2) return generator_size_ok(g, B, N, 1);
+    return QGX_OK;
+}
+
+int generator_forward_mean(qgx_generator *g, const double *q, double *S, int B, int N, int M, int chunk, int demean,
+                           uint64_t seed, uint64_t member_offset, uint64_t step, hipStream_t st) {
+    QGX_REQUIRE(g && q && S, "generator_forward_mean: null argument");
+    if (const int rc = generator_mean_check(g, B, N, M, chunk, step)) return rc;
+    const int npix = N * N;
+    dim3 pg((npix + 255) / 256, B), pb(256);
+    int rc;
+    if (g->kind == QGX_GEN_GZ) {
+        // mean_var_model.py:111-115: S = y_std * net_mean(q / x_std); no draws, net_var is not evaluated
+        if ((rc = generator_reserve(g, B, N))) return rc;
+        const Workspace &w = g->work();
+        hipLaunchKernelGGL(k_prep_input, pg, pb, 0, st, q, (const float *)nullptr, w.X, 2, npix, g->x_std[0], g->x_std[1], g->range_dev);
+        if ((rc = cnn_forward(g, g->nets[0], w.X, w.Y0, B, N, st))) return rc;
+        finish(g, nullptr, FIN_PLAIN, nullptr, nullptr, S, B, npix, demean, st);
+        QGX_HIP(hipGetLastError());
+        return QGX_OK;
+    }
+    const int R = mean_chunk_R(B, M, chunk);
+    if ((rc = generator_reserve(g, B * R, N))) return rc;          // every buffer below holds B R pseudo-members
+    Workspace &w = g->work();
+    const size_t out_elems = (size_t)B * 2 * npix;
+    if (w.mean_elems < out_elems) {
+        w.free_mean();
+        QGX_HIP(hipMalloc((void **)&w.mean_acc, out_elems * sizeof(double)));
+        w.mean_elems = out_elems;
+    }
+    const bool regression = g->n_nets == 2;
+    if (regression) {
+        // net_mean(q / x_std), ONCE on the B members (cgan_regression.py:169-170), before the chunks take X over
+        hipLaunchKernelGGL(k_prep_input, pg, pb, 0, st, q, (const float *)nullptr, w.X, 2, npix, g->x_std[0], g->x_std[1], g->range_dev);
+        if ((rc = cnn_forward(g, g->nets[1], w.X, w.Y1, B, N, st))) return rc;
+    }
+    const int quads = 2 * npix / 4, n4 = 2 * npix / 4;
+    for (int j0 = 0; j0 < M; j0 += R) {
+        const int Rc = std::min(R, M - j0);
+        // net 0's raw output of the chunk: the (B R, 2, N, N) region behind X (Y0 takes the mean, Y1 the regression net's output)
+        float *Yc = w.X + (size_t)B * R * 4 * npix;
+        hipLaunchKernelGGL(k_prep_mean, dim3((quads + 255) / 256, B, std::min(Rc, 16)), pb, 0, st, q, w.X, npix, Rc, j0,
+                           g->x_std[0], g->x_std[1], seed, member_offset, step, g->range_dev);
+        if ((rc = net0_forward(g, w.X, Yc, B * Rc, N, st))) return rc;
+        const size_t threads = (size_t)B * n4;
+        hipLaunchKernelGGL(k_mean_accumulate, dim3((unsigned)((threads + 255) / 256)), pb, 0, st, (const float *)Yc, w.mean_acc,
+                           w.Y0, n4, B, Rc, j0 == 0 ? 1 : 0, j0 + Rc == M ? 1 : 0, (double)M);
+    }
+    finish(g, nullptr, regression ? FIN_SUM : FIN_PLAIN, regression ? w.Y1 : nullptr, nullptr, S, B, npix, demean, st);
+    QGX_HIP(hipGetLastError());
+    return QGX_OK;
+}
+
 }  // namespace qgx
 
 using namespace qgx;
@@ -415,7 +553,7 @@ extern "C" int qgx_generator_destroy(qgx_generator *g) {
     if (!g) return QGX_OK;
     (void)hipSetDevice(g->device);
     for (NetHost &net : g->nets) cnn_free_net(net);
-    for (Workspace &w : g->ws) { w.free_activations(); w.free_part(); }
+    for (Workspace &w : g->ws) { w.free_activations(); w.free_part(); w.free_mean(); }
     if (g->range_dev) (void)hipFree(g->range_dev);
     unet_destroy(g->unet);
     ann_destroy(g->ann);
@@ -438,6 +576,11 @@ extern "C" int qgx_generator_range_read(qgx_generator *g, unsigned *flags, float
 extern "C" int qgx_generator_forward(qgx_generator *g, const double *q_dev, const void *z_dev, double *S_dev,
                                      int B, int N, int demean, void *stream) {
     return generator_forward(g, q_dev, z_dev, S_dev, B, N, demean, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int qgx_generator_forward_mean(qgx_generator *g, const double *q_dev, double *S_dev, int B, int N, int M, int chunk,
+                                          int demean, uint64_t seed, uint64_t member_offset, uint64_t step, void *stream) {
+    return generator_forward_mean(g, q_dev, S_dev, B, N, M, chunk, demean, seed, member_offset, step, (hipStream_t)stream);
 }
 
 extern "C" int qgx_generator_size_ok(const qgx_generator *g, int inet, int B, int N) {

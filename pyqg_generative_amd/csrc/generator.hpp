@@ -52,6 +52,12 @@ struct Workspace {
         for (float **p : {&actA, &actB, &X, &Y0, &Y1}) if (*p) { (void)hipFree(*p); *p = nullptr; }
         cap_elems = 0;
     }
+    double *mean_acc = nullptr;    // deterministic sampling: float64 sum over realisations (B, 2, N, N), kept across the chunks
+    size_t mean_elems = 0;
+    void free_mean() {
+        if (mean_acc) (void)hipFree(mean_acc);
+        mean_acc = nullptr; mean_elems = 0;
+    }
     void free_part() {
         if (part) (void)hipFree(part);
         part = nullptr; part_elems = 0;

@@ -464,6 +464,7 @@ extern "C" int qgx_set_option(qgx_model *m, const char *name, int value) {
         QGX_REQUIRE(false, "option 'step_fault' is a test hook of the A/B library only (make ab, QGX_LIB=libqgx_ab.so)");
 #endif
     }
+    else if (!strcmp(name, "mean_chunk")) { QGX_REQUIRE(value >= 0, "mean_chunk must be 0 (auto) or a pseudo-member count"); o.mean_chunk = value; }
     else if (!strcmp(name, "large_fused")) o.large_fused = value ? 1 : 0;
     else if (!strcmp(name, "large_lazy_q")) o.large_lazy_q = value ? 1 : 0;
     else if (!strcmp(name, "large_specialised")) o.large_specialised = value ? 1 : 0;
@@ -522,22 +523,35 @@ static int step_adv_ensure(qgx_model *m) {
     return QGX_OK;
 }
 
+// what a deterministic-sampling step refuses, with no HIP call and no write to the model
+static int step_mean_check(const qgx_model *m, const qgx_param *p) {
+    QGX_REQUIRE(p->n_mean >= 1, "qgx_step: deterministic sampling needs n_mean >= 1 realisations (n_mean = %d)", p->n_mean);
+    QGX_REQUIRE(!p->z_external_dev, "qgx_step: deterministic sampling draws its own realisations (z_external_dev)");
+    return generator_mean_check(p->gen, m->B, m->N, p->n_mean, m->opts.mean_chunk, m->noise_step);
+}
+
 // ---- the stepping loop: pyqg model.py::_step_forward with the plugin call of
 // pyqg_generative/models/parameterization.py:23-34 and samplers of stochastic_pyqg.py:30-72
 // the steps of one call on one stream, for the whole ensemble or for one half of it (qgx_step below)
 static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_diag, hipStream_t st) {
     const int N = m->N, B = m->B;
     if (p && p->gen) {
-        QGX_REQUIRE(p->sampling == QGX_SAMPLING_AR1 || p->sampling == QGX_SAMPLING_CONSTANT,
+        QGX_REQUIRE(p->sampling == QGX_SAMPLING_AR1 || p->sampling == QGX_SAMPLING_CONSTANT || p->sampling == QGX_SAMPLING_DETERMINISTIC,
                     "qgx_step: unknown sampling %d", p->sampling);
-        QGX_REQUIRE(!(p->sampling == QGX_SAMPLING_CONSTANT && p->nsteps < 1),
-                    "qgx_step: constant sampler needs nsteps >= 1");
-        QGX_REQUIRE(p->nsteps != 0, "qgx_step: nsteps == 0 is not a valid decorrelation time");
-        QGX_REQUIRE(!(p->z_external_dev && nsteps != 1), "qgx_step: external noise needs nsteps_to_run == 1");
-        QGX_REQUIRE(!(p->z_external_dev && !generator_takes_noise(p->gen)),
-                    "qgx_step: an OLS or ANN generator takes no latent noise (z_external_dev)");
-        m->z_double = generator_noise_is_double(p->gen);
+        if (p->sampling == QGX_SAMPLING_DETERMINISTIC) {
+            // (qgx_step asked all of this before anything was touched; a half-way refusal cannot happen here)
+            if (nsteps > 0) { if (const int drc = step_mean_check(m, p)) return drc; }
+        } else {
+            QGX_REQUIRE(!(p->sampling == QGX_SAMPLING_CONSTANT && p->nsteps < 1),
+                        "qgx_step: constant sampler needs nsteps >= 1");
+            QGX_REQUIRE(p->nsteps != 0, "qgx_step: nsteps == 0 is not a valid decorrelation time");
+            QGX_REQUIRE(!(p->z_external_dev && nsteps != 1), "qgx_step: external noise needs nsteps_to_run == 1");
+            QGX_REQUIRE(!(p->z_external_dev && !generator_takes_noise(p->gen)),
+                        "qgx_step: an OLS or ANN generator takes no latent noise (z_external_dev)");
+            m->z_double = generator_noise_is_double(p->gen);      // (deterministic sampling leaves the sampler state alone)
+        }
     }
+    const bool det = p && p->gen && p->sampling == QGX_SAMPLING_DETERMINISTIC;
     // OLS (generate_latent_noise returns 0, ols_model.py:65-66): the sampler only decides when the forcing is recomputed —
     // AR1 on every step, constant on steps 1, n+1, 2n+1, ... (stochastic_pyqg.py:30-72) — with no draw and no write to z
     const bool noisy = p && p->gen && generator_takes_noise(p->gen);
@@ -575,7 +589,19 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
         StepArgs pre;
         bool have_pre = false;
         int ablevel_before = m->ablevel;
-        if (p && p->gen) {
+        if (det) {
+            // parameterization.py:27-28: the de-meaned mean of n_mean realisations for the current PV, recomputed on every step;
+            // never deferred into the step kernel, no next-input epilogue; z, have_noise and const_counter are not touched
+            weight = p->weight;
+            if (!m->small) { int qrc = large_ensure_q(m, st); if (qrc) return qrc; }
+            int rc = generator_forward_mean(p->gen, m->q, m->S, B, N, p->n_mean, m->opts.mean_chunk, p->demean, p->seed,
+                                            p->member_offset, m->noise_step, st);
+            if (rc) return rc;
+            m->noise_step += 1;
+            m->have_forcing = true;
+            has_S = true;
+            S = m->S;
+        } else if (p && p->gen) {
             weight = p->weight;
             bool compute = true;
             double a = 0.0, b = 1.0;
@@ -700,6 +726,7 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
 // kernels, so the bench's live roofline of that kernel would describe the mix, not the kernel.
 static bool step_in_halves(const qgx_model *m, const qgx_param *p) {
     if (m->opts.streams == 1 || !m->small || (m->B & 1) || !p || !p->gen || p->z_external_dev) return false;
+    if (p->sampling == QGX_SAMPLING_DETERMINISTIC) return false;      // its pseudo-batches fill the device on one stream
     if (m->opts.streams == 2) return true;
     return m->N == 96 && m->B >= 16 && m->B <= 64;
 }
@@ -715,8 +742,12 @@ extern "C" int qgx_step(qgx_model *m, int nsteps, const qgx_param *p, int refres
     // a grid the generator's kernels do not take is refused here: before any launch, and before step_core touches the
     // sampler state (the halves of an ensemble stepped on two streams ask the kernels for B / 2 members)
     if (p && p->gen && nsteps > 0) {
-        if (int src = generator_size_ok(p->gen, m->B, m->N)) return src;
-        if (step_in_halves(m, p)) { if (int src = generator_size_ok(p->gen, m->B / 2, m->N)) return src; }
+        if (p->sampling == QGX_SAMPLING_DETERMINISTIC) {       // (the size rule is asked for the pseudo-batch actually launched)
+            if (int src = step_mean_check(m, p)) return src;
+        } else {
+            if (int src = generator_size_ok(p->gen, m->B, m->N)) return src;
+            if (step_in_halves(m, p)) { if (int src = generator_size_ok(p->gen, m->B / 2, m->N)) return src; }
+        }
     }
     { int trc = team_settle(m, st); if (trc) return trc; }
     if (p && p->gen && nsteps > 0) { int arc = step_adv_ensure(m); if (arc) return arc; }

@@ -244,6 +244,22 @@ class Generator:
             return S
         return self._guarded(launch)
 
+    def forward_mean(self, q, M, seed=0, member_offset=0, step=0, demean=True, chunk=0, out=None):
+        """Deterministic sampling (predict_mean_snapshot for every member): q (B,2,N,N) float64 cuda -> S (B,2,N,N) float64,
+        y_std * (mean of M realisations of the generator [+ net_mean]); 'gz': y_std * net_mean, no draws.  Realisation j of
+        member b draws the Philox stream (seed, member_offset + b, step + ((j + 1) << 32)) on the device.  chunk: pseudo-members
+        (member x realisation) per launch of the generator, 0 = automatic, else at least B.  'ols' and 'ann' have no such
+        mode (QgxError)."""
+        assert q.is_cuda and q.dtype == torch.float64 and q.is_contiguous() and q.dim() == 4
+        B, _, N, _ = q.shape
+        S = out if out is not None else torch.empty_like(q)
+
+        def launch():
+            check(lib.qgx_generator_forward_mean(self._h, _ptr(q), _ptr(S), B, N, int(M), int(chunk), int(bool(demean)),
+                                                 int(seed), int(member_offset), int(step), _stream()))
+            return S
+        return self._guarded(launch)
+
     def cnn_forward(self, x, inet=0):
         """Raw net forward: x (B,n_in,N,N) float32 -> (B,2,N,N) float32 (net 0: the AndrewCNN or U-Net generator, 4 channels;
         'gz' / 'ols': 2 channels; 'ann': the stencil network on (B,1,N,N) images normalised by x_scale -> (B,1,N,N))."""
@@ -419,8 +435,12 @@ class EnsembleEngine:
         return out
 
     # ---- stepping -----------------------------------------------------------------
+    SAMPLINGS = {'AR1': _lib.SAMPLING_AR1, 'constant': _lib.SAMPLING_CONSTANT, 'deterministic': _lib.SAMPLING_DETERMINISTIC}
+
     def step(self, nsteps=1, generator=None, sampling='AR1', nsteps_decor=1, weight=1.0, seed=0,
-             member_offset=0, z_external=None, forcing=None, demean=None, refresh_diag=True):
+             member_offset=0, z_external=None, forcing=None, demean=None, refresh_diag=True, n_mean=100):
+        """sampling='deterministic': every step applies the mean of `n_mean` generator realisations for the current PV
+        (nsteps_decor is not used; the latent noise and the sampler state stay as they are)"""
         p = None
         keep = []
         if generator is not None or forcing is not None:
@@ -430,8 +450,9 @@ class EnsembleEngine:
                 generator.check_size(self.B, self.N)
             if generator is not None and generator not in self._generators:
                 self._generators.append(generator)
-            p.sampling = {'AR1': _lib.SAMPLING_AR1, 'constant': _lib.SAMPLING_CONSTANT}[sampling]
+            p.sampling = self.SAMPLINGS[sampling]
             p.nsteps = int(nsteps_decor)
+            p.n_mean = int(n_mean)
             p.weight = float(weight)
             p.seed = int(seed)
             p.member_offset = int(member_offset)
@@ -451,12 +472,13 @@ class EnsembleEngine:
         if keep:
             torch.cuda.current_stream().synchronize()
 
-    def step_streams(self, generator=None):
+    def step_streams(self, generator=None, sampling='AR1'):
         """1 or 2: the internal streams `step` advances this ensemble on with `generator` attached (qgx_step_streams)"""
         if generator is None:
             return 1
         p = _lib.qgx_param()
         p.gen = generator._h
+        p.sampling = self.SAMPLINGS[sampling]
         return int(lib.qgx_step_streams(self._h, C.byref(p)))
 
     def close(self):

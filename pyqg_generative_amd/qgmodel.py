@@ -212,7 +212,11 @@ class QGModel:
             return None, param, weight
         sampling = getattr(self, 'sampling_type', 'AR1')
         if sampling == 'deterministic':
-            return None, param, weight          # host-driven predict_mean_snapshot path
+            g = gen()
+            if g.kind not in ('gan', 'vae', 'gz'):
+                return None, param, weight      # OLS / ANN: the plugin call raises (no predict_mean_snapshot in the reference)
+            return dict(generator=g, sampling=sampling, n_mean=getattr(self, 'n_mean', 100), weight=weight,
+                        seed=self.seed, member_offset=self.member_offset), param, weight
         nsteps = self.noise_sampler.nsteps
         return dict(generator=gen(), sampling=sampling, nsteps_decor=nsteps, weight=weight,
                     seed=self.seed, member_offset=self.member_offset), param, weight

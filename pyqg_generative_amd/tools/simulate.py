@@ -90,7 +90,8 @@ def snapshot_dataset(m):
 def run_simulation(pyqg_params, parameterization=None, q_init=None, sampling_freq=ANDREW_1000_STEPS,
                    n_members=1, seeds=None, device=0, seed=0, member_offset=0):
     """pyqg_params: dict of model parameters; parameterization: None or
-    dict(self=<Parameterization>, sampling='AR1'|'constant'|'deterministic', nsteps=int);
+    dict(self=<Parameterization>, sampling='AR1'|'constant'|'deterministic', nsteps=int[, M=int: the realisations
+    averaged per step by 'deterministic']);
     q_init: optional PV (nlev,ny,nx) or (B,nlev,ny,nx).  Returns a Dataset of snapshots taken
     every ``sampling_freq`` seconds of model time (reference: simulate.py:109-145)."""
     params = dict(pyqg_params)
@@ -100,6 +101,8 @@ def run_simulation(pyqg_params, parameterization=None, q_init=None, sampling_fre
         m = QGModel(**params, **eng)
     else:
         params['parameterization'] = parameterization['self']
+        if parameterization.get('M') is not None:      # sampling='deterministic': realisations per step (default 100)
+            eng['n_mean'] = int(parameterization['M'])
         m = stochastic_QGModel(params, parameterization['sampling'], parameterization['nsteps'], **eng)
     if q_init is not None:
         m.q = np.asarray(q_init, dtype='float64')

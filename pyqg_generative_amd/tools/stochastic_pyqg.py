@@ -2,7 +2,9 @@
 (reference: pyqg_generative/tools/stochastic_pyqg.py:3-88).
 
 In a fused on-device run the sampler object only carries (kind, nsteps): the update
-z <- a z + b xi and the recompute/skip decision run inside qgx_step.  The host
+z <- a z + b xi and the recompute/skip decision run inside qgx_step; with 'deterministic'
+sampling there is no sampler, only ``n_mean``, and the mean of the realisations runs inside
+qgx_step too.  The host
 ``update`` methods keep the reference's stand-alone behaviour for code that drives a
 parameterization by hand.
 """
@@ -45,9 +47,12 @@ class constant_sampler(noise_time_sampler):
 
 
 class stochastic_QGModel(QGModel):
-    def __init__(self, pyqg_params, sampling_type='AR1', nsteps=1, **engine_kw):
+    def __init__(self, pyqg_params, sampling_type='AR1', nsteps=1, n_mean=100, **engine_kw):
         super().__init__(**pyqg_params, **engine_kw)
         self.sampling_type = sampling_type
+        # 'deterministic': realisations averaged per step, the reference's M = 100 (predict_mean_snapshot); the mean runs
+        # inside qgx_step for the whole ensemble (GAN / VAE / GZ)
+        self.n_mean = int(n_mean)
         if sampling_type == 'AR1':
             self.noise_sampler = AR1_sampler(nsteps)
         elif sampling_type == 'constant':

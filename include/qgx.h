@@ -173,6 +173,24 @@ int qgx_reset_time(qgx_model *m);
  * below the member count is refused by the step).  The library reads NO environment variable. */
 int qgx_set_option(qgx_model *m, const char *name, int value);
 
+/* Molecular viscosity: the Laplace(nu, PV) q-parameterization of the reference's third kind of online run
+ * (--molecular_viscosity, tools/simulate.py:207-236), evaluated inside every step kernel as a term of the spectral
+ * tendency:  pv != 0: dqh_k = -nu K^2 qh_k (nu lap q);  pv == 0: dqh_k = nu K^4 ph_k (nu lap zeta, zeta = lap psi).
+ * nu_host: n_members doubles, one per member (a viscosity sweep is one ensemble), or NULL to switch the term off; an
+ * all-zero array is "on, zero".  Copied into device memory the model owns, behind the work already on `stream` (the call
+ * waits for it: the array is free on return).  A property of the handle, like rek: it is present in every later qgx_step
+ * — p == NULL (256 x 256: such a model takes three launches per step, not the single-launch run kernel, whose registers
+ * have no room for the term; qgx_run_kernel_state stays as it was), forcing_dev, a generator under any sampling, halves
+ * on two streams — is untouched by weight and demean, counts as the parameterization's tendency in the diagnostics
+ * (paramspec, paramspec_APEflux, paramspec_KEflux, ENSparamspec; the tendency of Dissspec / ENSDissspec), may be set
+ * between steps (it takes effect at the next one) and leaves the AB history alone.  With the term off every result is
+ * bitwise what it was without this entry point.  Refused before any device call and with the previous setting still in
+ * force: a plan_only handle (QGX_ERR_STATE), a non-finite or negative nu (QGX_ERR_INVALID). */
+int qgx_set_viscosity(qgx_model *m, const double *nu_host, int pv, void *stream);
+/* nu_host (n_members doubles) and *pv as set; off: zeros and *pv = 0.  Returns the number of members the term is on for
+ * (n_members, or 0 when it is off — which an all-zero array alone would not tell), or a negative qgx_status. */
+int qgx_get_viscosity(const qgx_model *m, double *nu_host, int *pv);
+
 /* status reductions of pyqg's _print_status: out_dev[2*b+0] = KE, [2*b+1] = CFL (of ph,u,v as the last step stored
  * them; after steps with refresh_diag == 0 the current state is inverted first) */
 int qgx_status_ke_cfl(qgx_model *m, double *out_dev, void *stream);

@@ -140,6 +140,8 @@ struct StepArgs {
     double dt1, dt2, dt3;
     double weight;
     int has_S, demean, diag;
+    const double *nu = nullptr;     // molecular viscosity per member (qgx_set_viscosity), null = off; spectral_elem.hpp::visc_add
+    int nu_pv = 0;                  //   != 0: nu lap q, else nu lap zeta
     GenFuse gf;
     // k_step_small PART 3 (forcing and advection workgroups of a (member, layer) in one launch): one word per (member, layer),
     // set to the launch's epoch by the forcing workgroup once the forcing's spectrum is in memory
@@ -150,7 +152,8 @@ struct StepArgs {
 
 // time-averaged diagnostics (diag.hip; the small-grid increment is one kernel of spectral_small.hip)
 struct DiagConst { double del1, del2, rdm2, Udiff, rek, invM2, H0, H1;
-                   double dt1, dt2, dt3, invdt; };       // AB coefficients of the step about to be taken (Dissspec)
+                   double dt1, dt2, dt3, invdt;          // AB coefficients of the step about to be taken (Dissspec)
+                   const double *nu; int nu_pv; };       // molecular viscosity per member or null (StepArgs::nu): part of dqh
 struct DiagAcc { double *KEspec, *Ensspec, *entspec, *APEflux, *KEflux, *APEgenspec, *KEfrictionspec, *paramspec,
                         *paramspec_APEflux, *paramspec_KEflux,
                         *Dissspec, *ENSDissspec, *ENSflux, *ENSgenspec, *ENSfrictionspec, *ENSparamspec; };
@@ -209,6 +212,11 @@ struct qgx_model {
     uint64_t x_ready_step = 0;             //   ... for this noise step
     int64_t tc = 0;
     int ablevel = 0;
+    // molecular viscosity (qgx_set_viscosity): one nu per member in device memory the model owns; a half-ensemble sees its slice
+    double *visc_nu = nullptr;
+    bool visc_on = false;
+    int visc_pv = 0;
+    std::shared_ptr<std::vector<double>> visc_host;
     uint64_t noise_step = 0;
     // time-averaged diagnostics (diag.hip)
     int64_t dg_start = 0, dg_count = 0;

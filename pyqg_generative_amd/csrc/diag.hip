@@ -72,6 +72,13 @@ __global__ void k_diag_accumulate(SpecDev d, DiagConst c, const double2 *qh, con
         const int j = idx / NK, i = idx - j * NK;
         const size_t o = (size_t)b * 2 * sz + idx, o2 = (size_t)b * sz + idx;
         const double2 zero = make_double2(0., 0.);
+        if (c.nu) {      // molecular viscosity: part of the parameterization's tendency (diag_add_visc)
+            double2 s1 = Sh ? Sh[o] : zero, s2 = Sh ? Sh[o + sz] : zero;
+            diag_add_visc(d, c, b, idx, qh[o], qh[o + sz], ph[o], ph[o + sz], s1, s2);
+            diag_accumulate_elem(d, c, a, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], S3[o], S3[o + sz], S4[o], S4[o + sz],
+                                 S5[o], S5[o + sz], true, s1, s2, S6[o], S6[o + sz], S7[o], S7[o + sz], dq_p[o], dq_p[o + sz], dq_pp[o],
+                                 dq_pp[o + sz]);
+        } else
         diag_accumulate_elem(d, c, a, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], S3[o], S3[o + sz], S4[o], S4[o + sz],
                              S5[o], S5[o + sz], Sh != nullptr, Sh ? Sh[o] : zero, Sh ? Sh[o + sz] : zero, S6[o], S6[o + sz], S7[o],
                              S7[o + sz], dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
@@ -128,6 +135,8 @@ int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st)
         else { c.dt1 = 23. / 12. * dt; c.dt2 = -16. / 12. * dt; c.dt3 = 5. / 12. * dt; }
         c.invdt = 1.0 / dt;
     }
+    c.nu = m->visc_on ? m->visc_nu : nullptr;      // the viscous term is part of the parameterization's tendency
+    c.nu_pv = m->visc_pv;
     const double2 *dq_p = m->dq[m->i_new], *dq_pp = m->dq[m->i_p];       // T_{n-1}, T_{n-2}
     DiagAcc a;
     a.KEspec = m->dg_acc[0]; a.Ensspec = m->dg_acc[1]; a.entspec = m->dg_acc[2]; a.APEflux = m->dg_acc[3];

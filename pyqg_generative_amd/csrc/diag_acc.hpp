@@ -2,6 +2,7 @@
 // spectral_small.hip::k_diag_small): the sixteen time-averaged diagnostics, pyqg's 1/M^2 normalisation.
 #pragma once
 #include "common.hpp"
+#include "spectral_elem.hpp"
 
 namespace qgx {
 
@@ -16,6 +17,17 @@ __device__ __forceinline__ double2 diag_jacobian(double kx, double ly, double2 A
     return make_double2(-__builtin_fma(kx, A.y, ly * B.y), __builtin_fma(kx, A.x, ly * B.x));
 }
 __device__ __forceinline__ double diag_dot(double2 a, double bx, double by) { return __builtin_fma(a.x, bx, a.y * by); }
+// Models with molecular viscosity (DiagConst::nu != null): the parameterization's spectral tendency dqh of member b at element
+// idx is weight * S^ (s1, s2 on entry; zero without a forcing) plus the viscous term the step kernels add to the tendency
+// (spectral_elem.hpp::visc_elem).  The callers keep their call of diag_accumulate_elem for models without viscosity exactly
+// as it was, in a branch of its own: its expressions compile to what they always were (paramspec and ENSparamspec moved
+// a last bit when (s1, s2) reached the one call through a select).
+__device__ __forceinline__ void diag_add_visc(const SpecDev &d, const DiagConst &c, int b, int idx, double2 q1, double2 q2, double2 p1,
+                                              double2 p2, double2 &s1, double2 &s2) {
+    const double nu = c.nu[b], wv2 = d.wv2[idx];
+    const double2 v1 = visc_elem(nu, c.nu_pv, wv2, q1, p1), v2 = visc_elem(nu, c.nu_pv, wv2, q2, p2);
+    s1.x += v1.x; s1.y += v1.y; s2.x += v2.x; s2.y += v2.y;
+}
 template <int PARTS = 7, bool JPRE = false>
 __device__ __forceinline__ void diag_accumulate_elem(const SpecDev &d, const DiagConst &c, const DiagAcc &a, int idx, int i, int j,
                                                      size_t o, size_t o2, int sz, double2 q1, double2 q2, double2 p1, double2 p2,

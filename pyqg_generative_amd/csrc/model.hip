@@ -48,6 +48,8 @@ static void step_args_begin(qgx_model *m, int diag, StepArgs &a) {
     a.dq_pp = m->dq[m->i_p];
     a.ph = m->ph; a.u = m->u; a.v = m->v;
     a.diag = diag;
+    a.nu = m->visc_on ? m->visc_nu : nullptr;
+    a.nu_pv = m->visc_pv;
 }
 
 // pre: the first half of this step (k_step_small PART 1) is already in flight on the model's side stream with these
@@ -328,7 +330,7 @@ extern "C" int qgx_destroy(qgx_model *m) {
     (void)hipSetDevice(m->cfg.device);
     void *ptrs[] = {m->t_filtr, m->t_wv2, m->t_a, m->t_kk, m->t_ll, m->t_tw, m->t_pos, m->q, m->u, m->v,
                     m->S, m->qh[0], m->qh[1], m->ph, m->dqh, m->dq[0], m->dq[1], m->dq[2], m->dq[3], m->dg_z, m->zbuf, m->team_ctl,
-                    m->z, m->xi};
+                    m->z, m->xi, m->visc_nu};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (double *p : m->dg_R) if (p) (void)hipFree(p);
     for (double *p : m->dg_S) if (p) (void)hipFree(p);
@@ -475,6 +477,36 @@ extern "C" int qgx_set_option(qgx_model *m, const char *name, int value) {
 extern "C" int64_t qgx_step_count(const qgx_model *m) { return m ? m->tc : -1; }
 extern "C" int qgx_run_kernel_state(const qgx_model *m) { return m ? m->team_state : 0; }
 
+// Laplace(nu, PV) of pyqg_generative/tools/simulate.py:207-225 inside every step (spectral_elem.hpp::visc_add)
+extern "C" int qgx_set_viscosity(qgx_model *m, const double *nu_host, int pv, void *stream) {
+    QGX_NEEDS_STATE(m, "qgx_set_viscosity");
+    QGX_REQUIRE(m, "qgx_set_viscosity: null model");
+    if (nu_host)
+        for (int b = 0; b < m->B; ++b)
+            QGX_REQUIRE(std::isfinite(nu_host[b]) && nu_host[b] >= 0.0, "qgx_set_viscosity: nu of member %d is %g (finite and >= 0 required)",
+                        b, nu_host[b]);
+    hipStream_t st = (hipStream_t)stream;
+    { int trc = team_settle(m, st); if (trc) return trc; }      // a pending run reads the array it was launched with
+    if (!nu_host) { m->visc_on = false; m->visc_pv = 0; return QGX_OK; }
+    if (!m->visc_nu) QGX_HIP(hipMalloc((void **)&m->visc_nu, (size_t)m->B * sizeof(double)));
+    // ordered behind the steps already enqueued on `stream`; the caller's array is free on return
+    auto host = std::make_shared<std::vector<double>>(nu_host, nu_host + m->B);
+    QGX_HIP(hipMemcpyAsync(m->visc_nu, host->data(), (size_t)m->B * sizeof(double), hipMemcpyHostToDevice, st));
+    QGX_HIP(hipStreamSynchronize(st));
+    m->visc_host = host;
+    m->visc_on = true;
+    m->visc_pv = pv ? 1 : 0;
+    return QGX_OK;
+}
+
+extern "C" int qgx_get_viscosity(const qgx_model *m, double *nu_host, int *pv) {
+    QGX_REQUIRE(m && nu_host && pv, "qgx_get_viscosity: null argument");
+    const bool on = m->visc_on && m->visc_host;
+    for (int b = 0; b < m->B; ++b) nu_host[b] = on ? (*m->visc_host)[b] : 0.0;
+    *pv = on ? m->visc_pv : 0;
+    return on ? m->B : 0;
+}
+
 extern "C" int qgx_reset_time(qgx_model *m) {
     QGX_NEEDS_STATE(m, "qgx_reset_time");
     QGX_REQUIRE(m, "qgx_reset_time: null model");
@@ -555,7 +587,9 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
     // OLS (generate_latent_noise returns 0, ols_model.py:65-66): the sampler only decides when the forcing is recomputed —
     // AR1 on every step, constant on steps 1, n+1, 2n+1, ... (stochastic_pyqg.py:30-72) — with no draw and no write to z
     const bool noisy = p && p->gen && generator_takes_noise(p->gen);
-    const bool plain = !(p && (p->gen || p->forcing_dev));
+    // (a model with molecular viscosity steps on the three-launch path at 256 x 256 as well: the run kernel holds a member's
+    // state in all 256 registers of its waves, and its instance with the viscous term spilled — DESIGN.md section 3.12)
+    const bool plain = !(p && (p->gen || p->forcing_dev)) && !m->visc_on;
     const bool fuse_ok = m->opts.genfuse != 0;
     m->x_ready_gen = nullptr;                                            // an assembled input never outlives its call
     for (int s = 0; s < nsteps; ++s) {
@@ -790,6 +824,7 @@ extern "C" int qgx_step(qgx_model *m, int nsteps, const qgx_param *p, int refres
         k.sub_stream[0] = k.sub_stream[1] = nullptr;
         k.adv_slot = c;
         k.is_half = true;
+        if (k.visc_nu) k.visc_nu += b0;                 // (one nu per member)
         if (k.sib_flag) k.sib_flag += b0 * 4;          // (a half owns the flag words and the placement words of its members: 4 per member)
         pp[c].member_offset = p->member_offset + b0;
     }

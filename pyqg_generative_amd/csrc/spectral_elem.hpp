@@ -56,6 +56,25 @@ __device__ __forceinline__ double2 tendency_elem(int k, double kx, double ly, do
     return make_double2(tx, ty);
 }
 
+// Molecular viscosity, the Laplace(nu, PV) q-parameterization of pyqg_generative/tools/simulate.py:207-225, per spectral
+// element: dqh_k = c src with  PV: c = -nu K^2, src = qh_k (nu lap q);  else: c = nu K^4, src = ph_k (nu lap zeta,
+// zeta = lap psi, lap = (ik)^2 + (il)^2 = -K^2).  The coefficient is a chain of single products, so there is nothing for
+// the compiler to contract differently from kernel to kernel.
+__device__ __forceinline__ double visc_coef(double nu, int pv, double wv2) { return pv ? -(nu * wv2) : (nu * wv2) * wv2; }
+// the term itself (diagnostics: the parameterization's tendency, pyqg's dqh)
+__device__ __forceinline__ double2 visc_elem(double nu, int pv, double wv2, double2 qh_k, double2 ph_k) {
+    const double c = visc_coef(nu, pv, wv2);
+    const double2 s = pv ? qh_k : ph_k;
+    return make_double2(c * s.x, c * s.y);
+}
+// the tendency with the term added (after tendency_elem and after the forcing): one explicit fused multiply-add per
+// component, the same rounding in every kernel whatever surrounds the call
+__device__ __forceinline__ double2 visc_add(double2 t, double nu, int pv, double wv2, double2 qh_k, double2 ph_k) {
+    const double c = visc_coef(nu, pv, wv2);
+    const double2 s = pv ? qh_k : ph_k;
+    return make_double2(__builtin_fma(c, s.x, t.x), __builtin_fma(c, s.y, t.y));
+}
+
 // third-order Adams-Bashforth step of one element with the exponential filter f
 __device__ __forceinline__ double2 ab3_filter(double f, double2 qk, double2 t, double2 p, double2 pp, double dt1, double dt2, double dt3) {
     return make_double2(f * (qk.x + dt1 * t.x + dt2 * p.x + dt3 * pp.x), f * (qk.y + dt1 * t.y + dt2 * p.y + dt3 * pp.y));

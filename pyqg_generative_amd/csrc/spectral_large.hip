@@ -174,6 +174,7 @@ __global__ void k_l_tendency(SpecDev d, StepArgs a, const double2 *zbuf) {
             double2 t = tendency_elem(k, kx, ly, d.Qy[k], d.rek, d.wv2 + idx, uqh, vqh, ph);
             const size_t o = (size_t)b * 2 * sz + k * sz + idx;
             if (a.has_S) { const double2 s = a.dqh[o]; t.x += s.x; t.y += s.y; }
+            if (a.nu) t = visc_add(t, a.nu[b], a.nu_pv, d.wv2[idx], k == 0 ? q0 : q1, ph);
             const double2 p = a.dq_p[o], pp = a.dq_pp[o];
             const double f = d.filtr[idx];
             a.dq_new[o] = t;
@@ -475,6 +476,7 @@ __global__ __launch_bounds__(NT > 0 ? NT : 1024) void k_l_rows_fwd_tend(SpecDev 
             double2 tn = tendency_elem(k, kx, ly, d.Qy[k], d.rek, d.wv2 + idx, uqh, vqh, ph);
             const double2 s = k == 0 ? s0 : s1;
             tn.x += s.x; tn.y += s.y;
+            if (a.nu) tn = visc_add(tn, a.nu[b], a.nu_pv, d.wv2[idx], k == 0 ? q0 : q1, ph);
             const size_t o = (size_t)b * 2 * sz + k * sz + idx;
             const double2 p = a.dq_p[o], pp = a.dq_pp[o];
             const double f = d.filtr[idx];
@@ -576,6 +578,12 @@ __global__ __launch_bounds__(NT) void k_l_rows_diag_acc(SpecDev d, DiagConst c, 
         const double2 A5 = make_double2(A[1].x - F2 * A[3].x, A[1].y - F2 * A[3].y), B5 = make_double2(Bv[1].x - F2 * Bv[3].x, Bv[1].y - F2 * Bv[3].y);
         const size_t o = (size_t)b * 2 * sz + idx, o2 = (size_t)b * sz + idx;
         const double2 zero = make_double2(0., 0.);
+        if (c.nu) {      // molecular viscosity: part of the parameterization's tendency (diag_add_visc)
+            double2 s1 = Sh ? Sh[o] : zero, s2 = Sh ? Sh[o + sz] : zero;
+            diag_add_visc(d, c, b, idx, qh[o], qh[o + sz], ph[o], ph[o + sz], s1, s2);
+            diag_accumulate_elem(d, c, acc, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], A3, B3, A4, B4, A5, B5, true,
+                                 s1, s2, A[0], Bv[0], A[1], Bv[1], dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
+        } else
         diag_accumulate_elem(d, c, acc, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], A3, B3, A4, B4, A5, B5, Sh != nullptr,
                              Sh ? Sh[o] : zero, Sh ? Sh[o + sz] : zero, A[0], Bv[0], A[1], Bv[1], dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
     }

@@ -335,10 +335,12 @@ __global__ void k_step_small(SpecDev d, StepArgs a) {
             const size_t o = so + k * sz + idx;
             const double2 q0 = qh0[idx], q1 = qh1[idx];
             double tx, ty;
+            double2 phk = make_double2(0., 0.);      // psi_k of this element, for the viscous term
             if constexpr (PART != 2) {
                 double2 uqh, vqh;
                 unpack_pair(Z, g, j, i, uqh, vqh);
                 const double2 ph = invert_layer(d, k, idx, q0, q1);
+                phk = ph;
                 const double2 t = tendency_elem(k, d.kk[i], d.ll[j], d.Qy[k], d.rek, d.wv2 + idx, uqh, vqh, ph);
                 tx = t.x; ty = t.y;
             } else {
@@ -353,8 +355,13 @@ __global__ void k_step_small(SpecDev d, StepArgs a) {
                     tx += s.x;
                     ty += s.y;
                 }
-                const double2 p = a.dq_p[o], pp = a.dq_pp[o];
                 const double2 qk = k == 0 ? q0 : q1;
+                if (a.nu) {      // molecular viscosity (workgroup-uniform branch)
+                    if constexpr (PART == 2) phk = invert_layer(d, k, idx, q0, q1);      // (half 1 kept the tendency, not psi)
+                    const double2 t = visc_add(make_double2(tx, ty), a.nu[b], a.nu_pv, d.wv2[idx], qk, phk);
+                    tx = t.x; ty = t.y;
+                }
+                const double2 p = a.dq_p[o], pp = a.dq_pp[o];
                 const double f = d.filtr[idx];
                 a.dq_new[o] = make_double2(tx, ty);
                 double2 qn = ab3_filter(f, qk, make_double2(tx, ty), p, pp, a.dt1, a.dt2, a.dt3);
@@ -593,6 +600,13 @@ __global__ void k_diag_small(SpecDev d, DiagConst c, const double2 *qh, double2 
         const int j = idx / NK, i = idx - j * NK;
         const size_t o = so + idx, o2 = (size_t)b * sz + idx;
         const double2 zero = make_double2(0., 0.);
+        if (c.nu) {      // molecular viscosity: part of the parameterization's tendency (diag_add_visc)
+            double2 s1 = S ? Sh[o] : zero, s2 = S ? Sh[o + sz] : zero;
+            diag_add_visc(d, c, b, idx, qh[o], qh[o + sz], ph[o], ph[o + sz], s1, s2);
+            diag_accumulate_elem(d, c, acc, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], S3[o], S3[o + sz], S4[o], S4[o + sz],
+                                 S5[o], S5[o + sz], true, s1, s2, S6[o], S6[o + sz], S7[o], S7[o + sz],
+                                 dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
+        } else
         diag_accumulate_elem(d, c, acc, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], S3[o], S3[o + sz], S4[o], S4[o + sz],
                              S5[o], S5[o + sz], S != nullptr, S ? Sh[o] : zero, S ? Sh[o + sz] : zero, S6[o], S6[o + sz], S7[o], S7[o + sz],
                              dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
@@ -812,6 +826,12 @@ __global__ __launch_bounds__(1024) void k_diag_small_reg(SpecDev d, DiagConst c,
             const double2 q1 = qh0[idx], q2 = qh1[idx];
             const double2 p1 = ph0[idx], p2 = ph1[idx];
             const size_t o = so + idx;
+            if (c.nu) {      // molecular viscosity: part of the parameterization's tendency (diag_add_visc)
+                double2 s1 = S ? SH[idx] : zero, s2 = S ? SH[sz + idx] : zero;
+                diag_add_visc(d, c, b, idx, q1, q2, p1, p2, s1, s2);
+                diag_accumulate_elem<4, true>(d, c, acc, idx, i, j, o, (size_t)b * sz + idx, sz, q1, q2, p1, p2, zero, zero, zero, zero, zero, zero,
+                                              true, s1, s2, G1[r], zero, A7, B7, dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
+            } else
             diag_accumulate_elem<4, true>(d, c, acc, idx, i, j, o, (size_t)b * sz + idx, sz, q1, q2, p1, p2, zero, zero, zero, zero, zero, zero,
                                           S != nullptr, S ? SH[idx] : zero, S ? SH[sz + idx] : zero, G1[r], zero, A7, B7, dq_p[o], dq_p[o + sz],
                                           dq_pp[o], dq_pp[o + sz]);

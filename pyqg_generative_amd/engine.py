@@ -331,6 +331,7 @@ class EnsembleEngine:
         self.device = torch.device('cuda', device)
         self._h = C.c_void_p(0)
         self._generators = []           # generators used by step(): their range guard is read at status time
+        self.step_calls = 0             # qgx_step calls made through step() (a fused run makes few, a host plug-in one per step)
         check(lib.qgx_create(C.byref(cfg), C.byref(self._h)))
 
     # ---- tables -------------------------------------------------------------------
@@ -397,6 +398,32 @@ class EnsembleEngine:
     def set_option(self, name, value):
         """kernel-path switch of this model (include/qgx.h::qgx_set_option): same results, different fusion / tiling"""
         check(lib.qgx_set_option(self._h, name.encode(), int(value)))
+
+    # ---- molecular viscosity (the reference's Laplace(nu, PV), tools/simulate.py:207-225) ----
+    def set_viscosity(self, nu, PV=False):
+        """nu lap zeta (PV=False) or nu lap q (PV=True) as a term of every later step's tendency, evaluated inside the step
+        kernels (qgx_set_viscosity).  nu: a scalar for all members, or one value per member (a viscosity sweep is one
+        ensemble); None switches the term off.  Takes effect at the next step; the AB history is kept."""
+        if nu is None:
+            check(lib.qgx_set_viscosity(self._h, None, 0, _stream()))
+            return
+        a = np.asarray(nu, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(self.B, float(a))
+        if a.shape != (self.B,):
+            raise ValueError(f'nu must be a scalar or one value per member ({self.B}), got shape {a.shape}')
+        a = np.ascontiguousarray(a)
+        check(lib.qgx_set_viscosity(self._h, a.ctypes.data_as(C.POINTER(C.c_double)), int(bool(PV)), _stream()))
+
+    @property
+    def viscosity(self):
+        """None while the term is off, else (nu per member as a numpy array, PV)"""
+        a = np.zeros(self.B, dtype=np.float64)
+        pv = C.c_int(0)
+        n = lib.qgx_get_viscosity(self._h, a.ctypes.data_as(C.POINTER(C.c_double)), C.byref(pv))
+        if n < 0:
+            check(n)
+        return (a, bool(pv.value)) if n > 0 else None
 
     def status(self):
         """-> (KE[B], CFL[B]) as pyqg's _print_status computes them (from the last inversion)."""
@@ -469,6 +496,7 @@ class EnsembleEngine:
             p.demean = int(bool(demean))
         check(lib.qgx_step(self._h, int(nsteps), C.byref(p) if p is not None else None,
                            int(bool(refresh_diag)), _stream()))
+        self.step_calls += 1
         if keep:
             torch.cuda.current_stream().synchronize()
 

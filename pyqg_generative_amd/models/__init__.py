@@ -4,5 +4,6 @@ from .cvae_regression import CVAERegression
 from .mean_var_model import MeanVarModel
 from .ols_model import OLSModel
 from .ann_model import ANNModel
+from .laplace import Laplace
 
-__all__ = ['Parameterization', 'CGANRegression', 'CVAERegression', 'MeanVarModel', 'OLSModel', 'ANNModel']
+__all__ = ['Parameterization', 'CGANRegression', 'CVAERegression', 'MeanVarModel', 'OLSModel', 'ANNModel', 'Laplace']

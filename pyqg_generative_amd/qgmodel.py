@@ -76,6 +76,7 @@ class QGModel:
         self._eng = EnsembleEngine(nx=nx, n_members=n_members, device=device, L=L, dt=dt, rek=rek,
                                    delta=delta, beta=beta, rd=rd, U1=U1, U2=U2, H1=H1,
                                    filterfac=filterfac)
+        self._visc_key = None             # what the engine's molecular viscosity was last set from (_fused_viscosity)
         self._init_grid()
         self.t = 0.
         self.taveints = math.ceil(self.taveint / self.dt)
@@ -221,16 +222,37 @@ class QGModel:
         return dict(generator=gen(), sampling=sampling, nsteps_decor=nsteps, weight=weight,
                     seed=self.seed, member_offset=self.member_offset), param, weight
 
+    def _fused_viscosity(self):
+        """A (possibly weighted) models.Laplace with its fused switch on is not a plug-in to call: (nu, PV) go to the engine
+        once — again only if the attached object, its weight or its nu changes — and the step kernels evaluate the term.
+        -> whether the attached parameterization is such a one."""
+        from .models.laplace import Laplace
+        param, weight = _unwrap(self.q_parameterization)
+        if isinstance(param, Laplace) and param.fused:
+            nu = np.asarray(param.nu, dtype='float64') * weight
+            key = (id(param), bool(param.PV), nu.tobytes())
+            if key != self._visc_key:
+                self._eng.set_viscosity(nu if nu.ndim else float(nu), PV=param.PV)
+                self._visc_key = key
+            return True
+        if self._visc_key is not None:       # the Laplace was detached: the term goes with it
+            self._eng.set_viscosity(None)
+            self._visc_key = None
+        return False
+
     def _advance(self, n, refresh_diag=True):
         if n <= 0:
             return
-        if self.q_parameterization is None:
+        if self._fused_viscosity() or self.q_parameterization is None:
             self._eng.step(n, refresh_diag=refresh_diag)
         else:
             kw, param, weight = self._step_kwargs()
             if kw is not None:               # fused on-device plugin
                 self._eng.step(n, refresh_diag=refresh_diag, **kw)
             else:                            # generic pyqg plugin: one host call per step
+                # (pyqg calls the plug-in behind _invert: ph, u, v it reads are those of the current state — the last
+                # step of the previous call stored the ones of the state before it)
+                self._eng.invert()
                 for s in range(n):
                     dq = np.asarray(param(self), dtype='float64')
                     f = torch.as_tensor(self._bcast(dq, (2, self.ny, self.nx))).to(self._eng.device)

@@ -92,6 +92,8 @@ def run_simulation(pyqg_params, parameterization=None, q_init=None, sampling_fre
     """pyqg_params: dict of model parameters; parameterization: None or
     dict(self=<Parameterization>, sampling='AR1'|'constant'|'deterministic', nsteps=int[, M=int: the realisations
     averaged per step by 'deterministic']);
+    pyqg_params may carry a q-parameterization object of its own under 'parameterization', the reference's spelling of
+    the molecular-viscosity run (simulate.py:229-234: a models.Laplace, which then runs inside the step kernels).
     q_init: optional PV (nlev,ny,nx) or (B,nlev,ny,nx).  Returns a Dataset of snapshots taken
     every ``sampling_freq`` seconds of model time (reference: simulate.py:109-145)."""
     params = dict(pyqg_params)
@@ -117,6 +119,19 @@ def run_simulation(pyqg_params, parameterization=None, q_init=None, sampling_fre
     ds.attrs['pyqg_params'] = str(pyqg_params)
     m.close()
     return ds
+
+
+def run_molecular_viscosity(pyqg_params, sampling_freq=ANDREW_1000_STEPS, n_members=1, seeds=None, device=0, PV=False):
+    """The reference's molecular-viscosity run (simulate.py:227-236): ``pyqg_params['nu']`` — a scalar, or one value per
+    member: a viscosity sweep as one ensemble — becomes a ``Laplace(nu, PV)`` q-parameterization and the exponential filter
+    a sharp cut-off (filterfac = 1e20, '2/3 dealiasing'); then run_simulation.  The viscous term runs inside the step
+    kernels (models/laplace.py).  The dataset's 'pyqg_params' attribute is, as in the reference, the dictionary the run
+    was made with: 'nu' taken out, 'parameterization' and 'filterfac' put in."""
+    from ..models.laplace import Laplace
+    params = dict(pyqg_params)
+    params['parameterization'] = Laplace(params.pop('nu'), PV)
+    params['filterfac'] = 1e+20
+    return run_simulation(params, sampling_freq=sampling_freq, n_members=n_members, seeds=seeds, device=device)
 
 
 def generate_subgrid_forcing(Nc, pyqg_params, sampling_freq=ANDREW_1000_STEPS, n_members=1, seeds=None,

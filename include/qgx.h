@@ -191,6 +191,27 @@ int qgx_set_viscosity(qgx_model *m, const double *nu_host, int pv, void *stream)
  * (n_members, or 0 when it is off — which an all-zero array alone would not tell), or a negative qgx_status. */
 int qgx_get_viscosity(const qgx_model *m, double *nu_host, int *pv);
 
+/* The Jansen-Held backscatter closure, pyqg 0.7.2 parameterizations.py::BackscatterBiharmonic(smag_constant, back_constant,
+ * eps) — the reference's physical parameterizations (models/physical_parameterizations.py: BackscatterEddy =
+ * (sqrt(0.007), 1.2), BackscatterJet = (sqrt(0.005), 0.8), run by tools/simulate.py:243-244) — evaluated on the device from
+ * the current qh:  dq = D - C_B R lap lap psi,  D = -lap(lap lap psi dx^2 nu_Smagorinsky(C_S)),  R = sum_k H_k <psi_k D_k> /
+ * (sum_k H_k <psi_k lap lap psi_k> + eps), one R per member.  smag_host, back_host: n_members doubles each (a (C_S, C_B)
+ * sweep is one ensemble); smag_host == NULL switches the closure off.  A property of the handle: while it is on, every
+ * step of qgx_step with p == NULL recomputes S (QGX_F_S) from the state and steps with it (weight 1, no de-mean; 256 x 256:
+ * three launches per step, qgx_run_kernel_state stays as it was); it counts as the parameterization's tendency in the
+ * diagnostics and composes with qgx_set_viscosity.  A member's result is bitwise the same in any ensemble (fixed-order
+ * reductions, no atomics).  With the closure off every result is bitwise what it was without this entry point.  Refused
+ * before any launch and with the previous setting in force: a plan_only handle (QGX_ERR_STATE); a non-finite or negative
+ * C_S, a non-finite C_B, eps < 0 (QGX_ERR_INVALID); qgx_step with a generator or forcing_dev while the closure is on
+ * (pyqg has one q-parameterization slot). */
+int qgx_set_backscatter(qgx_model *m, const double *smag_host, const double *back_host, double eps, void *stream);
+/* the constants as set (off: zeros).  Returns the number of members the closure is on for (n_members or 0), or a
+ * negative qgx_status. */
+int qgx_get_backscatter(const qgx_model *m, double *smag_host, double *back_host, double *eps);
+/* The closure of the current state into caller buffers: S_dev (n_members,2,N,N) doubles, ratio_dev (n_members) doubles
+ * (R) or NULL.  Changes no state; the closure must be on. */
+int qgx_backscatter_forcing(qgx_model *m, double *S_dev, double *ratio_dev, void *stream);
+
 /* status reductions of pyqg's _print_status: out_dev[2*b+0] = KE, [2*b+1] = CFL (of ph,u,v as the last step stored
  * them; after steps with refresh_diag == 0 the current state is inverted first) */
 int qgx_status_ke_cfl(qgx_model *m, double *out_dev, void *stream);

@@ -88,6 +88,9 @@ SYMBOLS = [
     ('qgx_set_option', C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ('qgx_set_viscosity', C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_void_p]),
     ('qgx_get_viscosity', C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ('qgx_set_backscatter', C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_void_p]),
+    ('qgx_get_backscatter', C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ('qgx_backscatter_forcing', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('qgx_status_ke_cfl', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ('qgx_diag_config', C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
     ('qgx_diag_get', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -217,6 +217,14 @@ struct qgx_model {
     bool visc_on = false;
     int visc_pv = 0;
     std::shared_ptr<std::vector<double>> visc_host;
+    // Jansen-Held backscatter closure (qgx_set_backscatter, backscatter.hip): C_S then C_B, one each per member, in device
+    // memory the model owns; the work fields of the large-grid path (three spectral, three real)
+    double *bs_const = nullptr;
+    bool bs_on = false;
+    double bs_eps = 0.0;
+    std::shared_ptr<std::vector<double>> bs_host;
+    double2 *bs_spec[3] = {nullptr, nullptr, nullptr};
+    double *bs_real[3] = {nullptr, nullptr, nullptr};
     uint64_t noise_step = 0;
     // time-averaged diagnostics (diag.hip)
     int64_t dg_start = 0, dg_count = 0;
@@ -268,6 +276,10 @@ int small_step(const SpecDev &d, const ModelOpts &o, const StepArgs &a, hipStrea
 int small_q_to_qh(const SpecDev &d, const ModelOpts &o, const double *q, double2 *qh, hipStream_t st);
 int small_qh_to_q(const SpecDev &d, const ModelOpts &o, const double2 *qh, double *q, hipStream_t st);
 int small_invert(const SpecDev &d, const ModelOpts &o, const double2 *qh, double2 *ph, double *u, double *v, hipStream_t st);
+
+// backscatter.hip: kernel attributes / work fields of the closure; S (B,2,N,N) [and R (B)] of the state qh
+int backscatter_prepare(qgx_model *m);
+int backscatter_eval(qgx_model *m, const double2 *qh, double *S, double *ratio, hipStream_t st);
 
 bool generator_noise_is_double(const qgx_generator *g);
 bool generator_takes_noise(const qgx_generator *g);     // false for OLS and ANN: no latent noise at all

@@ -66,9 +66,12 @@ static int model_step_once(qgx_model *m, bool has_S, const double *S, double wei
     if (pre) {
         QGX_HIP(hipStreamWaitEvent(st, m->adv_event[m->adv_slot][1], 0));
         rc = small_step(m->d, m->opts, a, st, 2);
-    } else if (m->small && has_S && m->sib_flag && m->opts.siblings != 0 && small_layer_split(m->d, m->opts) &&
+    } else if (m->small && has_S && !m->bs_on && m->sib_flag && m->opts.siblings != 0 && small_layer_split(m->d, m->opts) &&
                (m->opts.siblings >= 1 || 4 * m->B * (m->is_half ? 2 : 1) <= 256)) {   // (two halves run side by side: both must fit)    // while all four workgroups of every member are resident at once
-        // the forcing's transform on a workgroup of its own beside the inversion / advection chain (k_step_small PART 3)
+        // the forcing's transform on a workgroup of its own beside the inversion / advection chain (k_step_small PART 3).
+        // Not for the backscatter closure: the flag words exist only once a generator or forcing step has been made on this
+        // handle, and which kernel form a closure step takes must not depend on that history (the form was measured for
+        // generator steps, DESIGN 3.1d, not for the closure)
         a.sib_flag = m->sib_flag;
         a.sib_epoch = ++m->sib_epoch;
         a.sib_full = m->opts.siblings == 2;
@@ -330,7 +333,8 @@ extern "C" int qgx_destroy(qgx_model *m) {
     (void)hipSetDevice(m->cfg.device);
     void *ptrs[] = {m->t_filtr, m->t_wv2, m->t_a, m->t_kk, m->t_ll, m->t_tw, m->t_pos, m->q, m->u, m->v,
                     m->S, m->qh[0], m->qh[1], m->ph, m->dqh, m->dq[0], m->dq[1], m->dq[2], m->dq[3], m->dg_z, m->zbuf, m->team_ctl,
-                    m->z, m->xi, m->visc_nu};
+                    m->z, m->xi, m->visc_nu, m->bs_const, m->bs_spec[0], m->bs_spec[1], m->bs_spec[2],
+                    m->bs_real[0], m->bs_real[1], m->bs_real[2]};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (double *p : m->dg_R) if (p) (void)hipFree(p);
     for (double *p : m->dg_S) if (p) (void)hipFree(p);
@@ -507,6 +511,54 @@ extern "C" int qgx_get_viscosity(const qgx_model *m, double *nu_host, int *pv) {
     return on ? m->B : 0;
 }
 
+// The Jansen-Held backscatter closure (backscatter.hip): pyqg's BackscatterBiharmonic(C_S, C_B) per member
+extern "C" int qgx_set_backscatter(qgx_model *m, const double *smag_host, const double *back_host, double eps, void *stream) {
+    QGX_NEEDS_STATE(m, "qgx_set_backscatter");
+    QGX_REQUIRE(m, "qgx_set_backscatter: null model");
+    if (smag_host) {
+        QGX_REQUIRE(back_host, "qgx_set_backscatter: smag_host without back_host");
+        QGX_REQUIRE(eps >= 0.0 && std::isfinite(eps), "qgx_set_backscatter: eps is %g (finite and >= 0 required)", eps);
+        for (int b = 0; b < m->B; ++b) {
+            QGX_REQUIRE(std::isfinite(smag_host[b]) && smag_host[b] >= 0.0,
+                        "qgx_set_backscatter: C_S of member %d is %g (finite and >= 0 required)", b, smag_host[b]);
+            QGX_REQUIRE(std::isfinite(back_host[b]), "qgx_set_backscatter: C_B of member %d is %g (finite required)", b, back_host[b]);
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    { int trc = team_settle(m, st); if (trc) return trc; }
+    if (!smag_host) { m->bs_on = false; return QGX_OK; }
+    if (!m->bs_const) QGX_HIP(hipMalloc((void **)&m->bs_const, (size_t)2 * m->B * sizeof(double)));
+    { int prc = backscatter_prepare(m); if (prc) return prc; }
+    // ordered behind the steps already enqueued on `stream`; the caller's arrays are free on return
+    auto host = std::make_shared<std::vector<double>>(smag_host, smag_host + m->B);
+    host->insert(host->end(), back_host, back_host + m->B);
+    QGX_HIP(hipMemcpyAsync(m->bs_const, host->data(), (size_t)2 * m->B * sizeof(double), hipMemcpyHostToDevice, st));
+    QGX_HIP(hipStreamSynchronize(st));
+    m->bs_host = host;
+    m->bs_eps = eps;
+    m->bs_on = true;
+    return QGX_OK;
+}
+
+extern "C" int qgx_get_backscatter(const qgx_model *m, double *smag_host, double *back_host, double *eps) {
+    QGX_REQUIRE(m && smag_host && back_host && eps, "qgx_get_backscatter: null argument");
+    const bool on = m->bs_on && m->bs_host;
+    for (int b = 0; b < m->B; ++b) {
+        smag_host[b] = on ? (*m->bs_host)[b] : 0.0;
+        back_host[b] = on ? (*m->bs_host)[m->B + b] : 0.0;
+    }
+    *eps = on ? m->bs_eps : 0.0;
+    return on ? m->B : 0;
+}
+
+extern "C" int qgx_backscatter_forcing(qgx_model *m, double *S_dev, double *ratio_dev, void *stream) {
+    QGX_NEEDS_STATE(m, "qgx_backscatter_forcing");
+    QGX_REQUIRE(m && S_dev, "qgx_backscatter_forcing: null argument");
+    QGX_REQUIRE(m->bs_on, "qgx_backscatter_forcing: the closure is off (qgx_set_backscatter)");
+    { int trc = team_settle(m, (hipStream_t)stream); if (trc) return trc; }
+    return backscatter_eval(m, m->qh[m->cur_q], S_dev, ratio_dev, (hipStream_t)stream);
+}
+
 extern "C" int qgx_reset_time(qgx_model *m) {
     QGX_NEEDS_STATE(m, "qgx_reset_time");
     QGX_REQUIRE(m, "qgx_reset_time: null model");
@@ -589,7 +641,8 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
     const bool noisy = p && p->gen && generator_takes_noise(p->gen);
     // (a model with molecular viscosity steps on the three-launch path at 256 x 256 as well: the run kernel holds a member's
     // state in all 256 registers of its waves, and its instance with the viscous term spilled — DESIGN.md section 3.12)
-    const bool plain = !(p && (p->gen || p->forcing_dev)) && !m->visc_on;
+    // (so does a model with the backscatter closure: its forcing is recomputed from the state on every step)
+    const bool plain = !(p && (p->gen || p->forcing_dev)) && !m->visc_on && !m->bs_on;
     const bool fuse_ok = m->opts.genfuse != 0;
     m->x_ready_gen = nullptr;                                            // an assembled input never outlives its call
     for (int s = 0; s < nsteps; ++s) {
@@ -727,6 +780,13 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
             S = p->forcing_dev;
             weight = p->weight;
             demean_in_kernel = p->demean;
+        } else if (m->bs_on) {
+            // the backscatter closure of the current state (pyqg calls a q-parameterization behind _invert): weight 1, and no
+            // de-mean — its spectrum has no (0, 0) element
+            int rc = backscatter_eval(m, m->qh[m->cur_q], m->S, nullptr, st);
+            if (rc) return rc;
+            has_S = true;
+            S = m->S;
         }
         // model.py::_calc_diagnostics: t >= dt, t >= tavestart, tc % taveints == 0 (before the time step)
         if (m->dg_every > 0 && m->tc >= 1 && m->tc >= m->dg_start && m->tc % m->dg_every == 0) {
@@ -772,6 +832,9 @@ extern "C" int qgx_step_streams(const qgx_model *m, const qgx_param *p) {
 extern "C" int qgx_step(qgx_model *m, int nsteps, const qgx_param *p, int refresh_diag, void *stream) {
     QGX_NEEDS_STATE(m, "qgx_step");
     QGX_REQUIRE(m && nsteps >= 0, "qgx_step: bad argument");
+    // pyqg has one q-parameterization slot: refused before anything is launched or changed
+    QGX_REQUIRE(!(m->bs_on && p && (p->gen || p->forcing_dev)),
+                "qgx_step: the backscatter closure is on (qgx_set_backscatter): a generator or forcing_dev cannot be stepped with it");
     hipStream_t st = (hipStream_t)stream;
     // a grid the generator's kernels do not take is refused here: before any launch, and before step_core touches the
     // sampler state (the halves of an ensemble stepped on two streams ask the kernels for B / 2 members)

@@ -425,6 +425,47 @@ class EnsembleEngine:
             check(n)
         return (a, bool(pv.value)) if n > 0 else None
 
+    # ---- Jansen-Held backscatter closure (pyqg's BackscatterBiharmonic; the reference's physical parameterizations) ----
+    def _per_member(self, x, name):
+        a = np.asarray(x, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(self.B, float(a))
+        if a.shape != (self.B,):
+            raise ValueError(f'{name} must be a scalar or one value per member ({self.B}), got shape {a.shape}')
+        return np.ascontiguousarray(a)
+
+    def set_backscatter(self, smag, back=None, eps=1e-32):
+        """BackscatterBiharmonic(smag, back, eps) as the q-parameterization of every later plain step, evaluated on the
+        device from the current state (qgx_set_backscatter).  smag, back: scalars for all members, or one value per member
+        (a (C_S, C_B) sweep is one ensemble); smag None switches the closure off.  Takes effect at the next step."""
+        if smag is None:
+            check(lib.qgx_set_backscatter(self._h, None, None, 0.0, _stream()))
+            return
+        if back is None:
+            raise ValueError('set_backscatter needs back_constant with smag_constant')
+        cs, cb = self._per_member(smag, 'smag'), self._per_member(back, 'back')
+        dp = C.POINTER(C.c_double)
+        check(lib.qgx_set_backscatter(self._h, cs.ctypes.data_as(dp), cb.ctypes.data_as(dp), float(eps), _stream()))
+
+    @property
+    def backscatter(self):
+        """None while the closure is off, else (smag per member, back per member, eps)"""
+        cs, cb = np.zeros(self.B, dtype=np.float64), np.zeros(self.B, dtype=np.float64)
+        eps = C.c_double(0.0)
+        dp = C.POINTER(C.c_double)
+        n = lib.qgx_get_backscatter(self._h, cs.ctypes.data_as(dp), cb.ctypes.data_as(dp), C.byref(eps))
+        if n < 0:
+            check(n)
+        return (cs, cb, eps.value) if n > 0 else None
+
+    def backscatter_forcing(self, ratio=False):
+        """The closure of the current state: S (B,2,N,N) float64 device tensor; ratio=True: (S, R) with the energy ratio
+        R (B).  Changes no state (qgx_backscatter_forcing)."""
+        S = self._real()
+        R = torch.empty((self.B,), dtype=torch.float64, device=self.device) if ratio else None
+        check(lib.qgx_backscatter_forcing(self._h, _ptr(S), _ptr(R), _stream()))
+        return (S, R) if ratio else S
+
     def status(self):
         """-> (KE[B], CFL[B]) as pyqg's _print_status computes them (from the last inversion)."""
         out = torch.empty((self.B, 2), dtype=torch.float64, device=self.device)

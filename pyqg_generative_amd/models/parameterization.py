@@ -92,7 +92,7 @@ class Parameterization(QParameterization):
                 raise ValueError(f'test_offline needs {name!r} in the dataset')
         check_fields(*(_values(ds[name]) for name in ('q', 'q_forcing_advection', 'psi')))
         preds = self.predict(ds, ensemble_size, **predict_kwargs)
-        return offline_dataset(ds, preds, device=self._gen.device if hasattr(self._gen, 'device') else 0)
+        return offline_dataset(ds, preds, device=getattr(getattr(self, '_gen', None), 'device', 0))      # (a physical parameterization has no network)
 
     def __call__(self, m):
         if m.sampling_type == 'deterministic':

@@ -77,6 +77,7 @@ class QGModel:
                                    delta=delta, beta=beta, rd=rd, U1=U1, U2=U2, H1=H1,
                                    filterfac=filterfac)
         self._visc_key = None             # what the engine's molecular viscosity was last set from (_fused_viscosity)
+        self._bs_key = None               # ... and its backscatter closure (_fused_backscatter)
         self._init_grid()
         self.t = 0.
         self.taveints = math.ceil(self.taveint / self.dt)
@@ -240,10 +241,34 @@ class QGModel:
             self._visc_key = None
         return False
 
+    def _fused_backscatter(self):
+        """A (weighted) BackscatterBiharmonic — or a PhysicalParameterization that wraps one — with its fused switch on is
+        not a plug-in to call either: (C_S sqrt(weight), C_B, eps) go to the engine once and every step recomputes the
+        closure on the device.  On a stochastic_QGModel this holds where the reference recomputes on every step:
+        sampling 'AR1' with any nsteps, 'constant' with nsteps == 1 (the per-layer de-mean of the plug-in call is applied
+        to a field that has no mean); 'constant' with nsteps > 1 and 'deterministic' take the host plug-in path.
+        -> whether the attached parameterization is such a one."""
+        from .models.physical_parameterizations import fused_closure
+        c = fused_closure(self.q_parameterization)
+        sampling = getattr(self, 'sampling_type', None)
+        every_step = sampling in (None, 'AR1') or (sampling == 'constant' and self.noise_sampler.nsteps == 1)
+        if c is not None and c.fused and every_step:
+            cs, cb = np.asarray(c.smag_constant, dtype='float64'), np.asarray(c.back_constant, dtype='float64')
+            key = (id(_unwrap(self.q_parameterization)[0]), cs.tobytes(), cb.tobytes(), float(c.eps))
+            if key != self._bs_key:
+                self._eng.set_backscatter(cs if cs.ndim else float(cs), cb if cb.ndim else float(cb), c.eps)
+                self._bs_key = key
+            return True
+        if self._bs_key is not None:         # the closure was detached: the engine's copy goes with it
+            self._eng.set_backscatter(None)
+            self._bs_key = None
+        return False
+
     def _advance(self, n, refresh_diag=True):
         if n <= 0:
             return
-        if self._fused_viscosity() or self.q_parameterization is None:
+        on_device = [self._fused_viscosity(), self._fused_backscatter()]      # (both asked: each also detaches what is gone)
+        if any(on_device) or self.q_parameterization is None:
             self._eng.step(n, refresh_diag=refresh_diag)
         else:
             kw, param, weight = self._step_kwargs()

@@ -269,3 +269,17 @@ def load_parameterization(folder='model', model_weight=1.0, device=0):
         raise NotImplementedError(f'model {name!r} has no device path (available: {", ".join(classes)})')
     args.pop('folder', None)
     return model_weight * classes[name](**args, folder=folder, device=device)
+
+
+PHYSICAL_PARAMETERIZATIONS = ('ZannaBolton', 'ReynoldsStress', 'HybridSymbolic', 'ADM', 'BackscatterEddy', 'BackscatterJet')
+
+
+def named_parameterization(name, model_weight=1.0):
+    """The reference's ``--parameterization NAME`` branch (simulate.py:243-244: ``model_weight * eval(NAME)()`` over the
+    classes of models/physical_parameterizations.py): 'BackscatterEddy' and 'BackscatterJet' run on the device; the four
+    classes that wrap a pyqg fork raise NotImplementedError, as does a name the reference does not have."""
+    from ..models import physical_parameterizations as pp
+    if name not in PHYSICAL_PARAMETERIZATIONS:
+        raise NotImplementedError(f'no physical parameterization named {name!r} (the reference has: '
+                                  f'{", ".join(PHYSICAL_PARAMETERIZATIONS)})')
+    return model_weight * getattr(pp, name)()

@@ -438,7 +438,8 @@ int qgx_w1_workspace(size_t nu, size_t nv, int key_bits, size_t *bytes);
  * starting at element r*stride_r + t*stride_t of x (and of y, same strides; y is used by QGX_W1_SUMSQ2 only) — for the
  * last T snapshots of layer z of an (R, T_all, 2, N, N) array pass x + (T_all-T)*stride_t + z*N*N, P = N*N,
  * stride_t = 2*N*N, stride_r = T_all*stride_t.  is_double: x, y are double (1) or float (0).  key_bits 32 only for a
- * float identity feature.  keys_dev: R*T*P keys.  partials_dev: scratch of 2 * QGX_W1_PARTIALS doubles.
+ * float identity feature.  keys_dev: R*T*P keys.  partials_dev: scratch of 2 * QGX_W1_PARTIALS doubles (written in full, its contents before the
+ * call are not read).
  * stats_dev (2 doubles, written): [0] = sum of feature^2 in a fixed order, [1] = number of NaN / +-inf feature values.
  * QGX_ERR_INVALID before any device call for an empty view, a bad is_double / feature / key_bits, or null pointers. */
 int qgx_w1_keys(const void *x_dev, const void *y_dev, int is_double, int feature, int key_bits, int64_t R, int64_t T,
@@ -495,13 +496,19 @@ int qgx_offline_moments(const void *t_dev, const void *m_dev, const void *g_dev,
 /* np.histogram(x / scale, bins = nbins, range = (edges[0], edges[nbins])) in float64 over the view layer z, t >= t0 of an
  * (R, T, nlev, P) array; edges_dev: the np.linspace edges (nbins + 1 doubles).  counts_dev: nbins int64.  stats_dev (4
  * doubles): [0] mean, [1] population std (QGX_HIST_STATS only), [2] non-finite values in the view, [3] the scale used.
- * nbins = 0 with QGX_HIST_STATS computes the statistics only. */
+ * nbins = 0 with QGX_HIST_STATS computes the statistics only ([3]: the scale a count would have used; edges_dev and
+ * counts_dev are not touched and may be NULL).  Without QGX_HIST_STATS [0] and [1] are not written. */
 int qgx_histogram(const void *x_dev, int is_double, int64_t R, int64_t T, int64_t nlev, int64_t P, int64_t z, int64_t t0,
                   const double *edges_dev, int nbins, int flags, double scale, void *work_dev, size_t work_bytes,
                   int64_t *counts_dev, double *stats_dev, void *stream);
 
 /* ---- latent noise ------------------------------------------------------------
- * z <- a z + b xi with xi ~ N(0,1) from Philox4x32-10 (stochastic_pyqg.py:43-49). */
+ * z <- a z + b xi with xi ~ N(0,1) from Philox4x32-10 (stochastic_pyqg.py:43-49).  z: (B, n_per_member) float or double,
+ * n_per_member a positive multiple of 4; a == 0 overwrites z (its previous contents are not read).  Counter of the four
+ * normals at elements 4*quad .. 4*quad+3 of member b: (quad, step mod 2^32, (member_offset + b) mod 2^32, step >> 32),
+ * key (seed mod 2^32, seed >> 32).  The global member id enters the counter MODULO 2^32 — here, in qgx_step (qgx_param::
+ * member_offset) and in qgx_generator_forward_mean: ids that differ by a multiple of 2^32 draw the same stream, and a shard
+ * whose ids pass 2^32 - 1 wraps to 0 (oracle/samplers_ref.py::philox_normal masks in the same way). */
 int qgx_noise_normal(void *z_dev, int is_double, int B, int n_per_member, uint64_t seed,
                      uint64_t member_offset, uint64_t step, double a, double b, void *stream);
 

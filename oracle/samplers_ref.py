@@ -100,14 +100,15 @@ def philox_normal(seed, member, step, n_elem):
     """Standard normals for one member and one step.
 
     Counter layout (must match csrc/noise.hip): c0 = quad index (element//4),
-    c1 = step (low 32 bits), c2 = member id, c3 = step >> 32; key = (seed lo, seed hi).
+    c1 = step (low 32 bits), c2 = member id modulo 2^32 (the device's counter word is 32 bits wide; include/qgx.h states
+    the wrap), c3 = step >> 32; key = (seed lo, seed hi).
     Each Philox call yields 4 uint32 -> 2 Box-Muller pairs -> 4 normals, stored at
     elements 4*quad .. 4*quad+3.
     Returns float32 array of n_elem (n_elem must be a multiple of 4) and the raw uint32s.
     """
     assert n_elem % 4 == 0
     quad = np.arange(n_elem // 4, dtype=np.uint32)
-    r = philox4x32_10(quad, np.uint32(step & 0xFFFFFFFF), np.uint32(member),
+    r = philox4x32_10(quad, np.uint32(step & 0xFFFFFFFF), np.uint32(int(member) & 0xFFFFFFFF),
                       np.uint32((step >> 32) & 0xFFFFFFFF),
                       seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
     raw = np.stack(r, axis=1).reshape(-1)

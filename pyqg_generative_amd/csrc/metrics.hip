@@ -43,11 +43,17 @@ __device__ inline double value_of(uint32_t k) {
 
 template <typename T>
 __device__ inline double feature_of(const T *x, const T *y, size_t off, int feature) {
+    // numpy's u**2 + v**2: two rounded squares and a rounded sum.  __dmul_rn / __dadd_rn are plain * and + in this toolchain's
+    // headers, compiled with the default -ffp-contract, and fused into an fma after inlining (one rounding less for a float64
+    // input): the products are written out here with contraction switched off for this function.
+#pragma clang fp contract(off)
     const double a = (double)x[off];
     if (feature == QGX_W1_IDENTITY) return a;
-    if (feature == QGX_W1_SQUARE) return __dmul_rn(a, a);
+    const double aa = a * a;
+    if (feature == QGX_W1_SQUARE) return aa;
     const double b = (double)y[off];
-    return __dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b));   // numpy's u**2 + v**2: two rounded squares, no fma
+    const double bb = b * b;
+    return aa + bb;
 }
 
 // fixed-order tree over one value per thread of a KEY_THREADS / MERGE_THREADS (= 256) workgroup; result in lane 0
@@ -87,10 +93,15 @@ __global__ __launch_bounds__(KEY_THREADS) void k_w1_keys(const T *x, const T *y,
     }
 }
 
-// stats[0] = sum of partials[0 .. nblk), stats[1] = sum of partials[QGX_W1_PARTIALS ...]: one workgroup, fixed order
-__global__ __launch_bounds__(256) void k_w1_keys_finish(const double *partials, int nblk, double *stats) {
+// stats[0] = sum of partials[0 .. nblk), stats[1] = sum of partials[QGX_W1_PARTIALS ...]: one workgroup, fixed order.
+// The entries of blocks that were not launched are zeroed, so the caller's scratch is defined in full after the call.
+__global__ __launch_bounds__(256) void k_w1_keys_finish(double *partials, int nblk, double *stats) {
     __shared__ double red[256];
     double s = 0., b = 0.;
+    for (int i = nblk + threadIdx.x; i < QGX_W1_PARTIALS; i += 256) {
+        partials[i] = 0.;
+        partials[QGX_W1_PARTIALS + i] = 0.;
+    }
     for (int i = threadIdx.x; i < nblk; i += 256) {
         s += partials[i];
         b += partials[QGX_W1_PARTIALS + i];
@@ -405,7 +416,7 @@ extern "C" int qgx_w1_keys(const void *x_dev, const void *y_dev, int is_double, 
                                                           partials_dev, nblk, st);
     else launch_keys<float, uint64_t>(x_dev, y_dev, feature, T, P, stride_r, stride_t, n, keys_dev, partials_dev, nblk,
                                       st);
-    hipLaunchKernelGGL(k_w1_keys_finish, dim3(1), dim3(256), 0, st, (const double *)partials_dev, (int)nblk, stats_dev);
+    hipLaunchKernelGGL(k_w1_keys_finish, dim3(1), dim3(256), 0, st, partials_dev, (int)nblk, stats_dev);
     QGX_HIP(hipGetLastError());
     return QGX_OK;
 }

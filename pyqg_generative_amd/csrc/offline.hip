@@ -328,9 +328,10 @@ __global__ __launch_bounds__(HIST_THREADS) void k_hist_stats(const T *x, View v,
     }
 }
 
-// mode 0: stats[0] = mean, stats[2] = non-finite count; mode 1: stats[1] = population std
+// mode 0: stats[0] = mean, stats[2] = non-finite count; mode 1: stats[1] = population std, and with no_bins (statistics
+// only: no counting kernel follows to write it) stats[3] = the scale a count would have used
 __global__ __launch_bounds__(256) void k_hist_stats_finish(const double *partials, int nblk, int mode, double n,
-                                                           double *stats) {
+                                                           double *stats, int no_bins, int scale_std, double scale_val) {
     __shared__ double red[256];
     double s = 0., b = 0.;
     for (int i = threadIdx.x; i < nblk; i += 256) {
@@ -340,8 +341,10 @@ __global__ __launch_bounds__(256) void k_hist_stats_finish(const double *partial
     const double S = block_sum_256(s, red);
     const double B = block_sum_256(b, red);
     if (threadIdx.x == 0) {
-        if (mode) stats[1] = sqrt(S / n);
-        else {
+        if (mode) {
+            stats[1] = sqrt(S / n);
+            if (no_bins) stats[3] = scale_std ? stats[1] : scale_val;
+        } else {
             stats[0] = S / n;
             stats[2] = B;
         }
@@ -409,7 +412,7 @@ int histogram(const void *x, const View &v, const double *edges, int nbins, int 
             hipLaunchKernelGGL(k_hist_stats<T>, dim3(nblk), dim3(HIST_THREADS), 0, st, (const T *)x, v, mode,
                                (const double *)stats, dpart);
             hipLaunchKernelGGL(k_hist_stats_finish, dim3(1), dim3(256), 0, st, (const double *)dpart, nblk, mode,
-                               (double)v.n, stats);
+                               (double)v.n, stats, (int)(nbins == 0), (int)((flags & QGX_HIST_SCALE_STD) != 0), scale);
         }
     }
     if (nbins > 0) {

@@ -226,9 +226,29 @@ class Generator:
         if lib.qgx_generator_size_ok(self._h, int(inet), int(B), int(N)) != 0:
             raise ValueError(lib.qgx_last_error().decode())
 
+    @staticmethod
+    def _check_q_out(q, out):
+        """ValueError unless q is a contiguous float64 CUDA tensor (B,2,N,N) and `out` (if given) one of the same shape on
+        the same device: the library takes raw pointers and no capacities, so a float32 or short `out` would be overrun"""
+        if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.float64 and q.is_contiguous()):
+            raise ValueError('q must be a contiguous float64 CUDA tensor')
+        if q.dim() != 4 or q.shape[0] < 1 or q.shape[1] != 2 or q.shape[2] != q.shape[3]:
+            raise ValueError(f'q must be (B, 2, N, N) with a square grid, got {tuple(q.shape)}')
+        if out is None:
+            return
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == q.device):
+            raise ValueError("out must be a CUDA tensor on q's device")
+        if out.dtype != torch.float64:
+            raise ValueError(f'out must be float64, got {out.dtype}')
+        if tuple(out.shape) != tuple(q.shape):
+            raise ValueError(f"out must have q's shape {tuple(q.shape)}, got {tuple(out.shape)}")
+        if not out.is_contiguous():
+            raise ValueError('out must be contiguous')
+
     def forward(self, q, z=None, demean=True, out=None):
-        """q: (B,2,N,N) float64 cuda; z: (B,2,N,N) float32 (float64 for gz; 'ols' and 'ann' take none) -> S (B,2,N,N) float64."""
-        assert q.is_cuda and q.dtype == torch.float64 and q.is_contiguous() and q.dim() == 4
+        """q: (B,2,N,N) float64 cuda; z: (B,2,N,N) float32 (float64 for gz; 'ols' and 'ann' take none) -> S (B,2,N,N) float64.
+        out: a contiguous float64 CUDA tensor of q's shape to write S into (ValueError otherwise, before anything runs)."""
+        self._check_q_out(q, out)
         B, _, N, _ = q.shape
         if self.kind in self.NOISE_FREE:
             if z is not None:
@@ -249,8 +269,8 @@ class Generator:
         y_std * (mean of M realisations of the generator [+ net_mean]); 'gz': y_std * net_mean, no draws.  Realisation j of
         member b draws the Philox stream (seed, member_offset + b, step + ((j + 1) << 32)) on the device.  chunk: pseudo-members
         (member x realisation) per launch of the generator, 0 = automatic, else at least B.  'ols' and 'ann' have no such
-        mode (QgxError)."""
-        assert q.is_cuda and q.dtype == torch.float64 and q.is_contiguous() and q.dim() == 4
+        mode (QgxError).  out: as in forward."""
+        self._check_q_out(q, out)
         B, _, N, _ = q.shape
         S = out if out is not None else torch.empty_like(q)
 
@@ -364,6 +384,9 @@ class EnsembleEngine:
             out = torch.empty((self.B, 2, self.N, self.N), dtype=dtype, device=self.device)
         else:
             out = self._spec()
+        # qgx_get takes no capacity: the buffer must be exactly what the library will write
+        nbytes = int(lib.qgx_field_bytes(self._h, field))
+        assert out.numel() * out.element_size() == nbytes, (field, out.numel() * out.element_size(), nbytes)
         check(lib.qgx_get(self._h, field, _ptr(out), _stream()))
         return out
 
@@ -463,12 +486,17 @@ class EnsembleEngine:
         R (B).  Changes no state (qgx_backscatter_forcing)."""
         S = self._real()
         R = torch.empty((self.B,), dtype=torch.float64, device=self.device) if ratio else None
+        # S has the layout of a real field: the library's own count for one (qgx_field_bytes), not this class's arithmetic
+        assert S.numel() * S.element_size() == int(lib.qgx_field_bytes(self._h, _lib.F_Q)) and (R is None or R.numel() == self.B)
         check(lib.qgx_backscatter_forcing(self._h, _ptr(S), _ptr(R), _stream()))
         return (S, R) if ratio else S
 
     def status(self):
         """-> (KE[B], CFL[B]) as pyqg's _print_status computes them (from the last inversion)."""
         out = torch.empty((self.B, 2), dtype=torch.float64, device=self.device)
+        # out_dev[2*b + 0] = KE, [2*b + 1] = CFL: two doubles per member of the handle (the library exports no size query
+        # for this; the line states the contract next to the allocation, it cannot fail by itself)
+        assert out.numel() == 2 * self.B
         check(lib.qgx_status_ke_cfl(self._h, _ptr(out), _stream()))
         out = out.cpu().numpy()
         self.check_generators()
@@ -499,6 +527,10 @@ class EnsembleEngine:
         i = _lib.DIAGS.index(name)
         shape = (self.B, 2, self.N, self.NK) if i < 2 else (self.B, self.N, self.NK)
         out = torch.empty(shape, dtype=torch.float64, device=self.device)
+        # enum qgx_diag: (B,2,N,N/2+1) real for the first two, (B,N,N/2+1) for the rest, i.e. as many doubles as a spectral
+        # field has complex values, or half of that, by the library's own count of a spectral field
+        nspec = int(lib.qgx_field_bytes(self._h, _lib.F_QH)) // 16
+        assert out.numel() == (nspec if i < 2 else nspec // 2), (name, out.numel(), nspec)
         check(lib.qgx_diag_get(self._h, i, _ptr(out), _stream()))
         return out
 

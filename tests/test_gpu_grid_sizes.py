@@ -31,6 +31,11 @@ from conftest import GOLDEN, golden, load_generator
 from oracle import qg_ref, gen_ref, samplers_ref
 
 F64_TOL = 1e-12
+# float32 generator: forcing S (of the layer maximum) and qh after one step.  TIGHT where the measured worst error is at most
+# a third of it (every admitted kind, size and member count: S <= 3.7e-6, qh <= 4.9e-8) except GZ at 128 x 128 with two
+# members, which measured S 3.8e-5, qh 2.8e-7 (its 5x5 layer's kernel at that size carries 8e-6 of the net output) and keeps
+# LOOSE, the earlier bound.  DESIGN.md section 4
+TIGHT, LOOSE = (2e-5, 5e-7), (5e-5, 2e-6)
 JET = dict(dt=7200., rek=7e-8, delta=0.1, beta=1e-11)      # tools/parameters.py:26-27,37
 
 ALL = [8, 12, 16, 18, 24, 32, 36, 48, 54, 64, 72, 96, 108, 128, 144, 162, 192, 216, 256, 288, 324, 384, 432, 486, 512]
@@ -597,8 +602,9 @@ def test_generator_grid_size_contract(kind, N):
                 sc = np.abs(m.PV_forcing).max(axis=(1, 2), keepdims=True)
                 eS, eq = (np.abs(S[b] - m.PV_forcing) / sc).max(), _rel(qh[b], m.qh)
                 worst_S, worst_q = max(worst_S, eS), max(worst_q, eq)
-                assert eS < 5e-5, (kind, N, B, b, eS)
-                assert eq < 2e-6, (kind, N, B, b, eq)
+                s_bound, qh_bound = LOOSE if (kind, N, B) == ('gz', 128, 2) else TIGHT
+                assert eS < s_bound, (kind, N, B, b, eS)
+                assert eq < qh_bound, (kind, N, B, b, eq)
             assert gen.range_ok() is None
             e.close()
             print(f'\nGRID generator {kind} N={N} B={B}: admitted; net error {worst_y:.2e}, S {worst_S:.2e}, qh {worst_q:.2e}')
@@ -660,7 +666,9 @@ def test_generator_grid_size_contract(kind, N):
         qh = e.get(L.F_QH).cpu().numpy()
         m = _oracle_model(kind, ora, 64, dict(dt=14400.), q64[1], z64[1] if z64 is not None else None)
         m._step_forward()
-        assert _rel(qh[1], m.qh) < 2e-6, (kind, N, B)
+        eq = _rel(qh[1], m.qh)
+        print(f'\nBOUND generator {kind} after a refusal at N={N} B={B}: qh at 64 x 64 {eq:.2e}')
+        assert eq < TIGHT[1], (kind, N, B, eq)           # measured <= 6.5e-8 over all kinds and refused sizes
         assert gen.range_ok() is None
         e.close()
     print(f'\nGRID generator {kind} N={N}: ' + ', '.join(f'B={B} ' + ('admitted' if ADMITTED[(kind, N, B)] else 'refused') for B in (1, 2)))

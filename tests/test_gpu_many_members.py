@@ -20,6 +20,10 @@ from conftest import load_generator, GOLDEN
 from oracle import qg_ref, gen_ref, samplers_ref
 
 F64_TOL = 1e-12
+# float32 generator: forcing S (of the layer maximum) and qh after the steps.  TIGHT where the measured worst error is at
+# most a third of it (gan / vae: S <= 3.4e-6, qh <= 1.1e-7); LOOSE, the earlier bound, for the GZ case (48 x 48, 300 members:
+# S 2.5e-5, qh 1.15e-6 — net_mean + sqrt(net_var) * z carries the variance net's error times the noise).  DESIGN.md section 4
+TIGHT, LOOSE = (2e-5, 5e-7), (5e-5, 2e-6)
 JET = dict(dt=7200., rek=7e-8, delta=0.1, beta=1e-11)      # tools/parameters.py:26-27,37
 
 
@@ -136,6 +140,7 @@ def test_parameterized_steps_one_workgroup_per_member(kind, N, B, sampling, nd, 
         m.set_q(q0[b])
         refs[b] = m
     draws = 0
+    worst_S = worst_q = 0.0
     for s in range(nsteps):
         xi = torch.as_tensor(np.ascontiguousarray(xis[draws].reshape(B, 2, N, N))).cuda()
         if sampling == 'AR1' or s % nd == 0:
@@ -147,8 +152,12 @@ def test_parameterized_steps_one_workgroup_per_member(kind, N, B, sampling, nd, 
         S = e.get(L.F_S).cpu().numpy()
         for b, m in refs.items():
             sc = np.abs(m.PV_forcing).max(axis=(1, 2), keepdims=True)
-            assert (np.abs(S[b] - m.PV_forcing) / sc).max() < 5e-5, (s, b)
-            assert _rel(qh[b], m.qh) < 2e-6, (s, b)
+            worst_S = max(worst_S, (np.abs(S[b] - m.PV_forcing) / sc).max())
+            worst_q = max(worst_q, _rel(qh[b], m.qh))
+        s_bound, qh_bound = LOOSE if kind == 'gz' else TIGHT
+        assert worst_S < s_bound, (s, worst_S)
+        assert worst_q < qh_bound, (s, worst_q)
+    print(f'\nBOUND many members {kind} N={N} B={B} {sampling}: S {worst_S:.2e}, qh {worst_q:.2e}')
     assert gen.range_ok() is None
 
 

@@ -17,6 +17,14 @@ from conftest import golden, load_generator, GOLDEN
 from oracle import qg_ref, gen_ref, samplers_ref
 
 F64_TOL = 1e-12
+# float32 generator: forcing S (of the layer maximum) and qh after the steps.  TIGHT where the measured worst error is at
+# most a third of it, LOOSE (the earlier bound) elsewhere; measured values in DESIGN.md section 4
+TIGHT, LOOSE = (2e-5, 5e-7), (5e-5, 2e-6)
+# randomised cases 5, 8, 11: GZ with 9, 33, 57 members measured S 4.4e-5, 2.9e-5, 3.1e-5 and qh 4.3e-7, 9.3e-7, 5.6e-7
+# (every other case: S <= 3.7e-6, qh <= 8.0e-8).  GZ's forcing is net_mean + sqrt(net_var) * z, which carries the variance
+# net's error times a noise value of up to 4-5 sigma (GZ with 5 members, case 2, measured 2.6e-6 / 8.0e-8: the kernels a
+# larger ensemble takes differ).  Above a third of the tight bound, so these keep the earlier one
+LOOSE_RANDOMISED = (5, 8, 11)
 
 
 def _engine(N, B, **kw):
@@ -543,10 +551,15 @@ def test_randomised_configurations_match_oracle(case):
             m._step_forward()
     qh = e.get(L.F_QH).cpu().numpy()
     S = e.get(L.F_S).cpu().numpy()
+    worst_S = worst_q = 0.0
     for b, m in refs.items():
         sc = np.abs(m.PV_forcing).max(axis=(1, 2), keepdims=True)
-        assert (np.abs(S[b] - m.PV_forcing) / sc).max() < 5e-5, (N, B, kind, b)
-        assert _rel(qh[b], m.qh) < 2e-6, (N, B, kind, b)
+        worst_S = max(worst_S, (np.abs(S[b] - m.PV_forcing) / sc).max())
+        worst_q = max(worst_q, _rel(qh[b], m.qh))
+    print(f'\nBOUND randomised case {case} {kind} N={N} B={B}: S {worst_S:.2e}, qh {worst_q:.2e}')
+    s_bound, qh_bound = LOOSE if case in LOOSE_RANDOMISED else TIGHT
+    assert worst_S < s_bound, (N, B, kind, worst_S)
+    assert worst_q < qh_bound, (N, B, kind, worst_q)
     assert gen.range_ok() is None
 
 

@@ -251,7 +251,7 @@ int qgx_diag_reset(qgx_model *m);
 enum qgx_gen_kind { QGX_GEN_GAN = 0, QGX_GEN_VAE = 1, QGX_GEN_GZ = 2, QGX_GEN_OLS = 3 };
 
 typedef struct qgx_cnn_weights {      /* host pointers, float32, PyTorch layouts */
-    int32_t n_in, n_out;              /* 4/2 and 2                                   */
+    int32_t n_in, n_out;              /* 4/2; 2, or 4: a flux-form net (see below)   */
     const float *conv_w[8];           /* (cout, cin, k, k)                           */
     const float *conv_b[8];           /* (cout)                                      */
     const float *bn_gamma[7], *bn_beta[7], *bn_mean[7], *bn_var[7];
@@ -264,7 +264,14 @@ typedef struct qgx_cnn_weights {      /* host pointers, float32, PyTorch layouts
  * OLS — the deterministic AndrewCNN(2, 2) `net` of OLSModel (ols_model.py:29-31), S = y_std * net(q/x_std) (:68-75): n_nets 1,
  * n_in 2.  It takes no latent noise: qgx_generator_forward ignores z (NULL allowed), qgx_step draws none and writes no z,
  * and refuses z_external_dev; the sampler still decides when the forcing is recomputed (generate_latent_noise returns 0,
- * parameterization.py:23-34).  Any other n_nets, n_in or n_out is refused (QGX_ERR_INVALID) before any allocation.
+ * parameterization.py:23-34).
+ * n_out = 4 marks a flux-form net, AndrewCNN(n_in, 2, div=True) (cnn_tools.py:100-123, 139-142, 170-175): conv_w[7] is
+ * (4, 32, 3, 3), the last convolution writes the x-fluxes of both layers, then the y-fluxes, and the net's output is
+ * (B, 2, N, N) = 10000 * divergence(fluxes), spectral, in float32, with the grid lines of pyqg.QGModel(nx = N) at pyqg's
+ * default L = 1e6 as complex64 — NOT the online model's L — evaluated by one LDS-resident FFT kernel behind the last
+ * convolution.  Every net of a GAN, VAE or OLS handle is 2 or 4 on its own (the regression net independently of net 0);
+ * GZ takes 2 only.  Such a net's output integrates to zero over the domain before any de-mean.
+ * Any other n_nets, n_in or n_out is refused (QGX_ERR_INVALID) before any allocation.
  * Grid sizes: the AndrewCNN kernels of such a handle run N = 16, 32, 48, 64, 96 and 128 (every member count).  The
  * other sizes qgx_create admits have no whole number of the kernels' row tiles (8, 12, 24 and every size that divides
  * neither 256 nor 384) or a 5x5-layer patch beyond the LDS (192, 256, 384).  qgx_generator_forward, qgx_cnn_forward and
@@ -305,7 +312,8 @@ typedef struct qgx_unet_weights {
 } qgx_unet_weights;
 
 /* A GAN-kind handle whose generator is the U-Net (exact-f32 matrix-core kernels, unet.hip); net_mean: the AndrewCNN(2, 2)
- * regression net of regression != 'None' (cgan_regression.py:59-60) or NULL.  S = y_std * (U-Net([q/x_std, z]) + net_mean(q/x_std)).
+ * regression net of regression != 'None' (cgan_regression.py:59-60) or NULL; it may be flux-form (n_out = 4, div=True) while
+ * the U-Net is not.  S = y_std * (U-Net([q/x_std, z]) + net_mean(q/x_std)).
  * The handle serves qgx_generator_forward, qgx_step (gen), qgx_cnn_forward (inet 0: the U-Net, inet 1: net_mean),
  * qgx_generator_range_read and qgx_generator_info (precision 0).  N must be 32, 48, 64, 96 or 128 (QGX_ERR_INVALID before
  * any launch otherwise).  The AndrewCNN-only options and queries (qgx_generator_set_option with anything but precision 0,
@@ -355,7 +363,8 @@ int qgx_generator_forward(qgx_generator *g, const double *q_dev, const void *z_d
  * a grid the nets do not take for the pseudo-batches launched. */
 int qgx_generator_forward_mean(qgx_generator *g, const double *q_dev, double *S_dev, int B, int N, int M, int chunk,
                                int demean, uint64_t seed, uint64_t member_offset, uint64_t step, void *stream);
-/* raw CNN forward of net `inet`: x (B,n_in,N,N) float -> y (B,n_out,N,N) float
+/* raw CNN forward of net `inet`: x (B,n_in,N,N) float -> y (B,2,N,N) float — also for a flux-form net (n_out = 4), whose
+ * four fluxes stay in the handle's workspace and whose y is 10000 * their divergence; the ANN: (B,1,N,N) -> (B,1,N,N)
  * (AndrewCNN.forward in eval mode; used by predict_mean_snapshot / offline sampling) */
 int qgx_cnn_forward(qgx_generator *g, int inet, const float *x_dev, float *y_dev,
                     int B, int N, void *stream);

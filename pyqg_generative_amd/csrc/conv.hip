@@ -33,6 +33,7 @@ struct ConvArgs {
     const float *w;        // packed [kgroup][COUTP][8]
     const float *bias, *scale, *shift;   // [COUTP]
     int N, R, cout_real;
+    int out_channels;      // k_conv_last: channels of a member in `out` (a flux-form net writes its four in two launches of two)
     size_t npix_total;     // B*N*N (stride of one split-K partial plane)
     float ascale;          // OUTH: power-of-two pre-scale of the stored 16-bit activations
     unsigned *range;       // OUTH: f16x3 range guard flag word (conv_half.hpp::range_guard)
@@ -600,7 +601,7 @@ __global__ __launch_bounds__(256) void k_conv_last(ConvArgs a, LastWeights lw) {
             red[(part * 64 + p) * 2] = acc0;
             red[(part * 64 + p) * 2 + 1] = acc1;
         } else {
-            float *o = a.out + (size_t)b * a.cout_real * N * N + (size_t)y0 * N + p;
+            float *o = a.out + (size_t)b * a.out_channels * N * N + (size_t)y0 * N + p;
             o[0] = acc0 + a.bias[0];
             if (a.cout_real > 1) o[(size_t)N * N] = acc1 + a.bias[1];
         }
@@ -612,7 +613,7 @@ __global__ __launch_bounds__(256) void k_conv_last(ConvArgs a, LastWeights lw) {
             float v = a.bias[c];
 #pragma unroll
             for (int q = 0; q < PARTS; ++q) v += red[(q * 64 + p) * 2 + c];   // fixed order
-            a.out[((size_t)b * a.cout_real + c) * N * N + (size_t)y0 * N + p] = v;
+            a.out[((size_t)b * a.out_channels + c) * N * N + (size_t)y0 * N + p] = v;
         }
     }
 }
@@ -888,11 +889,11 @@ static int pack_layer(LayerHost &L, int li, const qgx_cnn_weights *w, bool plana
     }
     if (li == 7) {      // [tap][c][2] for the VALU last-layer kernel
         const int cin = L.cin, ks = L.ks;
-        memset(&L.wv_host, 0, sizeof(L.wv_host));
-        for (int co = 0; co < cout && co < 2; ++co)
+        memset(L.wv_host, 0, sizeof(L.wv_host));
+        for (int co = 0; co < cout && co < 4; ++co)
             for (int c = 0; c < cin; ++c)
                 for (int t = 0; t < ks * ks; ++t)
-                    L.wv_host.w[((size_t)t * cin + c) * 2 + co] = w->conv_w[li][((size_t)co * cin + c) * ks * ks + t];
+                    L.wv_host[co / 2].w[((size_t)t * cin + c) * 2 + (co & 1)] = w->conv_w[li][((size_t)co * cin + c) * ks * ks + t];
     }
     std::vector<float> bias(L.coutp, 0.f), sc(L.coutp, 1.f), sh(L.coutp, 0.f);
     for (int co = 0; co < cout; ++co) {
@@ -911,6 +912,7 @@ static int pack_layer(LayerHost &L, int li, const qgx_cnn_weights *w, bool plana
 
 int cnn_pack_net(NetHost &net, const qgx_cnn_weights *w) {
     net.n_in = w->n_in; net.n_out = w->n_out;
+    if (net.flux()) { if (const int rc = fluxdiv_prepare()) return rc; }
     for (int li = 0; li < 8; ++li) {
         LayerHost &L = net.L[li];
         L.cin = li == 0 ? w->n_in : HID[li - 1];
@@ -1136,20 +1138,24 @@ static int launch_conv_last(qgx_generator *g, const LayerHost &L, const float *i
     QGX_REQUIRE(R > 0 && N % R == 0, "generator: unsupported grid size N=%d", N);
     ProfScope prof;
     if (const int prc = prof.begin(g, 7, st)) return prc;
-    ConvArgs a = {};
-    a.in = in; a.out = out; a.w = nullptr; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
-    a.N = N; a.R = R; a.cout_real = n_out;
     const bool split = R * N == 64;
     const size_t lds = last_lds_bytes(R, N);
     QGX_REQUIRE(lds <= 160 * 1024, "generator: LDS patch %zu B too large for N=%d", lds, N);
-    if (split) {
-        auto kern = k_conv_last<32, 3, 4>;
-        { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-        hipLaunchKernelGGL(kern, dim3(B * (N / R)), dim3(256), lds, st, a, L.wv_host);
-    } else {
-        auto kern = k_conv_last<32, 3>;
-        { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-        hipLaunchKernelGGL(kern, dim3(B * (N / R)), dim3(256), lds, st, a, L.wv_host);
+    // two accumulators per thread, and two channels of weights are 2.3 KB of kernel arguments (the limit is 4 KB): the four
+    // flux channels of a flux-form net are two launches, each writing its channel pair of the (B, 4, N, N) output
+    for (int c0 = 0; c0 < n_out; c0 += 2) {
+        ConvArgs a = {};
+        a.in = in; a.out = out + (size_t)c0 * N * N; a.w = nullptr; a.bias = L.bias + c0; a.scale = L.scale; a.shift = L.shift;
+        a.N = N; a.R = R; a.cout_real = n_out - c0 < 2 ? n_out - c0 : 2; a.out_channels = n_out;
+        if (split) {
+            auto kern = k_conv_last<32, 3, 4>;
+            { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
+            hipLaunchKernelGGL(kern, dim3(B * (N / R)), dim3(256), lds, st, a, L.wv_host[c0 / 2]);
+        } else {
+            auto kern = k_conv_last<32, 3>;
+            { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
+            hipLaunchKernelGGL(kern, dim3(B * (N / R)), dim3(256), lds, st, a, L.wv_host[c0 / 2]);
+        }
     }
     QGX_HIP(hipGetLastError());
     return QGX_OK;
@@ -1796,14 +1802,16 @@ static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x
 #else
         QGX_REQUIRE(done1, "generator: no f16x3 kernel for N=%d", N);
 #endif
-        const bool pairs_ok = NS == 2 && net.n_out <= 2;      // the pair kernels: f16x3, and (7, 8) writes at most two channels
+        const bool pairs_ok = NS == 2;                         // the pair kernels: f16x3
+        // ... and the fused (7, 8) pair writes at most two channels: a flux-form net takes layer 7's kernel and the VALU last layer
+        const int no78 = net.n_out <= 2 ? ~0 : ~2, tiny_no78 = net.n_out <= 2 ? ~0 : ~1;
         if (p.tiny) {
             // (local names: the 64-channel activation of layer 2 is in Bb; `cur` holds a layer's input, `oth` takes its output)
             float *cur = Bb, *oth = A;
             // Layers (3, 4), (5, 6) and (7, 8) each as ONE launch on 2-row strips ("tiny_pairs" bits 2, 1, 0): a single member is
             // a chain of launch latencies, and a strip's fixed costs — layer B's 36 KB of MFMA weights above all — are cheaper
             // than a kernel boundary there; for (3, 4) the one launch also replaces split-K and its combine kernel
-            const int tp = pairs_ok && N == 64 ? g->opt_tiny_pairs : 0;
+            const int tp = pairs_ok && N == 64 ? g->opt_tiny_pairs & tiny_no78 : 0;
             if (tp & 4) {
                 if ((rc = launch_convh_pair<64, false, false, 64, 2>(g, 2, net.L[2], net.L[3], cur, oth, Bc, N, 0, st))) return rc;
                 std::swap(cur, oth);
@@ -1818,7 +1826,7 @@ static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x
         }
         // 3x3 layers fused pairwise at 64 x 64; "fuse" bits: 1 = layers (5, 6), 2 = layers (7, 8), 4 = layers (3, 4) — the
         // 64-channel pair measured slower fused
-        const int fuse = pairs_ok && N == 64 ? g->opt_fuse : 0;
+        const int fuse = pairs_ok && N == 64 ? g->opt_fuse & no78 : 0;
         if (fuse & 4) {
             if ((rc = launch_convh_pair<64, false, false>(g, 2, net.L[2], net.L[3], Bb, A, Bc, N, 0, st))) return rc;
         } else {
@@ -1834,7 +1842,7 @@ static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x
         } else {
             // 96 x 96: the pair kernel on 4-row strips (a 6-row intermediate patch of 98 columns is 85 KB); "fuse96" bits as "fuse".
             // Every other grid: two kernels per pair
-            const int fuse96 = pairs_ok && N == 96 && Bc * 24 >= 256 ? g->opt_fuse96 : 0;
+            const int fuse96 = pairs_ok && N == 96 && Bc * 24 >= 256 ? g->opt_fuse96 & no78 : 0;
             rc = layers_5_to_8<NS, 96, 4>(g, net, fuse96 & 3, cur, oth, yc, Bc, N, st);
         }
         if (rc) return rc;
@@ -1842,8 +1850,8 @@ static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x
     return QGX_OK;
 }
 
-// AndrewCNN.forward: x planar (B,n_in,N,N) -> y planar (B,n_out,N,N)
-int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N, hipStream_t st) {
+// the eight convolutions: x planar (B,n_in,N,N) -> y planar (B,n_out,N,N)
+static int cnn_convs(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N, hipStream_t st) {
     int rc;
     if (g->opt_precision && half_path_ok(g, B, N))
 #ifdef QGX_AB
@@ -1877,10 +1885,26 @@ int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, float *y, 
     rec(5, Bb, 32);
     if ((rc = conv_hidden<32, 32, 3>(g, 6, net.L[6], Bb, A, B, N, st))) return rc;
     rec(6, A, 32);
-    if (g->opt_last_valu) rc = launch_conv_last(g, net.L[7], A, y, B, N, net.n_out, st);
+    // (the MFMA form of the last layer is instantiated for two output channels: a flux-form net takes the VALU kernel)
+    if (g->opt_last_valu || net.flux()) rc = launch_conv_last(g, net.L[7], A, y, B, N, net.n_out, st);
     else rc = launch_conv<32, 2, 3, 16, false, true>(g, 7, net.L[7], A, y, B, N, net.n_out, st);
     if (rc) return rc;
     return QGX_OK;
+}
+
+// AndrewCNN.forward (cnn_tools.py:164-176): x planar (B,n_in,N,N) -> y planar (B,2,N,N).  div=True: the convolutions write the
+// four fluxes into the workspace's F, and y = 10000 div F (fluxdiv.hip) — every caller (qgx_cnn_forward, generator_forward[_mean],
+// the calibration's comparisons, the step kernel's deferred finish) sees the one output shape and needs no second path
+int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N, hipStream_t st) {
+    if (!net.flux()) return cnn_convs(g, net, x, y, B, N, st);
+    QGX_REQUIRE(fluxdiv_size_ok(N), "flux-form net: no divergence kernel for N = %d (16, 32, 48, 64, 96 or 128)", N);
+    float *F = g->work().F;
+    QGX_REQUIRE(F && g->work().cap_elems >= (size_t)B * N * N, "flux-form net: the flux buffer is not reserved");
+    if (const int rc = cnn_convs(g, net, x, F, B, N, st)) return rc;
+#ifdef QGX_AB
+    if (g->opt_stop_layer) return QGX_OK;
+#endif
+    return fluxdiv_forward(F, y, B, N, st);
 }
 
 // Whether cnn_forward takes B members at N x N under the options in force: the conditions its launchers assert, gathered so
@@ -1892,6 +1916,7 @@ int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, float *y, 
 bool cnn_size_ok(const qgx_generator *g, const NetHost &net, int B, int N) {
     const int R = choose_rows(N);
     if (B < 1 || R <= 0 || N % R) return false;
+    if (net.flux() && !fluxdiv_size_ok(N)) return false;
     if (g->opt_precision && half_path_ok(g, B, N)) {
 #ifdef QGX_AB
         if (rows_h2(N) <= 0) return true;      // kernels of the A/B library's experiments: their launchers decide
@@ -2033,7 +2058,7 @@ static int calibrate_wino(qgx_generator *g) {
             if (rc) break;
             QGX_HIP(hipMemset(cd, 0, 2 * sizeof(unsigned)));
             hipLaunchKernelGGL(k_absdiff_max, dim3(64), dim3(256), 0, nullptr, (const float *)w.Y1, (const float *)w.Y0,
-                               (size_t)B * net.n_out * npix, cd);
+                               (size_t)B * net.y_channels() * npix, cd);
             float h[2];
             QGX_HIP(hipMemcpy(h, cd, sizeof(h), hipMemcpyDeviceToHost));
             const float err = h[1] > 0.f ? h[0] / h[1] : INFINITY;
@@ -2267,10 +2292,13 @@ extern "C" int qgx_generator_set_option(qgx_generator *g, const char *name, int 
 }
 
 #ifdef QGX_AB
-// A/B library, debugging: copy the first nbytes of activation buffer `which` (0: the odd layers' outputs, 1: the even layers')
+// A/B library, debugging: copy the first nbytes of activation buffer `which` (0: the odd layers' outputs, 1: the even layers',
+// 2: the fluxes (B, 4, N, N) of a flux-form net's last forward)
 extern "C" int qgx_debug_read_act(qgx_generator *g, int which, void *dst_dev, size_t nbytes, void *stream) {
-    QGX_REQUIRE(g && dst_dev, "qgx_debug_read_act: null argument");
-    QGX_HIP(hipMemcpyAsync(dst_dev, which ? (const void *)g->work().actB : (const void *)g->work().actA, nbytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    QGX_REQUIRE(g && dst_dev && which >= 0 && which <= 2, "qgx_debug_read_act: bad argument");
+    const Workspace &w = g->work();
+    QGX_REQUIRE(which != 2 || (w.F && nbytes <= w.cap_elems * 4 * sizeof(float)), "qgx_debug_read_act: no flux buffer of %zu bytes", nbytes);
+    QGX_HIP(hipMemcpyAsync(dst_dev, which == 2 ? (const void *)w.F : which ? (const void *)w.actB : (const void *)w.actA, nbytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return QGX_OK;
 }
 #endif

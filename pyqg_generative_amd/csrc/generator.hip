@@ -269,6 +269,8 @@ int generator_reserve(qgx_generator *g, int B, int N) {
     QGX_HIP(hipMalloc((void **)&w.X, need * 6 * sizeof(float)));    // (B, 4, N, N), and behind it (B, 2, N, N) for a regression net
     QGX_HIP(hipMalloc((void **)&w.Y0, need * 2 * sizeof(float)));
     QGX_HIP(hipMalloc((void **)&w.Y1, need * 2 * sizeof(float)));
+    // a flux-form net (n_out = 4) writes its fluxes (B, 4, N, N) here, and the divergence kernel reads them
+    if (g->nets[0].flux() || (g->n_nets == 2 && g->nets[1].flux())) QGX_HIP(hipMalloc((void **)&w.F, need * 4 * sizeof(float)));
     w.cap_elems = need;
     return QGX_OK;
 }
@@ -509,8 +511,11 @@ extern "C" int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n
                 kind == QGX_GEN_GZ ? "2" : kind == QGX_GEN_OLS ? "1" : "1 or 2", n_nets);
     for (int n = 0; n < n_nets; ++n) {      // every net's shape before anything is allocated
         const int want_in = kind == QGX_GEN_GZ || kind == QGX_GEN_OLS || n == 1 ? 2 : 4;
-        QGX_REQUIRE(nets[n].n_in == want_in && nets[n].n_out == 2, "net %d: n_in=%d n_out=%d, expected %d and 2", n,
-                    nets[n].n_in, nets[n].n_out, want_in);
+        // n_out = 4: a flux-form net (AndrewCNN(n_in, 2, div=True)), each net of a GAN / VAE / OLS handle on its own; MeanVarModel's
+        // variance net has no such form here
+        const bool out_ok = nets[n].n_out == 2 || (nets[n].n_out == 4 && kind != QGX_GEN_GZ);
+        QGX_REQUIRE(nets[n].n_in == want_in && out_ok, "net %d: n_in=%d n_out=%d, expected %d and %s", n,
+                    nets[n].n_in, nets[n].n_out, want_in, kind == QGX_GEN_GZ ? "2" : "2 (or 4: flux form)");
     }
     qgx_generator *g = nullptr;
     int rc = new_handle("qgx_generator_create", kind, n_nets, x_std, y_std, device, &g);
@@ -523,8 +528,8 @@ extern "C" int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n
 extern "C" int qgx_generator_create_unet(const qgx_unet_weights *w, const qgx_cnn_weights *net_mean, const float x_std[2],
                                          const float y_std[2], int device, qgx_generator **out) {
     QGX_REQUIRE(w && out && x_std && y_std, "qgx_generator_create_unet: null argument");
-    QGX_REQUIRE(!net_mean || (net_mean->n_in == 2 && net_mean->n_out == 2),
-                "qgx_generator_create_unet: net_mean must be an AndrewCNN(2, 2) (n_in=%d n_out=%d)", net_mean->n_in, net_mean->n_out);
+    QGX_REQUIRE(!net_mean || (net_mean->n_in == 2 && (net_mean->n_out == 2 || net_mean->n_out == 4)),
+                "qgx_generator_create_unet: net_mean must be an AndrewCNN(2, 2), n_out = 4 in flux form (n_in=%d n_out=%d)", net_mean->n_in, net_mean->n_out);
     qgx_generator *g = nullptr;
     int rc = new_handle("qgx_generator_create_unet", QGX_GEN_GAN, net_mean ? 2 : 1, x_std, y_std, device, &g);
     if (rc) return rc;

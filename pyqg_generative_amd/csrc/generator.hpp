@@ -15,7 +15,7 @@ struct LastWeights { float w[3 * 3 * 32 * 2]; };   // [tap][c][2], passed BY VAL
 
 struct LayerHost {
     int cin, cout, ks, coutp, cc, ngroups;
-    LastWeights wv_host;   // last layer, VALU kernel layout (kernel argument)
+    LastWeights wv_host[2];   // last layer, VALU kernel layout (kernel argument): output channels (0, 1), and (2, 3) of a flux-form net
     float *wl16 = nullptr, *wl8 = nullptr;   // k_conv3 layout [chunk][tap][g8][h][coutp][4], 16- / 8-channel chunks
     float *w = nullptr, *w32 = nullptr, *bias = nullptr, *scale = nullptr, *shift = nullptr;   // w: 16-ch chunks (or planar), w32: 32-ch chunks
     void *wh[2] = {nullptr, nullptr};        // conv_half.hpp layouts: [0] f16 (NS = 1), [1] f16 hi/lo (NS = 2)
@@ -38,18 +38,22 @@ struct LayerHost {
     }
 };
 struct NetHost {
-    int n_in, n_out;
+    int n_in, n_out;       // n_out = 4: a flux-form net (AndrewCNN(n_in, 2, div=True)): the last convolution writes four fluxes
     LayerHost L[8];
+    bool flux() const { return n_out == 4; }
+    int y_channels() const { return flux() ? 2 : n_out; }     // channels of AndrewCNN.forward's output
 };
 
 // activation buffers of one ensemble (or half-ensemble), grown on demand, outside any captured region
 struct Workspace {
     size_t cap_elems = 0;          // capacity in units of B*N*N pixels
     float *actA = nullptr, *actB = nullptr, *X = nullptr, *Y0 = nullptr, *Y1 = nullptr;
+    float *F = nullptr;            // fluxes (B, 4, N, N) of a flux-form net, between its last convolution and the divergence;
+                                   // allocated only for handles that hold such a net
     float *part = nullptr;         // split-K partial sums of the small-ensemble path
     size_t part_elems = 0;
     void free_activations() {      // everything generator_reserve allocates
-        for (float **p : {&actA, &actB, &X, &Y0, &Y1}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+        for (float **p : {&actA, &actB, &X, &Y0, &Y1, &F}) if (*p) { (void)hipFree(*p); *p = nullptr; }
         cap_elems = 0;
     }
     double *mean_acc = nullptr;    // deterministic sampling: float64 sum over realisations (B, 2, N, N), kept across the chunks
@@ -145,10 +149,16 @@ int cnn_pack_net(NetHost &net, const qgx_cnn_weights *w);    // shapes of the ei
 void cnn_free_net(NetHost &net);
 int cnn_calibrate(qgx_generator *g);          // range calibration, then the Winograd layer's per grid size (once, at creation)
 void cnn_exact_f32_only(qgx_generator *g);    // U-Net and ANN handles: a net_mean beside them takes the exact-f32 kernels
-// AndrewCNN.forward: x planar (B,n_in,N,N) -> y planar (B,n_out,N,N)
+// AndrewCNN.forward: x planar (B,n_in,N,N) -> y planar (B,2,N,N); a flux-form net's fluxes go through the workspace's F and
+// the divergence kernel (fluxdiv.hip), so that every caller sees the one output shape
 int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N, hipStream_t st);
 // whether cnn_forward's launchers take B members at N x N under the options in force (no HIP call)
 bool cnn_size_ok(const qgx_generator *g, const NetHost &net, int B, int N);
+
+// ---- fluxdiv.hip: y (B,2,N,N) = 10000 div F, F (B,4,N,N) = [fx1, fx2, fy1, fy2], float32 spectral, one kernel ----
+bool fluxdiv_size_ok(int N);
+int fluxdiv_prepare();                         // once per handle with a flux-form net, outside any captured region
+int fluxdiv_forward(const float *F, float *y, int B, int N, hipStream_t st);
 
 // ---- generator.hip, called by conv.hip ----
 int generator_reserve(qgx_generator *g, int B, int N);       // the active workspace's activation buffers for B members at N x N

@@ -130,12 +130,13 @@ class CGANRegression(_LatentCNN):
     def __init__(self, regression='None', nx=64, generator='Andrew', folder='model', div=False,
                  hidden_channels=[128, 64, 32, 32, 32, 32, 32], device=0):
         # generator='DeepInversion': the U-Net of deep_inversion.py:44-94 (cgan_regression.py:50-53); its net_mean stays an
-        # AndrewCNN(2, 2) (:59-60)
-        if generator not in ('Andrew', 'DeepInversion') or div or list(hidden_channels) != [128, 64, 32, 32, 32, 32, 32]:
-            raise NotImplementedError('only generator="Andrew" or "DeepInversion", div=False with the default hidden channels '
-                                      'has a device path')
+        # AndrewCNN(2, 2) (:59-60).  div=True (:51, :60): every AndrewCNN of the model is in flux form — a four-channel last
+        # layer and 10000 * divergence(fluxes) behind it, which the device nets apply themselves (csrc/fluxdiv.hip); the U-Net
+        # has no such form, so with 'DeepInversion' the flag reaches net_mean alone
+        if generator not in ('Andrew', 'DeepInversion') or list(hidden_channels) != [128, 64, 32, 32, 32, 32, 32]:
+            raise NotImplementedError('only generator="Andrew" or "DeepInversion" with the default hidden channels has a device path')
         self._set_regression(regression)
-        self.generator, self.nx, self.div = generator, nx, div
+        self.generator, self.nx, self.div = generator, nx, bool(div)
         self.hidden_channels = hidden_channels
         # needs G.pt, x_scale.json, y_scale.json (D.pt is training-only), and net_mean.pt with regression != 'None'
         self._load(folder, device, generator=generator)

@@ -22,7 +22,7 @@ class Parameterization(QParameterization):
     def _load(self, folder, device=0, generator='Andrew'):
         self.folder = folder
         nets, xs, ys = _weights.load_folder(folder, self.kind, regression=getattr(self, 'regression', 'None') != 'None',
-                                            generator=generator)
+                                            generator=generator, div=bool(getattr(self, 'div', False)))
         self.x_scale = ChannelwiseScaler(xs)
         self.y_scale = ChannelwiseScaler(ys)
         self._gen = Generator(self.kind, nets, xs, ys, device=device)

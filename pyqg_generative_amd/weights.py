@@ -25,6 +25,23 @@ def net_from_state_dict(sd):
     return net
 
 
+def is_flux_form(net):
+    """an AndrewCNN dict whose last convolution writes four channels: AndrewCNN(n_in, 2, div=True) (cnn_tools.py:139-142), the
+    x-fluxes of both layers, then the y-fluxes; its forward is 10000 * divergence(fluxes) (:170-175)"""
+    return int(np.shape(net['conv_w'][7])[0]) == 4
+
+
+def check_flux_form(net, div, name='net'):
+    """ValueError unless the last layer of the AndrewCNN dict is (4, 32, 3, 3) with div, (2, 32, 3, 3) without: a state dict
+    trained in one form must not be evaluated in the other (the shapes differ, so the reference's load_state_dict refuses
+    it too)"""
+    want = (4 if div else 2, 32, 3, 3)
+    got = tuple(np.shape(net['conv_w'][7]))
+    if got != want or tuple(np.shape(net['conv_b'][7])) != want[:1]:
+        raise ValueError(f'{name}: last convolution {got}, but div={bool(div)} takes {want} '
+                         f'({"four flux channels" if div else "two output channels"})')
+
+
 def net_from_npz(d, prefix):
     return dict(conv_w=[np.asarray(d[f'{prefix}w{i}'], np.float32) for i in range(8)],
                 conv_b=[np.asarray(d[f'{prefix}b{i}'], np.float32) for i in range(8)],
@@ -119,12 +136,14 @@ def synthetic_ann(stencil_size=3, hidden_channels=(24, 24), scale_invariant=Fals
                 scale_invariant=bool(scale_invariant), w=w, b=b)
 
 
-def load_folder(folder, kind, regression=False, generator='Andrew'):
+def load_folder(folder, kind, regression=False, generator='Andrew', div=False):
     """Reference model folder -> (nets, x_std, y_std).  kind: 'gan' | 'vae' | 'gz' | 'ols' (OLSModel: net.pt,
     ols_model.py:59-66) | 'ann' (ANNModel: net.pt, scale.json, ann_model.py:68-77 — see load_ann_folder; x_std, y_std are
     the scalars x_scale, y_scale); regression ('gan' / 'vae' trained with
     regression != 'None'): the folder also holds net_mean.pt (cgan_regression.py:98-101, cvae_regression.py:75-76).
-    generator='DeepInversion' (CGAN only, cgan_regression.py:50-53): G.pt is the U-Net, nets[0] its unet_from_state_dict."""
+    generator='DeepInversion' (CGAN only, cgan_regression.py:50-53): G.pt is the U-Net, nets[0] its unet_from_state_dict.
+    div: the model's `div` flag (model_args.json) — every AndrewCNN of the folder must then be in flux form (a (4, 32, 3, 3)
+    last layer), and none without it; a contradiction raises ValueError."""
     import torch
     if generator not in ('Andrew', 'DeepInversion') or (generator == 'DeepInversion' and kind != 'gan'):
         raise ValueError(f'generator={generator!r} is not available for kind {kind!r}')
@@ -136,19 +155,26 @@ def load_folder(folder, kind, regression=False, generator='Andrew'):
     nets = []
     for i, f in enumerate(files):
         sd = torch.load(os.path.join(folder, f), map_location='cpu', weights_only=True)
-        nets.append(unet_from_state_dict(sd) if generator == 'DeepInversion' and i == 0 else net_from_state_dict(sd))
+        if generator == 'DeepInversion' and i == 0:
+            nets.append(unet_from_state_dict(sd))
+        else:
+            nets.append(net_from_state_dict(sd))
+            check_flux_form(nets[-1], div, f)
     return nets, read_scaler_std(os.path.join(folder, 'x_scale.json')), \
         read_scaler_std(os.path.join(folder, 'y_scale.json'))
 
 
-def synthetic(kind, seed=0, regression=False):
-    """Seeded random weights of the architecture (throughput runs without fixtures)."""
+def synthetic(kind, seed=0, regression=False, div=False):
+    """Seeded random weights of the architecture (throughput runs without fixtures).  div: flux-form nets, AndrewCNN(div=True)
+    — a four-channel last layer; layers 1-7 are those of div=False with the same seed (for one net)."""
+    if div and kind == 'gz':
+        raise ValueError("'gz' (MeanVarModel) has no flux form: its variance net is not a divergence")
     rs = np.random.RandomState(seed)
     hidden = [128, 64, 32, 32, 32, 32, 32]
     ks = [5, 5, 3, 3, 3, 3, 3, 3]
 
     def one(n_in):
-        ch = [n_in] + hidden + [2]
+        ch = [n_in] + hidden + [4 if div else 2]
         net = dict(conv_w=[], conv_b=[], bn_g=[], bn_b=[], bn_m=[], bn_v=[])
         for i in range(8):
             cin, cout, k = ch[i], ch[i + 1], ks[i]

@@ -283,6 +283,11 @@ int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n_nets,
                          const float x_std[2], const float y_std[2], int device,
                          qgx_generator **out);
 int qgx_generator_destroy(qgx_generator *g);
+
+/* AndrewCNN nets of any architecture (other hidden_channels, no BatchNorm, no bias): the descriptor qgx_cnn_arch and the entry
+ * point that takes it are declared and documented in qgx_arch.h, which this header includes. */
+#include "qgx_arch.h"
+
 /* QGX_OK if the kernels of the handle's nets (inet >= 0: of that net alone; -1: of all of them) run B members at N x N
  * under the options in force, else QGX_ERR_INVALID with the message the three entry points above give.  No device call. */
 int qgx_generator_size_ok(const qgx_generator *g, int inet, int B, int N);

@@ -37,6 +37,15 @@ class qgx_cnn_weights(C.Structure):
                 ('bn_eps', C.c_float)]
 
 
+class qgx_cnn_arch(C.Structure):
+    _fields_ = [('n_layers', C.c_int32), ('channels', C.c_int32 * 9), ('ksize', C.c_int32 * 8),
+                ('batch_norm', C.c_int32), ('bias', C.c_int32), ('force_generic', C.c_int32),
+                ('conv_w', C.c_void_p * 8), ('conv_b', C.c_void_p * 8),
+                ('bn_gamma', C.c_void_p * 7), ('bn_beta', C.c_void_p * 7),
+                ('bn_mean', C.c_void_p * 7), ('bn_var', C.c_void_p * 7),
+                ('bn_eps', C.c_float)]
+
+
 class qgx_unet_res(C.Structure):
     _fields_ = [('bn_gamma', C.c_void_p), ('bn_beta', C.c_void_p), ('bn_mean', C.c_void_p), ('bn_var', C.c_void_p),
                 ('conv_a_w', C.c_void_p), ('conv_a_b', C.c_void_p),
@@ -148,6 +157,12 @@ SYMBOLS = [
     ('qgx_last_error', C.c_char_p, []),
     ('qgx_version', C.c_char_p, []),
 ]
+# what include/qgx_arch.h declares (SYMBOLS mirrors qgx.h itself): creators that take host descriptors and no caller's device buffer
+ARCH_SYMBOLS = [
+    ('qgx_generator_create_arch', C.c_int, [C.c_int, C.POINTER(qgx_cnn_arch), C.c_int,
+                                            C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                            C.POINTER(C.c_void_p)]),
+]
 
 
 def _load():
@@ -161,7 +176,7 @@ def _load():
     # Load torch's first — torch finds no GPU when it is handed the other runtime.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS:
+    for name, res, args in SYMBOLS + ARCH_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -633,7 +633,7 @@ __global__ void k_absdiff_max(const float *a, const float *b, size_t n, unsigned
 // hipFuncSetAttribute takes microseconds of host time; the single-member step is a chain of 5-15 us kernels whose
 // launches the host has to keep ahead of: the dynamic-LDS cap of a kernel is raised once per kernel, device and host
 // thread, not once per launch (rocprofv3: 14 launches / 116 us of kernels per step were taking 128 us of wall time)
-static int ensure_dynamic_lds(const void *kern, int bytes) {
+int ensure_dynamic_lds(const void *kern, int bytes) {
     static thread_local std::unordered_map<const void *, int> seen[16];
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -931,37 +931,11 @@ void cnn_free_net(NetHost &net) {
 // the summation order).  Measured at one member: the 5x5 layer's split-K kernel + combine 23.6 -> 19.9 us, layer 3 12.1 -> 10.9.
 static bool small_tiles(const qgx_generator *g, int B, int N) { return g->opt_small_tiles && N == 64 && B * 16 <= 64; }
 
-static int choose_rows(int N) {
+int choose_rows(int N) {
     if (N <= 256 && 256 % N == 0) return 256 / N;     // 8 M-tiles
     if (N <= 384 && 384 % N == 0) return 384 / N;     // 12 M-tiles
     return 0;
 }
-
-// The profiler's bracket around one launcher: begin() records the start event of a pair when `layer` is the profiled one,
-// and the stop event is recorded when the scope is left on ANY path, so that qgx_generator_profile_read never meets a
-// start event whose stop event was not recorded.
-struct ProfScope {
-    hipEvent_t stop = nullptr;
-    hipStream_t st = nullptr;
-    int begin(qgx_generator *g, int layer, hipStream_t stream) {
-        if (g->prof_layer != layer) return QGX_OK;
-        // an event pair costs ~6 us of idle GPU on each side of the kernel: bracket every prof_every-th launch only
-        if (g->prof_every > 1 && (g->prof_seen++ % g->prof_every) != 0) return QGX_OK;
-        if (g->prof_used + 2 > g->prof_ev.size()) {
-            for (int i = 0; i < 2; ++i) {
-                hipEvent_t e;
-                QGX_HIP(hipEventCreate(&e));
-                g->prof_ev.push_back(e);
-            }
-        }
-        QGX_HIP(hipEventRecord(g->prof_ev[g->prof_used], stream));
-        stop = g->prof_ev[g->prof_used + 1];
-        st = stream;
-        g->prof_used += 2;
-        return QGX_OK;
-    }
-    ~ProfScope() { if (stop) (void)hipEventRecord(stop, st); }
-};
 
 template <int CIN, int COUT, int KS, int CC, bool PLANAR_IN, bool FINAL, int CSPLIT = 1, int OUTH = 0>
 static int launch_conv(qgx_generator *g, int layer, const LayerHost &L, const float *in, float *out, int B,
@@ -1853,6 +1827,7 @@ static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x
 // the eight convolutions: x planar (B,n_in,N,N) -> y planar (B,n_out,N,N)
 static int cnn_convs(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N, hipStream_t st) {
     int rc;
+    if (net.generic) return cnng_convs(g, net, x, y, B, N, st);      // any other architecture than the shipped one: conv_generic.hip
     if (g->opt_precision && half_path_ok(g, B, N))
 #ifdef QGX_AB
         return g->opt_precision == 1 ? cnn_forward_half<1>(g, net, x, y, B, N, st) : cnn_forward_half<2>(g, net, x, y, B, N, st);
@@ -1917,6 +1892,7 @@ bool cnn_size_ok(const qgx_generator *g, const NetHost &net, int B, int N) {
     const int R = choose_rows(N);
     if (B < 1 || R <= 0 || N % R) return false;
     if (net.flux() && !fluxdiv_size_ok(N)) return false;
+    if (net.generic) return cnng_size_ok(net, B, N);
     if (g->opt_precision && half_path_ok(g, B, N)) {
 #ifdef QGX_AB
         if (rows_h2(N) <= 0) return true;      // kernels of the A/B library's experiments: their launchers decide
@@ -2181,6 +2157,8 @@ extern "C" int qgx_generator_layer2_kernel(const qgx_generator *g, int inet, int
     QGX_REQUIRE(g && kernel, "qgx_generator_layer2_kernel: null argument");
     REFUSE_NON_ANDREW(g, "qgx_generator_layer2_kernel");
     QGX_REQUIRE(inet >= 0 && inet < g->n_nets, "qgx_generator_layer2_kernel: net %d of %d", inet, g->n_nets);
+    QGX_REQUIRE(!g->nets[inet].generic, "qgx_generator_layer2_kernel: net %d runs the generic engine (conv_generic.hip), which has one exact-f32 "
+                "kernel for every layer; the question applies to the shipped architecture's 128 -> 64 5x5 layer", inet);
     *kernel = plan_layer2(g, g->nets[inet], B, N).kernel;
     return QGX_OK;
 }
@@ -2231,6 +2209,12 @@ extern "C" int qgx_generator_profile_read(qgx_generator *g, double *total_ms, in
 
 extern "C" int qgx_generator_set_option(qgx_generator *g, const char *name, int value) {
     QGX_REQUIRE(g && name, "qgx_generator_set_option: null argument");
+    if (g->generic) {          // the generic engine has one exact-f32 kernel family and no variants to select
+        QGX_REQUIRE(!strcmp(name, "precision") && value == 0,
+                    "qgx_generator_set_option('%s'=%d): a handle of qgx_generator_create_arch with a net of another architecture than the shipped one "
+                    "runs exact f32 (precision 0) only: the generic engine has no f16x3 or Winograd path and no kernel variants", name, value);
+        return QGX_OK;
+    }
     if (g->unet || g->ann) {   // every option selects between AndrewCNN kernels (net_mean runs the exact-f32 ones): only precision 0 holds
         QGX_REQUIRE(!strcmp(name, "precision") && value == 0,
                     "qgx_generator_set_option('%s'=%d): a%s generator handle runs exact f32 (precision 0) only; the option applies to the AndrewCNN kernels",

@@ -263,9 +263,9 @@ int generator_reserve(qgx_generator *g, int B, int N) {
         w.cap_elems = need;
         return QGX_OK;
     }
-    const size_t actA = g->unet ? std::max(need * 128, unet_workspace_floats(B, N)) : need * 128;
+    const size_t actA = g->unet ? std::max(need * g->actw[0], unet_workspace_floats(B, N)) : need * g->actw[0];
     QGX_HIP(hipMalloc((void **)&w.actA, actA * sizeof(float)));
-    QGX_HIP(hipMalloc((void **)&w.actB, need * 64 * sizeof(float)));
+    QGX_HIP(hipMalloc((void **)&w.actB, need * g->actw[1] * sizeof(float)));
     QGX_HIP(hipMalloc((void **)&w.X, need * 6 * sizeof(float)));    // (B, 4, N, N), and behind it (B, 2, N, N) for a regression net
     QGX_HIP(hipMalloc((void **)&w.Y0, need * 2 * sizeof(float)));
     QGX_HIP(hipMalloc((void **)&w.Y1, need * 2 * sizeof(float)));
@@ -522,6 +522,51 @@ extern "C" int qgx_generator_create(int kind, const qgx_cnn_weights *nets, int n
     if (rc) return rc;
     for (int n = 0; n < n_nets && !rc; ++n) rc = cnn_pack_net(g->nets[n], &nets[n]);
     if (!rc) rc = cnn_calibrate(g);
+    return hand_out(rc, g, out);
+}
+
+// The same rules per kind as qgx_generator_create, for nets described by their architecture.  A descriptor list that spells
+// the shipped architecture throughout IS qgx_generator_create (one code path, hence the same handle); otherwise the handle is
+// exact f32 only: nets of another architecture are packed for the generic engine (conv_generic.hip), a shipped-architecture
+// net beside them (a GAN's / VAE's net_mean) as ever, and takes conv.hip's exact-f32 kernels, as beside a U-Net.
+extern "C" int qgx_generator_create_arch(int kind, const qgx_cnn_arch *nets, int n_nets, const float x_std[2],
+                                         const float y_std[2], int device, qgx_generator **out) {
+    QGX_REQUIRE(nets && out && x_std && y_std, "qgx_generator_create_arch: null argument");
+    QGX_REQUIRE(kind == QGX_GEN_GAN || kind == QGX_GEN_VAE || kind == QGX_GEN_GZ || kind == QGX_GEN_OLS,
+                "unknown generator kind %d", kind);
+    QGX_REQUIRE(kind == QGX_GEN_GZ ? n_nets == 2 : kind == QGX_GEN_OLS ? n_nets == 1 : (n_nets == 1 || n_nets == 2),
+                "generator kind %d needs %s nets, not %d", kind,
+                kind == QGX_GEN_GZ ? "2" : kind == QGX_GEN_OLS ? "1" : "1 or 2", n_nets);
+    bool all_shipped = true;
+    for (int n = 0; n < n_nets; ++n) {      // every field of every net before anything is allocated
+        if (const int rc = cnn_arch_check(&nets[n], n)) return rc;
+        const int want_in = kind == QGX_GEN_GZ || kind == QGX_GEN_OLS || n == 1 ? 2 : 4;
+        const int n_out = nets[n].channels[nets[n].n_layers];
+        QGX_REQUIRE(nets[n].channels[0] == want_in && (n_out == 2 || kind != QGX_GEN_GZ),
+                    "qgx_cnn_arch (net %d): channels[0] = %d, channels[%d] = %d, expected n_in %d and n_out %s", n, nets[n].channels[0],
+                    nets[n].n_layers, n_out, want_in, kind == QGX_GEN_GZ ? "2" : "2 (or 4: flux form)");
+        all_shipped = all_shipped && cnn_arch_is_shipped(&nets[n]);
+    }
+    if (all_shipped) {
+        qgx_cnn_weights w[2];
+        for (int n = 0; n < n_nets; ++n) cnn_arch_to_weights(&nets[n], &w[n]);
+        return qgx_generator_create(kind, w, n_nets, x_std, y_std, device, out);
+    }
+    qgx_generator *g = nullptr;
+    int rc = new_handle("qgx_generator_create_arch", kind, n_nets, x_std, y_std, device, &g);
+    if (rc) return rc;
+    cnn_exact_f32_only(g);
+    g->generic = 1;
+    for (int n = 0; n < n_nets && !rc; ++n) {
+        if (cnn_arch_is_shipped(&nets[n])) {
+            qgx_cnn_weights w;
+            cnn_arch_to_weights(&nets[n], &w);
+            rc = cnn_pack_net(g->nets[n], &w);
+        } else rc = cnn_pack_net_arch(g->nets[n], &nets[n]);
+    }
+    g->actw[0] = g->actw[1] = 8;
+    for (int n = 0; n < n_nets; ++n)
+        for (int k = 0; k < 2; ++k) g->actw[k] = std::max(g->actw[k], g->nets[n].act_width(k));
     return hand_out(rc, g, out);
 }
 

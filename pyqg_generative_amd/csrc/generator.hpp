@@ -15,6 +15,9 @@ struct LastWeights { float w[3 * 3 * 32 * 2]; };   // [tap][c][2], passed BY VAL
 
 struct LayerHost {
     int cin, cout, ks, coutp, cc, ngroups;
+    // generic engine (conv_generic.hip): K per tap = the input channels padded to 8 (the NHWC pixel stride of the layer's
+    // input; 8 for the planar first layer), and the channels stored per output pixel (cout padded to 8; the last layer: cout)
+    int cinp = 0, cstore = 0;
     LastWeights wv_host[2];   // last layer, VALU kernel layout (kernel argument): output channels (0, 1), and (2, 3) of a flux-form net
     float *wl16 = nullptr, *wl8 = nullptr;   // k_conv3 layout [chunk][tap][g8][h][coutp][4], 16- / 8-channel chunks
     float *w = nullptr, *w32 = nullptr, *bias = nullptr, *scale = nullptr, *shift = nullptr;   // w: 16-ch chunks (or planar), w32: 32-ch chunks
@@ -40,6 +43,17 @@ struct LayerHost {
 struct NetHost {
     int n_in, n_out;       // n_out = 4: a flux-form net (AndrewCNN(n_in, 2, div=True)): the last convolution writes four fluxes
     LayerHost L[8];
+    // qgx_generator_create_arch: any other architecture than the shipped one with BatchNorm and bias runs the generic engine
+    // (conv_generic.hip) on L[0 .. n_layers - 1]; the shipped one keeps generic = false and every layout cnn_pack_net makes
+    bool generic = false;
+    int n_layers = 8, batch_norm = 1, bias = 1;
+    // channels per pixel of the widest activation this net stores in actA (which = 0: layers 1, 3, ...) / actB (layers 2, 4, ...)
+    int act_width(int which) const {
+        if (!generic) return which ? 64 : 128;
+        int w = 8;
+        for (int l = which; l < n_layers - 1; l += 2) w = L[l].cstore > w ? L[l].cstore : w;
+        return w;
+    }
     bool flux() const { return n_out == 4; }
     int y_channels() const { return flux() ? 2 : n_out; }     // channels of AndrewCNN.forward's output
 };
@@ -72,6 +86,8 @@ struct Workspace {
 
 struct qgx_generator {
     int kind, device, n_nets;
+    int generic = 0;               // qgx_generator_create_arch with a net of the generic engine: exact f32 only, as unet / ann
+    int actw[2] = {128, 64};       // channels per pixel of actA / actB: the widest layer of the handle's nets (generator_reserve)
     qgx::UNet *unet = nullptr;     // qgx_generator_create_unet: net 0 is the DeepInversion U-Net (unet.hip), its workspace is actA
     qgx::Ann *ann = nullptr;       // qgx_generator_create_ann: the pointwise stencil network (ann.hip); its only workspace is Y0
     qgx::NetHost nets[2];
@@ -154,6 +170,44 @@ void cnn_exact_f32_only(qgx_generator *g);    // U-Net and ANN handles: a net_me
 int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N, hipStream_t st);
 // whether cnn_forward's launchers take B members at N x N under the options in force (no HIP call)
 bool cnn_size_ok(const qgx_generator *g, const NetHost &net, int B, int N);
+
+// ---- conv_generic.hip: AndrewCNN nets of any admitted architecture (qgx_cnn_arch), exact-f32 MFMA kernels with run-time
+// channel counts; called by generator.hip (check, pack) and conv.hip (the dispatch of cnn_forward / cnn_size_ok)
+int cnn_arch_check(const qgx_cnn_arch *a, int inet);          // every field and required pointer; no HIP call, no allocation
+bool cnn_arch_is_shipped(const qgx_cnn_arch *a);              // [128, 64, 32 x 5], kernels 5, 5, 3 ..., BatchNorm, bias, not forced
+void cnn_arch_to_weights(const qgx_cnn_arch *a, qgx_cnn_weights *w);     // ... such a descriptor as cnn_pack_net takes it
+int cnn_pack_net_arch(NetHost &net, const qgx_cnn_arch *a);
+int cnng_convs(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N, hipStream_t st);
+bool cnng_size_ok(const NetHost &net, int B, int N);
+// conv.hip helpers the generic launchers share
+int ensure_dynamic_lds(const void *kern, int bytes);
+int choose_rows(int N);
+
+// The profiler's bracket around one launcher: begin() records the start event of a pair when `layer` is the profiled one,
+// and the stop event is recorded when the scope is left on ANY path, so that qgx_generator_profile_read never meets a
+// start event whose stop event was not recorded.
+struct ProfScope {
+    hipEvent_t stop = nullptr;
+    hipStream_t st = nullptr;
+    int begin(qgx_generator *g, int layer, hipStream_t stream) {
+        if (g->prof_layer != layer) return QGX_OK;
+        // an event pair costs ~6 us of idle GPU on each side of the kernel: bracket every prof_every-th launch only
+        if (g->prof_every > 1 && (g->prof_seen++ % g->prof_every) != 0) return QGX_OK;
+        if (g->prof_used + 2 > g->prof_ev.size()) {
+            for (int i = 0; i < 2; ++i) {
+                hipEvent_t e;
+                QGX_HIP(hipEventCreate(&e));
+                g->prof_ev.push_back(e);
+            }
+        }
+        QGX_HIP(hipEventRecord(g->prof_ev[g->prof_used], stream));
+        stop = g->prof_ev[g->prof_used + 1];
+        st = stream;
+        g->prof_used += 2;
+        return QGX_OK;
+    }
+    ~ProfScope() { if (stop) (void)hipEventRecord(stop, st); }
+};
 
 // ---- fluxdiv.hip: y (B,2,N,N) = 10000 div F, F (B,4,N,N) = [fx1, fx2, fy1, fy2], float32 spectral, one kernel ----
 bool fluxdiv_size_ok(int N);

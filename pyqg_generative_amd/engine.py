@@ -28,11 +28,14 @@ class Generator:
     KINDS = {'gan': _lib.GEN_GAN, 'vae': _lib.GEN_VAE, 'gz': _lib.GEN_GZ, 'ols': _lib.GEN_OLS, 'ann': _lib.GEN_ANN}
     NOISE_FREE = ('ols', 'ann')
 
-    def __init__(self, kind, nets, x_std, y_std, device=0):
+    def __init__(self, kind, nets, x_std, y_std, device=0, force_generic=False):
         """nets: list of dicts with float32 numpy arrays
         conv_w[8], conv_b[8], bn_g[7], bn_b[7], bn_m[7], bn_v[7] (PyTorch layouts).  kind 'gan' also takes the DeepInversion
-        U-Net as nets[0] (a weights.unet_from_state_dict / weights.synthetic_unet dict), optionally followed by net_mean."""
-        from .weights import is_unet
+        U-Net as nets[0] (a weights.unet_from_state_dict / weights.synthetic_unet dict), optionally followed by net_mean.
+        A net of another architecture than the shipped one (weights.net_from_state_dict_arch / synthetic_arch: other
+        hidden_channels, no BatchNorm, no bias) sends the handle through qgx_generator_create_arch: such nets run the generic
+        engine, and the handle is exact f32 only.  force_generic (measurements, tests): the generic engine for every net."""
+        from .weights import is_unet, is_shipped_arch
         self.kind = kind
         self.device = device
         self._h = C.c_void_p(0)
@@ -62,12 +65,50 @@ class Generator:
                 self._cnn_struct(nets[1], mean, keep)
             check(lib.qgx_generator_create_unet(C.byref(u), C.byref(mean) if mean is not None else None, xs, ys, device,
                                                 C.byref(self._h)))
+        elif force_generic or not all(is_shipped_arch(net) for net in nets):
+            arr = (_lib.qgx_cnn_arch * len(nets))()
+            for n, net in enumerate(nets):
+                self._arch_struct(net, arr[n], keep, force_generic)
+            check(lib.qgx_generator_create_arch(self.KINDS[kind], arr, len(nets), xs, ys, device, C.byref(self._h)))
         else:
             arr = (_lib.qgx_cnn_weights * len(nets))()
             for n, net in enumerate(nets):
                 self._cnn_struct(net, arr[n], keep)
             check(lib.qgx_generator_create(self.KINDS[kind], arr, len(nets), xs, ys, device, C.byref(self._h)))
         self.n_in = 2 if kind in ('gz', 'ols') else 4
+
+    @staticmethod
+    def _arch_struct(net, a, keep, force_generic=False):
+        """AndrewCNN dict of any architecture -> qgx_cnn_arch (host pointers into `keep`); absent biases / BatchNorm stay NULL"""
+        from .weights import net_arch
+        arch = net_arch(net)
+        n = len(net['conv_w'])
+        if not 2 <= n <= 8:
+            raise ValueError(f'an AndrewCNN has 2 ... 8 convolutions, not {n}')
+        a.n_layers = n
+        a.channels[0] = int(net['conv_w'][0].shape[1])
+        for l in range(n):
+            a.channels[l + 1] = int(net['conv_w'][l].shape[0])
+            a.ksize[l] = int(net['conv_w'][l].shape[-1])
+        a.batch_norm, a.bias, a.force_generic = int(bool(arch['batch_norm'])), int(bool(arch['bias'])), int(bool(force_generic))
+        a.bn_eps = 1e-5
+        for l in range(n):
+            cw = np.ascontiguousarray(net['conv_w'][l], dtype=np.float32)
+            want = (a.channels[l + 1], a.channels[l], a.ksize[l], a.ksize[l])
+            if cw.shape != want:
+                raise ValueError(f'conv_w[{l}] has shape {cw.shape}, the layers around it make it {want}')
+            keep.append(cw)
+            a.conv_w[l] = cw.ctypes.data
+            if arch['bias']:
+                cb = np.ascontiguousarray(net['conv_b'][l], dtype=np.float32).reshape(a.channels[l + 1])
+                keep.append(cb)
+                a.conv_b[l] = cb.ctypes.data
+        if arch['batch_norm']:
+            for l in range(n - 1):
+                for field, key in (('bn_gamma', 'bn_g'), ('bn_beta', 'bn_b'), ('bn_mean', 'bn_m'), ('bn_var', 'bn_v')):
+                    v = np.ascontiguousarray(net[key][l], dtype=np.float32).reshape(a.channels[l + 1])
+                    keep.append(v)
+                    getattr(a, field)[l] = v.ctypes.data
 
     @staticmethod
     def _cnn_struct(net, w, keep):

@@ -133,10 +133,13 @@ class CGANRegression(_LatentCNN):
         # AndrewCNN(2, 2) (:59-60).  div=True (:51, :60): every AndrewCNN of the model is in flux form — a four-channel last
         # layer and 10000 * divergence(fluxes) behind it, which the device nets apply themselves (csrc/fluxdiv.hip); the U-Net
         # has no such form, so with 'DeepInversion' the flag reaches net_mean alone
-        if generator not in ('Andrew', 'DeepInversion') or list(hidden_channels) != [128, 64, 32, 32, 32, 32, 32]:
-            raise NotImplementedError('only generator="Andrew" or "DeepInversion" with the default hidden channels has a device path')
+        # hidden_channels reaches the 'Andrew' generator alone (:51): the U-Net has no such argument, and net_mean keeps the
+        # default widths (:60).  Widths other than the default run the generic engine (csrc/conv_generic.hip).
+        if generator not in ('Andrew', 'DeepInversion'):
+            raise NotImplementedError('only generator="Andrew" or "DeepInversion" has a device path')
+        from ..weights import check_hidden_channels, SHIPPED_HIDDEN
         self._set_regression(regression)
         self.generator, self.nx, self.div = generator, nx, bool(div)
-        self.hidden_channels = hidden_channels
+        self.hidden_channels = check_hidden_channels(hidden_channels) if generator == 'Andrew' else list(SHIPPED_HIDDEN)
         # needs G.pt, x_scale.json, y_scale.json (D.pt is training-only), and net_mean.pt with regression != 'None'
         self._load(folder, device, generator=generator)

@@ -12,9 +12,9 @@ class MeanVarModel(Parameterization):
     NET_NAMES = ('net_mean', 'net_var')
 
     def __init__(self, folder='model', hidden_channels=[128, 64, 32, 32, 32, 32, 32], device=0):
-        if list(hidden_channels) != [128, 64, 32, 32, 32, 32, 32]:
-            raise NotImplementedError('only the shipped channel configuration has a device path')
-        self.hidden_channels = hidden_channels
+        # both nets take hidden_channels (mean_var_model.py:35-36); other widths than the default run the generic engine
+        from ..weights import check_hidden_channels
+        self.hidden_channels = check_hidden_channels(hidden_channels)
         self._load(folder, device)          # needs net_mean.pt and net_var.pt
 
     def generate_latent_noise(self, ny, nx):

@@ -6,6 +6,7 @@ import numpy as np
 
 from .parameterization import Parameterization
 from ..tools.cnn_tools import apply_function
+from ..weights import check_hidden_channels
 
 HIDDEN = [128, 64, 32, 32, 32, 32, 32]
 
@@ -16,12 +17,14 @@ class OLSModel(Parameterization):
 
     def __init__(self, div=False, batch_norm=True, bias=True, final_activation='None',
                  hidden_channels=[128, 64, 32, 32, 32, 32, 32], folder='model', device=0):
-        # AndrewCNN(2, 2) with the default block options is what the device kernels implement (ols_model.py:29-31)
-        if div or not batch_norm or not bias or final_activation != 'None' or list(hidden_channels) != HIDDEN:
-            raise NotImplementedError('only div=False, batch_norm=True, bias=True, final_activation="None" with the default '
-                                      'hidden channels has a device path')
-        self.div, self.batch_norm, self.bias = div, batch_norm, bias
-        self.final_activation, self.hidden_channels = final_activation, hidden_channels
+        # AndrewCNN(2, 2, batch_norm=, bias=, div=, hidden_channels=) (ols_model.py:29-31).  The default widths with BatchNorm
+        # and bias run the shipped kernels, every other admitted architecture (1 ... 7 widths of 1 ... 256) the generic engine;
+        # div=True: a four-channel last layer and the device's divergence behind it
+        if final_activation != 'None':
+            raise NotImplementedError(f'final_activation={final_activation!r} has no device path: the reference evaluates the '
+                                      "string with eval(), an arbitrary function of the output; only 'None' runs")
+        self.div, self.batch_norm, self.bias = bool(div), bool(batch_norm), bool(bias)
+        self.final_activation, self.hidden_channels = final_activation, check_hidden_channels(hidden_channels)
         # the reference builds an untrained net when the folder holds none (ols_model.py:57-60); there is no training here
         if not os.path.exists(os.path.join(folder, 'net.pt')):
             raise FileNotFoundError(f'{os.path.join(folder, "net.pt")} is missing: OLSModel needs a trained model folder '

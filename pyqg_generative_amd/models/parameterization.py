@@ -22,7 +22,9 @@ class Parameterization(QParameterization):
     def _load(self, folder, device=0, generator='Andrew'):
         self.folder = folder
         nets, xs, ys = _weights.load_folder(folder, self.kind, regression=getattr(self, 'regression', 'None') != 'None',
-                                            generator=generator, div=bool(getattr(self, 'div', False)))
+                                            generator=generator, div=bool(getattr(self, 'div', False)),
+                                            hidden_channels=getattr(self, 'hidden_channels', None),
+                                            batch_norm=bool(getattr(self, 'batch_norm', True)), bias=bool(getattr(self, 'bias', True)))
         self.x_scale = ChannelwiseScaler(xs)
         self.y_scale = ChannelwiseScaler(ys)
         self._gen = Generator(self.kind, nets, xs, ys, device=device)

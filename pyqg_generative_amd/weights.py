@@ -9,6 +9,18 @@ import os
 import numpy as np
 
 
+class ArchitectureMismatch(ValueError, NotImplementedError):
+    """A model folder whose state dict is not the one the constructor's arguments describe (other widths, flags or form).  It is a
+    ValueError — the arguments are wrong for this folder, which is what the loaders have always raised — and a
+    NotImplementedError: the model classes raise that for every configuration that does not run, and there is no conversion of a
+    net trained with one architecture into another, so callers that catch either see it."""
+
+
+class UntrainedFolder(NotImplementedError):
+    """A model folder without the trained files of its class.  The reference builds an untrained model there, to be fitted; there
+    is no training on the device."""
+
+
 def net_from_state_dict(sd):
     """AndrewCNN state_dict (keys conv.{3i}.weight/bias, conv.{3i+2}.* BatchNorm) -> dict."""
     get = lambda k: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], 'detach') else sd[k],
@@ -28,7 +40,7 @@ def net_from_state_dict(sd):
 def is_flux_form(net):
     """an AndrewCNN dict whose last convolution writes four channels: AndrewCNN(n_in, 2, div=True) (cnn_tools.py:139-142), the
     x-fluxes of both layers, then the y-fluxes; its forward is 10000 * divergence(fluxes) (:170-175)"""
-    return int(np.shape(net['conv_w'][7])[0]) == 4
+    return int(np.shape(net['conv_w'][-1])[0]) == 4
 
 
 def check_flux_form(net, div, name='net'):
@@ -38,8 +50,139 @@ def check_flux_form(net, div, name='net'):
     want = (4 if div else 2, 32, 3, 3)
     got = tuple(np.shape(net['conv_w'][7]))
     if got != want or tuple(np.shape(net['conv_b'][7])) != want[:1]:
-        raise ValueError(f'{name}: last convolution {got}, but div={bool(div)} takes {want} '
-                         f'({"four flux channels" if div else "two output channels"})')
+        raise ArchitectureMismatch(f'{name}: last convolution {got}, but div={bool(div)} takes {want} '
+                                   f'({"four flux channels" if div else "two output channels"}): the state dict is that of a '
+                                   f'model trained with div={not bool(div)}')
+
+
+SHIPPED_HIDDEN = [128, 64, 32, 32, 32, 32, 32]
+KERNELS = [5, 5, 3, 3, 3, 3, 3, 3]           # AndrewCNN's default `kernels` (cnn_tools.py:131): the only ones a model class passes
+
+
+def check_hidden_channels(hidden_channels):
+    """-> list of ints; ValueError unless it is 1 ... 7 widths of 1 ... 256 (what the device engine admits: the reference's
+    default kernels list has eight entries, so AndrewCNN itself takes at most seven hidden layers)"""
+    hidden = [int(h) for h in hidden_channels]
+    if not 1 <= len(hidden) <= 7 or any(h != v for h, v in zip(hidden, hidden_channels)):
+        raise ValueError(f'hidden_channels={list(hidden_channels)!r}: expected 1 ... 7 integer widths')
+    if any(not 1 <= h <= 256 for h in hidden):
+        raise ValueError(f'hidden_channels={hidden!r}: every width must be 1 ... 256')
+    return hidden
+
+
+def arch_kernels(hidden_channels):
+    """kernel size of each of the len(hidden_channels) + 1 convolutions (cnn_tools.py:146-158)"""
+    n = len(hidden_channels)
+    return KERNELS[:n] + [KERNELS[-1]]
+
+
+def arch_shapes(n_in, hidden_channels, batch_norm=True, bias=True, div=False, n_out=2):
+    """every parameter / buffer of AndrewCNN(n_in, n_out, batch_norm=, bias=, div=, hidden_channels=)'s state dict -> shape
+    (num_batches_tracked left out).  Blocks are Conv2d -> ReLU [-> BatchNorm2d] in one nn.Sequential `conv`, so convolution l
+    sits at index 3 l with BatchNorm (its BatchNorm at 3 l + 2) and at 2 l without; the last block is the convolution alone."""
+    hidden = check_hidden_channels(hidden_channels)
+    ch = [int(n_in)] + hidden + [2 * n_out if div else n_out]
+    ks = arch_kernels(hidden)
+    step = 3 if batch_norm else 2
+    s = {}
+    for l in range(len(ch) - 1):
+        s[f'conv.{step * l}.weight'] = (ch[l + 1], ch[l], ks[l], ks[l])
+        if bias:
+            s[f'conv.{step * l}.bias'] = (ch[l + 1],)
+        if batch_norm and l < len(ch) - 2:
+            for k in ('weight', 'bias', 'running_mean', 'running_var'):
+                s[f'conv.{step * l + 2}.{k}'] = (ch[l + 1],)
+    return s
+
+
+def net_from_state_dict_arch(sd, n_in, hidden_channels=SHIPPED_HIDDEN, batch_norm=True, bias=True, div=False, name='net'):
+    """AndrewCNN(n_in, 2, batch_norm=, bias=, div=, hidden_channels=) state dict -> dict(conv_w, conv_b, bn_g, bn_b, bn_m,
+    bn_v, arch): conv_b is empty without bias, the bn_* lists without BatchNorm.  Every key and shape is checked against the
+    constructor's arguments — a state dict trained with other widths, flags or form (div) raises ValueError naming the key,
+    as the reference's load_state_dict would refuse it."""
+    get = lambda k: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], 'detach') else sd[k], dtype=np.float32)
+    hidden = check_hidden_channels(hidden_channels)
+    want = arch_shapes(n_in, hidden, batch_norm, bias, div)
+    have = {k for k in sd.keys() if not k.endswith('num_batches_tracked')}
+    what = f'AndrewCNN({n_in}, 2, batch_norm={bool(batch_norm)}, bias={bool(bias)}, div={bool(div)}, hidden_channels={hidden})'
+    for k in want:
+        if k not in have:
+            raise ArchitectureMismatch(f'{name}: key {k!r} is missing: not a state dict of {what}')
+    for k in sorted(have):
+        if k not in want:
+            raise ArchitectureMismatch(f'{name}: unexpected key {k!r}: not a state dict of {what}')
+    for k, shape in want.items():
+        if tuple(get(k).shape) != shape:
+            raise ArchitectureMismatch(f'{name}: {k} has shape {tuple(get(k).shape)}, {what} has {shape}')
+    step = 3 if batch_norm else 2
+    n = len(hidden) + 1
+    net = dict(conv_w=[get(f'conv.{step * l}.weight') for l in range(n)],
+               conv_b=[get(f'conv.{step * l}.bias') for l in range(n)] if bias else [],
+               bn_g=[], bn_b=[], bn_m=[], bn_v=[],
+               arch=dict(n_in=int(n_in), hidden_channels=hidden, batch_norm=bool(batch_norm), bias=bool(bias), div=bool(div)))
+    if batch_norm:
+        for l in range(n - 1):
+            net['bn_g'].append(get(f'conv.{step * l + 2}.weight'))
+            net['bn_b'].append(get(f'conv.{step * l + 2}.bias'))
+            net['bn_m'].append(get(f'conv.{step * l + 2}.running_mean'))
+            net['bn_v'].append(get(f'conv.{step * l + 2}.running_var'))
+    return net
+
+
+def net_arch(net):
+    """the architecture of an AndrewCNN dict: its 'arch' entry, or — the dicts of net_from_state_dict / net_from_npz /
+    synthetic, which carry none — read off the arrays (BatchNorm and bias present)"""
+    if 'arch' in net:
+        return net['arch']
+    w = net['conv_w']
+    return dict(n_in=int(np.shape(w[0])[1]), hidden_channels=[int(np.shape(a)[0]) for a in w[:-1]],
+                batch_norm=len(net.get('bn_g', ())) > 0, bias=len(net.get('conv_b', ())) > 0, div=int(np.shape(w[-1])[0]) == 4)
+
+
+def is_shipped_arch(net):
+    """whether the dict is the architecture qgx_generator_create takes: the default widths with BatchNorm and bias"""
+    a = net_arch(net)
+    return list(a['hidden_channels']) == SHIPPED_HIDDEN and bool(a['batch_norm']) and bool(a['bias'])
+
+
+def state_dict_from_net(net):
+    """the inverse of net_from_state_dict_arch (numpy arrays under the reference's keys): fixtures and temporary model
+    folders of the tests are written from synthetic_arch nets with it"""
+    a = net_arch(net)
+    step = 3 if a['batch_norm'] else 2
+    sd = {}
+    for l, w in enumerate(net['conv_w']):
+        sd[f'conv.{step * l}.weight'] = np.asarray(w, np.float32)
+        if a['bias']:
+            sd[f'conv.{step * l}.bias'] = np.asarray(net['conv_b'][l], np.float32)
+        if a['batch_norm'] and l < len(net['conv_w']) - 1:
+            for k, key in (('weight', 'bn_g'), ('bias', 'bn_b'), ('running_mean', 'bn_m'), ('running_var', 'bn_v')):
+                sd[f'conv.{step * l + 2}.{k}'] = np.asarray(net[key][l], np.float32)
+    return sd
+
+
+def synthetic_arch(n_in, hidden_channels, batch_norm=True, bias=True, div=False, seed=0):
+    """Seeded weights of AndrewCNN(n_in, 2, batch_norm=, bias=, div=, hidden_channels=) from the legacy RandomState stream,
+    He-scaled like `synthetic` (conv weight, bias, BatchNorm weight, bias, running mean, running var per block, in that
+    order): fixtures store net_checksum instead of weights."""
+    hidden = check_hidden_channels(hidden_channels)
+    rs = np.random.RandomState(seed)
+    ch = [int(n_in)] + hidden + [4 if div else 2]
+    ks = arch_kernels(hidden)
+    n = len(ch) - 1
+    net = dict(conv_w=[], conv_b=[], bn_g=[], bn_b=[], bn_m=[], bn_v=[],
+               arch=dict(n_in=int(n_in), hidden_channels=hidden, batch_norm=bool(batch_norm), bias=bool(bias), div=bool(div)))
+    for i in range(n):
+        cin, cout, k = ch[i], ch[i + 1], ks[i]
+        net['conv_w'].append((rs.randn(cout, cin, k, k) * np.sqrt(2.0 / (cin * k * k))).astype('float32'))
+        if bias:
+            net['conv_b'].append((0.1 * rs.randn(cout)).astype('float32'))
+        if batch_norm and i < n - 1:
+            net['bn_g'].append((1 + 0.1 * rs.randn(cout)).astype('float32'))
+            net['bn_b'].append((0.1 * rs.randn(cout)).astype('float32'))
+            net['bn_m'].append((0.5 + 0.1 * rs.randn(cout)).astype('float32'))
+            net['bn_v'].append((0.5 + 0.2 * rs.rand(cout)).astype('float32'))
+    return net
 
 
 def net_from_npz(d, prefix):
@@ -136,15 +279,21 @@ def synthetic_ann(stencil_size=3, hidden_channels=(24, 24), scale_invariant=Fals
                 scale_invariant=bool(scale_invariant), w=w, b=b)
 
 
-def load_folder(folder, kind, regression=False, generator='Andrew', div=False):
+def load_folder(folder, kind, regression=False, generator='Andrew', div=False, hidden_channels=None, batch_norm=True, bias=True):
     """Reference model folder -> (nets, x_std, y_std).  kind: 'gan' | 'vae' | 'gz' | 'ols' (OLSModel: net.pt,
     ols_model.py:59-66) | 'ann' (ANNModel: net.pt, scale.json, ann_model.py:68-77 — see load_ann_folder; x_std, y_std are
     the scalars x_scale, y_scale); regression ('gan' / 'vae' trained with
     regression != 'None'): the folder also holds net_mean.pt (cgan_regression.py:98-101, cvae_regression.py:75-76).
     generator='DeepInversion' (CGAN only, cgan_regression.py:50-53): G.pt is the U-Net, nets[0] its unet_from_state_dict.
     div: the model's `div` flag (model_args.json) — every AndrewCNN of the folder must then be in flux form (a (4, 32, 3, 3)
-    last layer), and none without it; a contradiction raises ValueError."""
+    last layer), and none without it; a contradiction raises ValueError.
+    hidden_channels / batch_norm / bias: the architecture arguments the model was constructed with (model_args.json).  As in
+    the reference they reach OLSModel's net (all three), the generator / decoder of a GAN / VAE and both nets of a GZ model
+    (hidden_channels); a GAN's / VAE's net_mean always has the default widths (cgan_regression.py:60, cvae_regression.py:50).
+    With any of them off the defaults the state dicts go through net_from_state_dict_arch, which checks every key and shape."""
     import torch
+    hidden = SHIPPED_HIDDEN if hidden_channels is None else check_hidden_channels(hidden_channels)
+    generic = hidden != SHIPPED_HIDDEN or not batch_norm or not bias
     if generator not in ('Andrew', 'DeepInversion') or (generator == 'DeepInversion' and kind != 'gan'):
         raise ValueError(f'generator={generator!r} is not available for kind {kind!r}')
     if kind == 'ann':
@@ -153,10 +302,18 @@ def load_folder(folder, kind, regression=False, generator='Andrew', div=False):
     if regression and kind in ('gan', 'vae'):
         files = files + ['net_mean.pt']
     nets = []
+    for f in files:
+        if not os.path.exists(os.path.join(folder, f)):
+            raise UntrainedFolder(f'{os.path.join(folder, f)} is missing: the reference builds an untrained model there, to be fitted, '
+                                  'and there is no training on the device.  Only trained folders load, with the arguments they were '
+                                  "trained with (model_args.json; the reference's defaults: div=False, batch_norm=True, bias=True, "
+                                  f'hidden_channels={SHIPPED_HIDDEN})')
     for i, f in enumerate(files):
         sd = torch.load(os.path.join(folder, f), map_location='cpu', weights_only=True)
         if generator == 'DeepInversion' and i == 0:
             nets.append(unet_from_state_dict(sd))
+        elif generic and not (kind in ('gan', 'vae') and i == 1):
+            nets.append(net_from_state_dict_arch(sd, 4 if kind in ('gan', 'vae') else 2, hidden, batch_norm, bias, div, name=f))
         else:
             nets.append(net_from_state_dict(sd))
             check_flux_form(nets[-1], div, f)
@@ -298,9 +455,10 @@ def net_checksum(net):
     running mean, running var), first 16 hex digits"""
     import hashlib
     h = hashlib.sha256()
-    for i in range(8):
-        arrays = [net['conv_w'][i], net['conv_b'][i]]
-        if i < 7:
+    n = len(net['conv_w'])               # a net of another architecture (synthetic_arch): fewer blocks, BatchNorm / bias absent
+    for i in range(n):
+        arrays = [net['conv_w'][i]] + ([net['conv_b'][i]] if len(net['conv_b']) else [])
+        if i < n - 1 and len(net['bn_g']):
             arrays += [net['bn_g'][i], net['bn_b'][i], net['bn_m'][i], net['bn_v'][i]]
         for a in arrays:
             h.update(np.ascontiguousarray(a, dtype=np.float32).tobytes())

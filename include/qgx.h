@@ -516,6 +516,12 @@ int qgx_histogram(const void *x_dev, int is_double, int64_t R, int64_t T, int64_
                   const double *edges_dev, int nbins, int flags, double scale, void *work_dev, size_t work_bytes,
                   int64_t *counts_dev, double *stats_dev, void *stream);
 
+/* ---- flow statistics ---------------------------------------------------------
+ * The derived fields omega, KE, Ens, Vabs and the plane sums of KE behind dataset_statistics / dataset_smart_read
+ * (tools/comparison_tools.py:197-410): the two entry points are declared and documented in qgx_stats.h, which this header
+ * includes. */
+#include "qgx_stats.h"
+
 /* ---- latent noise ------------------------------------------------------------
  * z <- a z + b xi with xi ~ N(0,1) from Philox4x32-10 (stochastic_pyqg.py:43-49).  z: (B, n_per_member) float or double,
  * n_per_member a positive multiple of 4; a == 0 overwrites z (its previous contents are not read).  Counter of the four

@@ -163,6 +163,12 @@ ARCH_SYMBOLS = [
                                             C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                             C.POINTER(C.c_void_p)]),
 ]
+# what include/qgx_stats.h declares: the derived flow fields behind dataset_statistics / dataset_smart_read
+STATS_SYMBOLS = [
+    ('qgx_flow_features_workspace', C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_size_t)]),
+    ('qgx_flow_features', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+]
 
 
 def _load():
@@ -176,7 +182,7 @@ def _load():
     # Load torch's first — torch finds no GPU when it is handed the other runtime.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + ARCH_SYMBOLS:
+    for name, res, args in SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

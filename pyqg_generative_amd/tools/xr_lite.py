@@ -14,7 +14,10 @@ once against ``xr.Dataset`` / ``xr.DataArray`` / ``xr.concat`` and runs on eithe
   broadcast against the trailing axes), positional ``__getitem__``;
 * ``concat(objs, dim)`` along an existing or a new dimension; variables without ``dim`` are
   broadcast along it, as xarray's default ``data_vars='all'`` does;
-* ``to_netcdf`` through scipy (classic format, real variables only).
+* ``to_netcdf`` through scipy (classic format, real variables only);
+* ``open_dataset``, ``open_mfdataset(paths, combine='nested', concat_dim=...)`` and ``merge``, through
+  ``scipy.io.netcdf_file``: they read what ``to_netcdf`` here writes, i.e. the classic format.  The reference's own files
+  are NETCDF4 (HDF5); those cannot be read without xarray and its netCDF4 / h5netcdf engine.
 
 With xarray importable ``tools.simulate.dataset_backend()`` returns the real package and this
 module is unused.
@@ -347,4 +350,66 @@ def concat(objs, dim):
             out._coords[k] = c
     for k in first._vars:
         out._vars[k] = _concat_arrays([d._vars[k] for d in objs], dim, n_each)
+    return out
+
+
+# ---- reading ------------------------------------------------------------------------------------------------------
+def _text(v):
+    return v.decode() if isinstance(v, bytes) else v
+
+
+def open_dataset(path, **_ignored):
+    """the Dataset ``to_netcdf`` wrote to ``path`` (classic netCDF; values are copied, the file is closed again).  A variable
+    named after its only dimension is a coordinate.  xarray's keyword arguments (decode_times, chunks ...) are accepted and
+    ignored: nothing is decoded and nothing is lazy.  NETCDF4 files — the reference's own — are refused by scipy with a
+    message naming the format; they need xarray."""
+    from scipy.io import netcdf_file
+    out = Dataset()
+    with netcdf_file(path, 'r', mmap=False) as f:
+        for k, v in f.variables.items():
+            data = np.array(v.data)
+            data = data.astype(data.dtype.newbyteorder('='))
+            attrs = {ak: _text(av) for ak, av in v._attributes.items()}
+            a = DataArray(data, dims=v.dimensions, attrs=attrs, name=k)
+            if a.dims == (k,):
+                out._coords[k] = a
+            else:
+                out._vars[k] = a
+        out.attrs = {ak: _text(av) for ak, av in f._attributes.items()}
+    return out
+
+
+def open_mfdataset(paths, combine='nested', concat_dim=None, **_ignored):
+    """the files of ``paths`` (a glob pattern, sorted, or a list of paths) concatenated along ``concat_dim`` in that order,
+    as ``xr.open_mfdataset(paths, combine='nested', concat_dim=...)``: a file without the dimension contributes one entry"""
+    import glob
+    if combine != 'nested' or concat_dim is None:
+        raise NotImplementedError("open_mfdataset: only combine='nested' with a concat_dim")
+    files = sorted(glob.glob(paths)) if isinstance(paths, str) else list(paths)
+    if not files:
+        raise OSError(f'no files to open: {paths!r}')
+    out = concat([open_dataset(f) for f in files], concat_dim)
+    # a file cut out of an ensemble (isel(run=i)) carries its member id as a scalar: concatenated, it is the coordinate
+    if concat_dim in out._vars and out._vars[concat_dim].dims == (concat_dim,):
+        out._coords[concat_dim] = out._vars.pop(concat_dim)
+    return out
+
+
+def _same(a, b):
+    return a.dims == b.dims and a.shape == b.shape and np.array_equal(a.values, b.values, equal_nan=a.values.dtype.kind == 'f')
+
+
+def merge(objects):
+    """the union of the datasets' coordinates and variables (attributes of the first); a name that occurs twice must hold
+    the same values (xarray's compat='no_conflicts' for variables without missing values), else ValueError"""
+    objects = list(objects)
+    out = Dataset(attrs=dict(objects[0].attrs) if objects else None)
+    for ds in objects:
+        for tgt, src in ((out._coords, ds._coords), (out._vars, ds._vars)):
+            for k, a in src.items():
+                other = out._coords.get(k, out._vars.get(k))
+                if other is None:
+                    tgt[k] = a
+                elif not _same(other, a):
+                    raise ValueError(f'conflicting values for variable {k!r} on objects to be combined')
     return out

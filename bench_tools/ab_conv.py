@@ -11,15 +11,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# the A/B library (make -C pyqg_generative_amd/csrc ab) carries every kernel variant; the product library only
-# the fastest path per layer and size
-_AB = os.path.join(ROOT, 'pyqg_generative_amd', 'libqgx_ab.so')
-if 'QGX_LIB' not in os.environ and os.path.exists(_AB):
-    os.environ['QGX_LIB'] = _AB
 import pyqg_generative_amd as qa
 from pyqg_generative_amd import weights
 
-OPTS = {'chunk': 32, 'last_valu': 1, 'first_split': 2, 'v3': -1, 'precision': 0, 'ascale_log2': 0, 'first_h': 1, 'half_nw': 8, 'member_chunk': 0, 'res': 1, 'h2': 3, 'pair': 1, 'fuse': 3, 'half_min_tiles': 1, 'h3': 0, 'last_rows': 0, 'part_max_tiles': 96, 'fold': 1, 'h2_grid': 0, 'h4': 0, 'prio_alt': 1, 'h2_w8': 3, 'h2_tw32': 0, 'pair_lp': 1, 'wino_pl': 0, 'wino': 1, 'wino_min_tiles': 48, 'fuse96': 2, 'wino_rows96': 0, 'h2_rows96': 0, 'small_tiles': 1, 'wino_rows64': 0}      # option -> default
+OPTS = {'chunk': 32, 'last_valu': 1, 'first_split': 2, 'v3': -1, 'precision': 0, 'ascale_log2': 0, 'first_h': 1, 'member_chunk': 0, 'pair': 1, 'fuse': 3, 'half_min_tiles': 1, 'last_rows': 0, 'part_max_tiles': 96, 'fold': 1, 'h2_grid': 0, 'prio_alt': 1, 'h2_w8': 3, 'h2_tw32': 0, 'wino': 1, 'wino_min_tiles': 48, 'fuse96': 2, 'wino_rows96': 0, 'h2_rows96': 0, 'small_tiles': 1, 'wino_rows64': 0}      # option -> default
 MAC = [12800, 204800, 18432, 9216, 9216, 9216, 9216, 576]
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Developer tool: in-kernel timeline of one 16-bit conv layer (k_convh / k_convh_res) from s_memtime stamps.
+"""Developer tool: in-kernel timeline of one 16-bit conv layer (k_convh2, k_convh_pair, k_convh_first) from s_memtime stamps.
     python bench_tools/conv_stamps.py MEMBERS LAYER
 Needs the diagnostic library: make -C pyqg_generative_amd/csrc stamps; QGX_LIB=.../libqgx_stamps.so"""
 import ctypes as C

@@ -1,5 +1,5 @@
 // Developer tool: what does v_mfma_f32_32x32x16_f16 sustain on random data on this device with the
-// operand traffic of k_convh (8 waves per workgroup, 1 workgroup per CU, 4 accumulators per wave)?
+// operand traffic of the 16-bit conv kernels (conv_half.hpp; 8 waves per workgroup, 1 workgroup per CU, 4 accumulators per wave)?
 //   mode 0: operands in registers          mode 1: + 8 ds_read_b128 per tap (12 MFMAs), as the f16x3 loop
 //   mode 2: as 1 with 8 MFMAs per tap (the plain-f16 loop)     mode 3: 16x16x32 shape, 16 accumulators, 8 reads / 24 MFMAs
 //   mode 4: 32x32x16, 4x2 tiles per wave (8 accumulators), 12 reads / 24 MFMAs, 4 waves per workgroup

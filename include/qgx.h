@@ -397,9 +397,10 @@ int qgx_real_fma(const double *a_dev, const double *b_dev, double *out_dev, size
 /* sum += y, sumsq += y*y over Monte-Carlo samples (generate_mean_var, cgan_regression.py:139-146;
  * cvae_regression.py:120-126), accumulated in float64 */
 int qgx_moments_accumulate(const float *y_dev, double *sum_dev, double *sumsq_dev, size_t n, void *stream);
-/* kernel-variant switches for in-process A/B measurement (bench_tools/ab_conv.py): "chunk" (16|32 input
- * channels staged per pass of k_conv), "v3" (-1 auto | 0 | 1 | 2: LDS-operand kernel k_conv3),
- * "last_valu" (0|1), "first_split" (1|2|4 output-channel slices of the first layer). */
+/* kernel-variant switches for in-process A/B measurement (bench_tools/ab_conv.py): "precision" (0 exact f32 | 3 f16x3),
+ * "chunk" (16|32 input channels staged per pass of k_conv), "v3" (-1 auto | 0 | 1 | 2: LDS-operand kernel k_conv3),
+ * "last_valu" (0|1), "first_split" (1|2|4 output-channel slices of the first layer), and the tuning options of the
+ * f16x3 path.  An unknown name is QGX_ERR_INVALID. */
 int qgx_generator_set_option(qgx_generator *g, const char *name, int value);
 /* f16x3 range guard (no reference counterpart: the reference evaluates its nets in plain float32).  The default
  * generator arithmetic carries float32 operands as f16 hi/lo pairs, which is float32-class only inside a value window;

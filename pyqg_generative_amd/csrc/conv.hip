@@ -46,19 +46,16 @@ struct ConvArgs {
 // under the MFMAs, bit-identical to k_convw, for the tile shapes where it is faster; *done = false: take k_convw
 int launch_convw2(int N, int TW, int R, const ConvWArgs &a, int total_tiles, hipStream_t st, bool *done);
 bool convw2_takes(int N, int TW, int R);     // the tile shapes k_convw2 is built for
-// Kernel variants that were measured slower than the ones above (k_convh generic / plain f16, k_convh_res,
-// k_convh3 on 16x16x32 MFMAs, k_convh4 with full-line chunks) are compiled only into the A/B library
-// (`make ab` -> libqgx_ab.so, bench_tools/ab_conv.py): the product library carries one path per layer and size.
-#ifdef QGX_AB
-#include "conv_h16.hpp"
-#include "conv_h4.hpp"
-#endif
+// One path per layer and size: the kernel variants that were measured slower than the ones above (a generic run-time-N
+// 16-bit kernel and its plain-f16 mode, resident weights, 16x16x32 MFMAs, full-line chunks, a channel-planar layer 1) are
+// not carried; their measurements are in DESIGN.md 3.2b-d.  The A/B library (`make ab` -> libqgx_ab.so) is this code plus
+// the fault-injection hooks of model.hip / common.hpp and qgx_debug_read_act.
 
-// OUTH = 0: f32 NHWC output.  OUTH = 1 / 2 (first layer only): the MFMA roles are swapped (lane = pixel)
-// and the epilogue writes the packed f16 / f16 hi-lo activation layout of conv_half.hpp.
+// OUTH = 0: f32 NHWC output.  OUTH = 2 (first layer only): the MFMA roles are swapped (lane = pixel)
+// and the epilogue writes the packed f16 hi-lo activation layout of conv_half.hpp.
 template <int CIN, int COUT, int KS, int CC, int MT, bool PLANAR_IN, bool FINAL, int CSPLIT = 1, bool PARTIAL = false, int OUTH = 0>
 __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
-    static_assert(OUTH == 0 || (PLANAR_IN && !FINAL && !PARTIAL), "16-bit output: first layer only");
+    static_assert(OUTH == 0 || (OUTH == 2 && PLANAR_IN && !FINAL && !PARTIAL), "16-bit output: first layer only");
     constexpr int NTF = (COUT + 31) / 32;        // all output-channel tiles of the layer
     constexpr int NT = NTF / CSPLIT;             // tiles owned by this workgroup (blockIdx.y picks the slice)
     constexpr int COUTP = NTF * 32;
@@ -246,10 +243,10 @@ __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
         if (tile >= ntiles) continue;
         if constexpr (OUTH != 0) {
             char *pix = reinterpret_cast<char *>(a.out) +
-                        ((size_t)b * N * N + (size_t)y0 * N + tile * 32 + li) * (COUT * 2 * OUTH);
+                        ((size_t)b * N * N + (size_t)y0 * N + tile * 32 + li) * (COUT * 4);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
-                store_tile_t<OUTH, false>(acc[mt][nt], (nt0 + nt) * 32, h, pix, a.bias, a.scale, a.shift, 1.0f, a.ascale, a.range, 1u);
+                store_tile_t<false>(acc[mt][nt], (nt0 + nt) * 32, h, pix, a.bias, a.scale, a.shift, 1.0f, a.ascale, a.range, 1u);
             continue;
         }
 #pragma unroll
@@ -679,11 +676,11 @@ static int pack_weights(const LayerHost &L, int li, const qgx_cnn_weights *w, bo
     return upf(dst, pw);
 }
 
-// conv_half.hpp weight layout [chunk][tap][j][h][cout][8] f16, pre-scaled by 2^s with max|w| 2^s in [2^13, 2^14)
-static int pack_half(LayerHost &L, int li, const qgx_cnn_weights *w, int NS, const float *cin_scale = nullptr) {
+// conv_half.hpp weight layout [chunk][tap][part][h][cout][8] f16 (hi | lo), pre-scaled by 2^s with max|w| 2^s in [2^13, 2^14)
+static int pack_half(LayerHost &L, int li, const qgx_cnn_weights *w, const float *cin_scale = nullptr) {
     const int cin = L.cin, cout = L.cout, T = L.ks * L.ks;
     const int coutp = ((cout + 31) / 32) * 32;         // the 32 -> 2 last layer is padded with zero rows
-    const int CC = NS == 1 ? 32 : 16, nch = cin / CC;
+    const int nch = cin / 16;
     const float *W = w->conv_w[li];
     float mx = 0.f;
     for (int co = 0; co < cout; ++co)
@@ -702,16 +699,16 @@ static int pack_half(LayerHost &L, int li, const qgx_cnn_weights *w, int NS, con
                 for (int hh = 0; hh < 2; ++hh)
                     for (int co = 0; co < cout; ++co)
                         for (int e8 = 0; e8 < 8; ++e8) {
-                            const int c = NS == 1 ? ch * 32 + j * 16 + hh * 8 + e8 : ch * 16 + hh * 8 + e8;
+                            const int c = ch * 16 + hh * 8 + e8;
                             const float x = W[((size_t)co * cin + c) * T + t] * (cin_scale ? cin_scale[c] : 1.f) * sc;
                             const _Float16 xh = (_Float16)x;
-                            const _Float16 v = (NS == 1 || j == 0) ? xh : (_Float16)(x - (float)xh);
+                            const _Float16 v = j == 0 ? xh : (_Float16)(x - (float)xh);
                             pw[(((((size_t)ch * T + t) * 2 + j) * 2 + hh) * coutp + co) * 8 + e8] = v;
                         }
-    void *&dst = cin_scale ? L.whF : L.wh[NS - 1];
+    void *&dst = cin_scale ? L.whF : L.wh;
     QGX_HIP(hipMalloc(&dst, pw.size() * sizeof(_Float16)));
     QGX_HIP(hipMemcpy(dst, pw.data(), pw.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    (cin_scale ? L.whF_unscale : L.wh_unscale[NS - 1]) = ldexpf(1.f, -sexp);
+    (cin_scale ? L.whF_unscale : L.wh_unscale) = ldexpf(1.f, -sexp);
     return QGX_OK;
 }
 
@@ -774,30 +771,6 @@ static int pack_wino(LayerHost &L, int li, const qgx_cnn_weights *w, const float
     return QGX_OK;
 }
 
-// k_convh3 layout: 32-channel chunks, [chunk][tap][part][octet][cout][8]; same power-of-two pre-scale as wh[1]
-static int pack_half16(LayerHost &L, int li, const qgx_cnn_weights *w, const float *cin_scale = nullptr) {
-    const int cin = L.cin, cout = L.cout, T = L.ks * L.ks, nch = cin / 32;
-    const float *W = w->conv_w[li];
-    const float sc = 1.0f / (cin_scale ? L.whF_unscale : L.wh_unscale[1]);
-    std::vector<_Float16> pw((size_t)nch * T * 2 * 4 * cout * 8, (_Float16)0.f);
-    for (int ch = 0; ch < nch; ++ch)
-        for (int t = 0; t < T; ++t)
-            for (int part = 0; part < 2; ++part)
-                for (int o = 0; o < 4; ++o)
-                    for (int co = 0; co < cout; ++co)
-                        for (int e8 = 0; e8 < 8; ++e8) {
-                            const int c = ch * 32 + o * 8 + e8;
-                            const float x = W[((size_t)co * cin + c) * T + t] * (cin_scale ? cin_scale[c] : 1.f) * sc;
-                            const _Float16 xh = (_Float16)x;
-                            pw[(((((size_t)ch * T + t) * 2 + part) * 4 + o) * cout + co) * 8 + e8] =
-                                part == 0 ? xh : (_Float16)(x - (float)xh);
-                        }
-    void *&dst16 = cin_scale ? L.wh16F : L.wh16;
-    QGX_HIP(hipMalloc(&dst16, pw.size() * sizeof(_Float16)));
-    QGX_HIP(hipMemcpy(dst16, pw.data(), pw.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    return QGX_OK;
-}
-
 // first layer, f16x3 (k_convh_first): [step][part][h][cout][8], element j of lane half h in step s is
 // (tap, channel) = (TPS s + TPF h + j / n_in, j % n_in); tap slots >= 25 hold zeros
 static int pack_half_first(LayerHost &L, const qgx_cnn_weights *w) {
@@ -843,8 +816,8 @@ static int pack_layer(LayerHost &L, int li, const qgx_cnn_weights *w, bool plana
     } else {
         if ((rc = pack_weights(L, li, w, false, 16, L.w))) return rc;
         if ((rc = pack_weights(L, li, w, false, 32, L.w32))) return rc;
-        for (int cc : {16}) {      // LDS-operand layout for k_conv3
-            const int cin = L.cin, ks = L.ks, T = ks * ks, g8n = cc / 8, nch = cin / cc;
+        {      // LDS-operand layout for k_conv3
+            const int cc = 16, cin = L.cin, ks = L.ks, T = ks * ks, g8n = cc / 8, nch = cin / cc;
             std::vector<float> pw((size_t)nch * T * g8n * 2 * L.coutp * 4, 0.f);
             for (int ch = 0; ch < nch; ++ch)
                 for (int t = 0; t < T; ++t)
@@ -856,14 +829,10 @@ static int pack_layer(LayerHost &L, int li, const qgx_cnn_weights *w, bool plana
                                     pw[(((((size_t)ch * T + t) * g8n + g8) * 2 + hh) * L.coutp + co) * 4 + e] =
                                         w->conv_w[li][((size_t)co * cin + c) * T + t];
                                 }
-            if ((rc = upf(cc == 16 ? L.wl16 : L.wl8, pw))) return rc;
+            if ((rc = upf(L.wl16, pw))) return rc;
         }
         if (li < 7) {
-            if ((rc = pack_half(L, li, w, 2))) return rc;
-#ifdef QGX_AB
-            if ((rc = pack_half(L, li, w, 1))) return rc;
-            if (li == 1 && (rc = pack_half16(L, li, w))) return rc;
-#endif
+            if ((rc = pack_half(L, li, w))) return rc;
             if (li == 1) {
                 // fold layer 1's BatchNorm (alpha, beta' of its 128 output channels) into this layer
                 const int cin = L.cin, T = L.ks * L.ks;
@@ -879,13 +848,10 @@ static int pack_layer(LayerHost &L, int li, const qgx_cnn_weights *w, bool plana
                         for (int t = 0; t < T; ++t) acc += (double)w->conv_w[li][((size_t)co * cin + c) * T + t] * be[c];
                     bf[co] = (float)acc;
                 }
-                if ((rc = pack_half(L, li, w, 2, al.data())) || (rc = upf(L.biasF, bf))) return rc;
+                if ((rc = pack_half(L, li, w, al.data())) || (rc = upf(L.biasF, bf))) return rc;
                 if ((rc = pack_wino(L, li, w, nullptr, 0)) || (rc = pack_wino(L, li, w, al.data(), 1))) return rc;
-#ifdef QGX_AB
-                if ((rc = pack_half16(L, li, w, al.data()))) return rc;
-#endif
             }
-        } else if ((rc = pack_half(L, li, w, 2))) return rc;      // fused (layer 7, layer 8) pair
+        } else if ((rc = pack_half(L, li, w))) return rc;      // fused (layer 7, layer 8) pair
     }
     if (li == 7) {      // [tap][c][2] for the VALU last-layer kernel
         const int cin = L.cin, ks = L.ks;
@@ -953,17 +919,20 @@ static int launch_conv(qgx_generator *g, int layer, const LayerHost &L, const fl
     const size_t lds = (size_t)(R + KS - 1) * N * STRIDE * sizeof(float);
     QGX_REQUIRE(lds <= 160 * 1024, "generator: LDS patch %zu B too large for N=%d", lds, N);
     dim3 grid(B * (N / R), CSPLIT), block(256);
-    if (ntiles <= 8) {
-        auto kern = k_conv<CIN, COUT, KS, CC, 2, PLANAR_IN, FINAL, CSPLIT, false, OUTH>;
-        { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-        hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    } else {
-        auto kern = k_conv<CIN, COUT, KS, CC, 3, PLANAR_IN, FINAL, CSPLIT, false, OUTH>;
-        { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-        hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    }
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    if (ntiles <= 8) return launch_conv_kernel(k_conv<CIN, COUT, KS, CC, 2, PLANAR_IN, FINAL, CSPLIT, false, OUTH>, grid, block, lds, st, a);
+    return launch_conv_kernel(k_conv<CIN, COUT, KS, CC, 3, PLANAR_IN, FINAL, CSPLIT, false, OUTH>, grid, block, lds, st, a);
+}
+
+// the exact-f32 first layer (n_in = 4 or 2 planar channels -> 128, 5x5): its output-channel tiles over `split` = 1, 2 or 4
+// workgroups ("first_split"); outh = 2 (with split = 2): it stores the f16x3 activation layout for the 16-bit layers behind it
+static int launch_conv_first(qgx_generator *g, const LayerHost &L, int n_in, int split, int outh, const float *in, float *out,
+                             int B, int N, hipStream_t st) {
+#define QGX_L1(SPLIT, OUTH)                                                                              \
+    (n_in == 4 ? launch_conv<4, 128, 5, 4, true, false, SPLIT, OUTH>(g, 0, L, in, out, B, N, 128, st)    \
+               : launch_conv<2, 128, 5, 2, true, false, SPLIT, OUTH>(g, 0, L, in, out, B, N, 128, st))
+    if (outh == 2) return QGX_L1(2, 2);
+    return split == 2 ? QGX_L1(2, 0) : (split == 4 ? QGX_L1(4, 0) : QGX_L1(1, 0));
+#undef QGX_L1
 }
 
 // ---- small ensembles (few tiles): 4 M-tiles per workgroup (one per wave) and split-K over the
@@ -998,21 +967,11 @@ static int launch_conv_small(qgx_generator *g, int layer, const LayerHost &L, co
     a.N = N; a.R = R; a.cout_real = COUT; a.npix_total = npix;
     const size_t lds = (size_t)(R + KS - 1) * N * (CC + 4) * sizeof(float);
     dim3 grid(B * (N / R), nsplit), block(256);
-    if (nsplit > 1) {
-        auto kern = k_conv<CIN, COUT, KS, CC, 1, false, false, 1, true>;
-        { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-        hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-        const size_t n4 = npix * COUT / 4;
-        hipLaunchKernelGGL(k_conv_reduce<COUT>, dim3((unsigned)((n4 + 255) / 256 > 1024 ? 1024 : (n4 + 255) / 256)), dim3(256),
-                           0, st, (const float *)part, nsplit, npix, (const float *)L.bias, (const float *)L.scale,
-                           (const float *)L.shift, out);
-    } else {
-        auto kern = k_conv<CIN, COUT, KS, CC, 1, false, false, 1, false>;
-        { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-        hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    }
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    if (nsplit == 1) return launch_conv_kernel(k_conv<CIN, COUT, KS, CC, 1, false, false, 1, false>, grid, block, lds, st, a);
+    if (const int rc = launch_conv_kernel(k_conv<CIN, COUT, KS, CC, 1, false, false, 1, true>, grid, block, lds, st, a)) return rc;
+    const size_t n4 = npix * COUT / 4;
+    return launch_conv_kernel(k_conv_reduce<COUT>, dim3((unsigned)((n4 + 255) / 256 > 1024 ? 1024 : (n4 + 255) / 256)), dim3(256), 0, st,
+                              part, nsplit, npix, L.bias, L.scale, L.shift, out);
 }
 
 // ---- k_conv3 launcher -------------------------------------------------------------------------
@@ -1020,6 +979,7 @@ template <int CIN, int COUT, int KS, int TPS, int CC = 16, int NW = 4>
 static int launch_conv3(qgx_generator *g, int layer, const LayerHost &L, const float *in, float *out, int B,
                         int N, hipStream_t st, bool &done) {
     done = false;
+    static_assert(CC == 16, "k_conv3's weights are packed for 16-channel chunks (LayerHost::wl16)");
     constexpr int T = KS * KS, NSL = T / TPS, NTc = (COUT + 31) / 32;
     constexpr size_t WSLB = (size_t)TPS * (CC / 8) * 2 * NTc * 32 * 4 * sizeof(float);
     // rows per tile: as k_conv (8 or 12 M-tiles; twice that with 8 waves), LDS = 2 patches + 2 weight slices
@@ -1035,18 +995,12 @@ static int launch_conv3(qgx_generator *g, int layer, const LayerHost &L, const f
     ProfScope prof;
     if (const int prc = prof.begin(g, layer, st)) return prc;
     ConvArgs a = {};
-    a.in = in; a.out = out; a.w = CC == 16 ? L.wl16 : L.wl8; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
+    a.in = in; a.out = out; a.w = L.wl16; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
     a.N = N; a.R = R; a.cout_real = COUT;
     const int total_tiles = B * (N / R);
-    const int wgs = lds * 2 <= 160 * 1024 ? 2 : 1;
-    int grid = 256 * wgs;
-    if (grid > total_tiles) grid = total_tiles;
-#define QGX_L3(MTV, PPTV)                                                                                     \
-    {                                                                                                         \
-        auto kern = k_conv3<CIN, COUT, KS, CC, MTV, TPS, PPTV, NW>;                                           \
-        { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; } \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a, total_tiles);                         \
-    }
+    const int grid = persistent_grid(lds * 2 <= 160 * 1024 ? 512 : 256, total_tiles);
+    void (*kern)(ConvArgs, int) = nullptr;
+#define QGX_L3(MTV, PPTV) { kern = k_conv3<CIN, COUT, KS, CC, MTV, TPS, PPTV, NW>; }
     const int mtv = (ntiles + NW - 1) / NW <= 1 ? 1 : ((ntiles + NW - 1) / NW == 2 ? 2 : 3);
     if (mtv == 1) {
         if (ppt <= 2) QGX_L3(1, 2) else if (ppt <= 4) QGX_L3(1, 4) else return QGX_OK;
@@ -1055,7 +1009,7 @@ static int launch_conv3(qgx_generator *g, int layer, const LayerHost &L, const f
     else if (ppt <= 8) { if (mtv == 2) QGX_L3(2, 8) else QGX_L3(3, 8) }
     else return QGX_OK;
 #undef QGX_L3
-    QGX_HIP(hipGetLastError());
+    if (const int rc = launch_conv_kernel(kern, dim3(grid), dim3(NW * 64), lds, st, a, total_tiles)) return rc;
     done = true;
     return QGX_OK;
 }
@@ -1121,30 +1075,13 @@ static int launch_conv_last(qgx_generator *g, const LayerHost &L, const float *i
         ConvArgs a = {};
         a.in = in; a.out = out + (size_t)c0 * N * N; a.w = nullptr; a.bias = L.bias + c0; a.scale = L.scale; a.shift = L.shift;
         a.N = N; a.R = R; a.cout_real = n_out - c0 < 2 ? n_out - c0 : 2; a.out_channels = n_out;
-        if (split) {
-            auto kern = k_conv_last<32, 3, 4>;
-            { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-            hipLaunchKernelGGL(kern, dim3(B * (N / R)), dim3(256), lds, st, a, L.wv_host[c0 / 2]);
-        } else {
-            auto kern = k_conv_last<32, 3>;
-            { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-            hipLaunchKernelGGL(kern, dim3(B * (N / R)), dim3(256), lds, st, a, L.wv_host[c0 / 2]);
-        }
+        if (const int rc = launch_conv_kernel(split ? k_conv_last<32, 3, 4> : k_conv_last<32, 3>, dim3(B * (N / R)), dim3(256), lds, st,
+                                              a, L.wv_host[c0 / 2])) return rc;
     }
-    QGX_HIP(hipGetLastError());
     return QGX_OK;
 }
 
 // ---- 16-bit matrix-core path (conv_half.hpp) ------------------------------------------------------
-// rows per 8-wave workgroup: 16 or 24 M-tiles of 32 pixels
-static int rows_half(int N) {
-    int R = 0;
-    if (N <= 512 && 512 % N == 0) R = 512 / N;
-    else if (N <= 768 && 768 % N == 0) R = 768 / N;
-    if (R == 0 || N % R) return 0;
-    if ((size_t)(R + 4) * N * 80 + 2 * 5 * 4 * 64 * 16 > 160 * 1024 - 256) return 0;
-    return R;
-}
 // rows per tile of k_convh2 (4 waves x MT M-tiles of 32 pixels), 0 when the grid size has no specialisation
 static int rows_h2(int N) {
     switch (N) {
@@ -1160,76 +1097,22 @@ static int rows_h2(int N) {
 // k_convh2 is specialised for, so it is always taken there ("half_min_tiles" = 1; raise it to send small
 // ensembles to the exact-f32 split-K kernels)
 static bool half_path_ok(const qgx_generator *g, int B, int N) {
-#ifndef QGX_AB
-    // product library: f16x3 on the grids k_convh2 is specialised for, exact f32 everywhere else
-    if (g->opt_precision != 3 || g->opt_h2 != 3 || rows_h2(N) <= 0) return false;
-#endif
-    if (N > 128 || choose_rows(N) <= 0) return false;
-    int R = (g->opt_h2 == 3 && g->opt_precision == 3) ? rows_h2(N) : 0;
-    if (R == 0) R = g->opt_half_nw == 4 ? choose_rows(N) : rows_half(N);
-    if (R <= 0 || N % R) return false;
+    // f16x3 on the grids k_convh2 is specialised for (each a whole number of its row tiles), exact f32 everywhere else
+    const int R = rows_h2(N);
+    if (g->opt_precision != 3 || R <= 0) return false;
     return B * (N / R) >= g->opt_half_min_tiles;
 }
 
-// the fields every f16 / f16x3 hidden-layer launcher fills alike (the f16x3 weight layout unless the launcher says otherwise)
+// the fields every f16x3 hidden-layer launcher fills alike
 static ConvHArgs convh_args(const qgx_generator *g, int layer, const LayerHost &L, const void *in, void *out, bool outf32, int N, int R) {
     ConvHArgs a = {};
-    a.in = in; a.out = out; a.w = L.wh[1]; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
-    a.unscale = L.wh_unscale[1] / g->opt_ascale; a.ascale = outf32 ? 1.f : g->opt_ascale;
+    a.in = in; a.out = out; a.w = L.wh; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
+    a.unscale = L.wh_unscale / g->opt_ascale; a.ascale = outf32 ? 1.f : g->opt_ascale;
     a.range = g->range_dev; a.range_bit = 1u << layer;
     a.N = N; a.R = R;
     a.stamps = layer == g->stamp_layer ? g->stamps : nullptr;
     return a;
 }
-
-#ifdef QGX_AB
-template <int CIN, int COUT, int KS, int NS, bool OUTF32>
-static int launch_convh(qgx_generator *g, int layer, const LayerHost &L, const void *in, void *out, int B, int N,
-                        hipStream_t st) {
-    constexpr int TPS = KS == 5 ? 5 : 9;
-    // two shapes: 4 waves x 2 workgroups per CU (swizzled 64-byte patch pixels; the two workgroups run out
-    // of phase, so one's staging overlaps the other's MFMAs) or 8 waves x 1 workgroup (double-height tiles)
-    const bool four = g->opt_half_nw == 4;
-    const int R = four ? choose_rows(N) : rows_half(N);
-    QGX_REQUIRE(R > 0 && N % R == 0, "generator: 16-bit path does not support N=%d", N);
-    const int nw = four ? 4 : 8;
-    const int PR = R + KS - 1;
-    const int ntiles = R * N / 32;
-    const int mtv = ntiles / nw;
-    const int ppt = (PR * N * 4 + nw * 64 - 1) / (nw * 64);
-    const size_t lds = (size_t)PR * N * (four ? 64 : 80) + (size_t)2 * TPS * 4 * COUT * 16 + 3 * COUT * sizeof(float);
-    QGX_REQUIRE(lds <= 160 * 1024 - 256 && (mtv == 2 || mtv == 3) && ntiles % nw == 0 && ppt <= 12,
-                "generator: 16-bit path tile shape unsupported for N=%d", N);
-    ProfScope prof;
-    if (const int prc = prof.begin(g, layer, st)) return prc;
-    ConvHArgs a = convh_args(g, layer, L, in, out, OUTF32, N, R);
-    a.w = L.wh[NS - 1]; a.unscale = L.wh_unscale[NS - 1] / g->opt_ascale;
-    const int total_tiles = B * (N / R);
-    int grid = 256 * (lds * 2 <= 160 * 1024 ? 2 : 1);
-    if (grid > total_tiles) grid = total_tiles;
-#define QGX_LH(MTV, PPTV, NWV, SWZV)                                                                          \
-    {                                                                                                         \
-        auto kern = k_convh<CIN, COUT, KS, NS, MTV, TPS, PPTV, OUTF32, NWV, SWZV>;                            \
-        { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; } \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NWV * 64), lds, st, a, total_tiles);                        \
-    }
-    if (four) {
-        if (mtv == 2) { if (ppt <= 6) QGX_LH(2, 6, 4, true) else if (ppt <= 8) QGX_LH(2, 8, 4, true) else QGX_LH(2, 12, 4, true) }
-        else QGX_LH(3, 12, 4, true)
-    } else {
-        QGX_REQUIRE(ppt <= 10, "generator: 16-bit path tile shape unsupported for N=%d", N);
-        if (mtv == 2) { if (ppt <= 6) QGX_LH(2, 6, 8, false) else QGX_LH(2, 10, 8, false) }
-        else { if (ppt <= 6) QGX_LH(3, 6, 8, false) else QGX_LH(3, 10, 8, false) }
-    }
-#undef QGX_LH
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
-}
-
-#endif  // QGX_AB
-
-static int launch_conv_last(qgx_generator *g, const LayerHost &L, const float *in, float *out, int B, int N,
-                            int n_out, hipStream_t st);
 
 // f16x3 hidden layers at the grid sizes with a compile-time specialisation (k_convh2; 2 workgroups per CU
 // where the LDS budget allows)
@@ -1246,16 +1129,11 @@ static int launch_convh2_n(qgx_generator *g, int layer, const LayerHost &L, cons
     ConvHArgs a = convh_args(g, layer, L, in, out, OUTF32, NN, R);
     a.prio_alt = KS == 5 ? g->opt_prio_alt : (g->opt_prio_alt == 3 ? 3 : 0);      // measured: -2 % on the 5x5 layer, nothing on the 3x3 layers (3: by phase)
     const int total_tiles = B * (NN / R);
-    int grid = lds * 2 <= 160 * 1024 ? 512 : 256;
-    if (g->opt_h2_grid > 0) grid = g->opt_h2_grid;
-    if (grid > total_tiles) grid = total_tiles;
+    const int grid = persistent_grid(g->opt_h2_grid > 0 ? g->opt_h2_grid : (lds * 2 <= 160 * 1024 ? 512 : 256), total_tiles);
     constexpr bool TWO = lds * 2 <= 160 * 1024 && MT == 2;        // two workgroups per CU: <= 256 registers
     auto kern = g->opt_pair && KS == 3 ? k_convh2<CIN, COUT, KS, NN, MT, TPS, OUTF32, WDB, TWO, KS == 3>
                                         : k_convh2<CIN, COUT, KS, NN, MT, TPS, OUTF32, WDB, TWO, false>;
-    { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, total_tiles);
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    return launch_conv_kernel(kern, dim3(grid), dim3(256), lds, st, a, total_tiles);
 }
 
 // single members: split K over the 16-channel chunks (k_convh2<PART> + k_convh_reduce), so that the wide
@@ -1277,15 +1155,11 @@ static int launch_convh2_part_n(qgx_generator *g, int layer, const LayerHost &L,
     a.npix_total = npix; a.stamps = nullptr;
     const int total_tiles = B * (NN / R);
     constexpr bool TWO = lds * 2 <= 160 * 1024 && MT == 2;
-    auto kern = k_convh2<CIN, COUT, KS, NN, MT, TPS, OUTF32, WDB, TWO, false, true>;
-    { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-    hipLaunchKernelGGL(kern, dim3(total_tiles, nsplit), dim3(256), lds, st, a, total_tiles);
+    if (const int rc = launch_conv_kernel(k_convh2<CIN, COUT, KS, NN, MT, TPS, OUTF32, WDB, TWO, false, true>, dim3(total_tiles, nsplit),
+                                          dim3(256), lds, st, a, total_tiles)) return rc;
     const size_t n = npix * (COUT / 8);
-    hipLaunchKernelGGL((k_convh_reduce<COUT, OUTF32>), dim3((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), dim3(256), 0, st,
-                       (const float *)part, nsplit, npix, (const float *)L.bias, (const float *)L.scale, (const float *)L.shift,
-                       a.unscale, a.ascale, out, a.range, a.range_bit);
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    return launch_conv_kernel(k_convh_reduce<COUT, OUTF32>, dim3((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), dim3(256), 0, st,
+                              part, nsplit, npix, L.bias, L.scale, L.shift, a.unscale, a.ascale, out, a.range, a.range_bit);
 }
 
 template <int CIN, int COUT, int KS, bool OUTF32>
@@ -1317,13 +1191,8 @@ static int launch_convh2_w8(qgx_generator *g, int layer, const LayerHost &L, con
     if (const int prc = prof.begin(g, layer, st)) return prc;
     ConvHArgs a = convh_args(g, layer, L, in, out, false, NN, R);
     const int total_tiles = B * (NN / R) * (NN / TW);
-    int grid = 256;
-    if (grid > total_tiles) grid = total_tiles;
-    auto kern = k_convh2<CIN, COUT, KS, NN, MT, TPS, false, true, false, false, false, NW, TW>;
-    { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a, total_tiles);
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    return launch_conv_kernel(k_convh2<CIN, COUT, KS, NN, MT, TPS, false, true, false, false, false, NW, TW>,
+                              dim3(persistent_grid(256, total_tiles)), dim3(NW * 64), lds, st, a, total_tiles);
 }
 
 // the 3x3 layers in the same 8-wave shape (64 x 64)
@@ -1336,13 +1205,8 @@ static int launch_convh2_w8_3x3(qgx_generator *g, int layer, const LayerHost &L,
     if (const int prc = prof.begin(g, layer, st)) return prc;
     ConvHArgs a = convh_args(g, layer, L, in, out, OUTF32, NN, R);
     const int total_tiles = B * (NN / R) * (NN / TW);
-    int grid = 256;
-    if (grid > total_tiles) grid = total_tiles;
-    auto kern = k_convh2<CIN, COUT, KS, NN, MT, TPS, OUTF32, true, false, true, false, NW, TW>;
-    { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a, total_tiles);
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    return launch_conv_kernel(k_convh2<CIN, COUT, KS, NN, MT, TPS, OUTF32, true, false, true, false, NW, TW>,
+                              dim3(persistent_grid(256, total_tiles)), dim3(NW * 64), lds, st, a, total_tiles);
 }
 
 template <int CIN, int COUT, int KS, bool OUTF32>
@@ -1384,115 +1248,17 @@ static int launch_convh2(qgx_generator *g, int layer, const LayerHost &L, const 
     }
 }
 
-#ifdef QGX_AB
-// 3x3 layers, f16x3, resident weights (k_convh_res); done = false when the tile does not fit in LDS
+// a 3x3 layer of the f16x3 path: half_path_ok admits only the grids k_convh2 is specialised for
 template <int CIN, int COUT, bool OUTF32>
-static int launch_convh_res(qgx_generator *g, int layer, const LayerHost &L, const void *in, void *out, int B, int N,
-                            hipStream_t st, bool &done) {
-    done = false;
-    const int R = rows_half(N);
-    if (R <= 0 || N % R) return QGX_OK;
-    const int PR = R + 2, ntiles = R * N / 32, mtv = ntiles / 8;
-    const size_t lds = (size_t)(CIN / 16) * 9 * 4 * COUT * 16 + (size_t)PR * N * 128 + 3 * COUT * sizeof(float);
-    const int ppt = (PR * N * 8 + 511) / 512;
-    if (lds > 160 * 1024 || ntiles % 8 || (mtv != 2 && mtv != 3) || ppt > 14) return QGX_OK;
-    ProfScope prof;
-    if (const int prc = prof.begin(g, layer, st)) return prc;
-    ConvHArgs a = convh_args(g, layer, L, in, out, OUTF32, N, R);
-    const int total_tiles = B * (N / R);
-    int grid = 256;
-    if (grid > total_tiles) grid = total_tiles;
-#define QGX_LR(MTV, PPTV)                                                                                     \
-    {                                                                                                         \
-        auto kern = k_convh_res<CIN, COUT, MTV, PPTV, OUTF32>;                                                \
-        { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; } \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a, total_tiles);                             \
-    }
-    if (mtv == 2) { if (ppt <= 10) QGX_LR(2, 10) else QGX_LR(2, 14) }
-    else { if (ppt <= 10) QGX_LR(3, 10) else QGX_LR(3, 14) }
-#undef QGX_LR
-    QGX_HIP(hipGetLastError());
-    done = true;
-    return QGX_OK;
-}
-
-#endif  // QGX_AB
-
-template <int CIN, int COUT, int NS, bool OUTF32>
 static int conv3x3_half(qgx_generator *g, int layer, const LayerHost &L, const void *in, void *out, int B, int N,
                         hipStream_t st) {
-    if (NS == 2 && g->opt_h2) {
-        bool done = false;
-        int rc = launch_convh2<CIN, COUT, 3, OUTF32>(g, layer, L, in, out, B, N, st, done);
-        if (rc || done) return rc;
-    }
-#ifdef QGX_AB
-    if (NS == 2 && g->opt_res) {
-        bool done = false;
-        int rc = launch_convh_res<CIN, COUT, OUTF32>(g, layer, L, in, out, B, N, st, done);
-        if (rc || done) return rc;
-    }
-    return launch_convh<CIN, COUT, 3, NS, OUTF32>(g, layer, L, in, out, B, N, st);
-#else
-    QGX_REQUIRE(false, "generator: no f16x3 kernel for N=%d (half_path_ok admits only the specialised grids)", N);
-#endif
-}
-
-#ifdef QGX_AB
-// the 128 -> 64, 5x5 layer on 16x16x32 MFMAs (k_convh3); grids whose rows tile 256 pixels
-static int launch_convh3(qgx_generator *g, int layer, const LayerHost &L, const void *in, void *out, int B, int N,
-                         hipStream_t st, bool &done) {
-    done = false;
-    if (N != 64 || !L.wh16) return QGX_OK;
-    constexpr int NN = 64, R = 256 / NN, PR = R + 4, PW = NN + 4;
-    constexpr size_t lds = (size_t)4 * PR * PW * 48 + (size_t)5 * 2 * 4 * 64 * 16 + 3 * 64 * sizeof(float);
-    static_assert(lds <= 160 * 1024, "LDS");
-    ProfScope prof;
-    if (const int prc = prof.begin(g, layer, st)) return prc;
-    ConvHArgs a = convh_args(g, layer, L, in, out, false, N, R);
-    a.w = L.wh16; a.stamps = nullptr;
-    const int total_tiles = B * (N / R);
-    int grid = 256;
-    if (grid > total_tiles) grid = total_tiles;
-    auto kern = k_convh3<NN>;
-    { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, total_tiles);
-    QGX_HIP(hipGetLastError());
-    done = true;
+    bool done = false;
+    if (const int rc = launch_convh2<CIN, COUT, 3, OUTF32>(g, layer, L, in, out, B, N, st, done)) return rc;
+    QGX_REQUIRE(done, "generator: no f16x3 kernel for N=%d (half_path_ok admits only the specialised grids)", N);
     return QGX_OK;
 }
 
-// the 128 -> 64, 5x5 layer with full-line patch chunks (k_convh4: 8 waves, R = 8)
-template <int NN, int MT, int NW>
-static int launch_convh4_n(qgx_generator *g, int layer, const LayerHost &L, const void *in, void *out, int B, hipStream_t st) {
-    constexpr int R = NW * MT * 32 / NN, PR = R + 4, PW = NN + 4;
-    constexpr size_t lds = (size_t)PR * PW * 144 + (size_t)2 * 5 * 4 * 64 * 16 + 3 * 64 * sizeof(float);
-    static_assert(lds <= 160 * 1024, "LDS");
-    ProfScope prof;
-    if (const int prc = prof.begin(g, layer, st)) return prc;
-    ConvHArgs a = convh_args(g, layer, L, in, out, false, NN, R);
-    a.stamps = nullptr;
-    const int total_tiles = B * (NN / R);
-    int grid = 256;
-    if (grid > total_tiles) grid = total_tiles;
-    auto kern = k_convh4<NN, MT, NW>;
-    { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a, total_tiles);
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
-}
-static int launch_convh4(qgx_generator *g, int layer, const LayerHost &L, const void *in, void *out, int B, int N,
-                         hipStream_t st, bool &done) {
-    done = true;
-    if (N == 64 && B * 8 >= 256)
-        return g->opt_h4 == 2 ? launch_convh4_n<64, 4, 4>(g, layer, L, in, out, B, st) : launch_convh4_n<64, 2, 8>(g, layer, L, in, out, B, st);
-    done = false;
-    return QGX_OK;
-}
-
-// two fused 3x3 layers (k_convh_pair); 64 x 64 grids
-#endif  // QGX_AB
-
+// two fused 3x3 layers (k_convh_pair) on R-row strips of an NN x NN grid
 template <int CINA, bool LAST, bool BOUTF32, int NN = 64, int R = 8>
 static int launch_convh_pair(qgx_generator *g, int layerA, const LayerHost &LA, const LayerHost &LB, const void *in,
                              void *out, int B, int N, int n_out, hipStream_t st) {
@@ -1504,29 +1270,20 @@ static int launch_convh_pair(qgx_generator *g, int layerA, const LayerHost &LA, 
     ProfScope prof;
     if (const int prc = prof.begin(g, layerA, st)) return prc;
     ConvPairArgs a = {};
-    a.in = in; a.out = out; a.wA = LA.wh[1]; a.wB = LB.wh[1];
+    a.in = in; a.out = out; a.wA = LA.wh; a.wB = LB.wh;
     a.biasA = LA.bias; a.scaleA = LA.scale; a.shiftA = LA.shift;
     a.biasB = LB.bias; a.scaleB = LB.scale; a.shiftB = LB.shift;
-    a.unscaleA = LA.wh_unscale[1] / g->opt_ascale; a.unscaleB = LB.wh_unscale[1] / g->opt_ascale; a.ascale = g->opt_ascale;
+    a.unscaleA = LA.wh_unscale / g->opt_ascale; a.unscaleB = LB.wh_unscale / g->opt_ascale; a.ascale = g->opt_ascale;
     a.range = g->range_dev; a.range_bit = 1u << layerA;
     a.n_out = n_out;
     a.stamps = layerA == g->stamp_layer ? g->stamps : nullptr;
     const int total_tiles = B * (N / R);
-    int grid = 256;
-    if (grid > total_tiles) grid = total_tiles;
-    auto kern = k_convh_pair<CINA, NN, LAST, BOUTF32, CINA == 32, R>;
-#ifdef QGX_AB
-    if (!g->opt_pair_lp) kern = k_convh_pair<CINA, NN, LAST, BOUTF32, false, R>;
-#endif
-    { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a, total_tiles);
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    return launch_conv_kernel(k_convh_pair<CINA, NN, LAST, BOUTF32, R>, dim3(persistent_grid(256, total_tiles)), dim3(512), lds, st, a, total_tiles);
 }
 
 template <int NIN>
 static int launch_convh_first(qgx_generator *g, const LayerHost &L, const float *in, void *out, int B, int N,
-                              hipStream_t st, bool wino_next = false, bool planar = false) {
+                              hipStream_t st, bool wino_next = false) {
     int R = choose_rows(N);
     QGX_REQUIRE(R > 0 && N % R == 0 && N % 4 == 0, "generator: unsupported grid size N=%d", N);
     // one 8-wave workgroup per CU with double-height tiles where two M-tiles per wave result (64 x 64, 32 x 32) and
@@ -1552,32 +1309,19 @@ static int launch_convh_first(qgx_generator *g, const LayerHost &L, const float 
     a.guard_mul = wino_next ? 16.f : 1.f;
     a.range = g->range_dev; a.range_bit = 1u;
     const int total_tiles = B * (N / R);
-    const int wgs = lds * 2 <= 160 * 1024 ? 2 : 1;
-    int grid = 256 * wgs;
-    if (grid > total_tiles) grid = total_tiles;
-#ifdef QGX_AB
-#define QGX_LF_KERN(MTV, PPTV, NWV) (planar ? k_convh_first<NIN, MTV, PPTV, NWV, true> : k_convh_first<NIN, MTV, PPTV, NWV, false>)
-#else
-#define QGX_LF_KERN(MTV, PPTV, NWV) k_convh_first<NIN, MTV, PPTV, NWV, false>
-#endif
-#define QGX_LF(MTV, PPTV, NWV)                                                                                \
-    {                                                                                                         \
-        auto kern = QGX_LF_KERN(MTV, PPTV, NWV);                                                              \
-        { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; } \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NWV * 64), lds, st, a, total_tiles);                        \
-    }
+    const int grid = persistent_grid(lds * 2 <= 160 * 1024 ? 512 : 256, total_tiles);
+    void (*kern)(ConvHFirstArgs, int) = nullptr;
+#define QGX_LF(MTV, PPTV, NWV) { kern = k_convh_first<NIN, MTV, PPTV, NWV>; }
     if (half_rows) { if (ppt <= 2) QGX_LF(1, 2, 4) else QGX_LF(1, 3, 4) }
     else if (w8) { if (ppt <= 2) QGX_LF(2, 2, 8) else QGX_LF(2, 3, 8) }
     else if (ntiles == 8) { if (ppt <= 2) QGX_LF(2, 2, 4) else QGX_LF(2, 3, 4) }
     else { if (ppt <= 2) QGX_LF(3, 2, 4) else QGX_LF(3, 3, 4) }
 #undef QGX_LF
-#undef QGX_LF_KERN
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    return launch_conv_kernel(kern, dim3(grid), dim3(nw * 64), lds, st, a, total_tiles);
 }
 
 // layer 2 as a 1-D Winograd convolution (conv_wino.hpp); use2: as k_convw2 where that kernel is built for the tile shape
-template <int NN, int TW, int R, bool PL = false>
+template <int NN, int TW, int R>
 static int launch_convw_n(qgx_generator *g, int layer, const LayerHost &L, int which, bool use2, const void *in, void *out, int B,
                           hipStream_t st) {
     ProfScope prof;
@@ -1588,28 +1332,14 @@ static int launch_convw_n(qgx_generator *g, int layer, const LayerHost &L, int w
     a.ascale = g->opt_ascale;
     a.range = g->range_dev; a.range_bit = 1u << layer;
     const int total_tiles = B * (NN / R) * (NN / TW);
-    constexpr size_t lds = convw_lds_bytes(NN, TW, R, PL);
+    constexpr size_t lds = convw_lds_bytes(NN, TW, R);
     static_assert(lds <= 160 * 1024 - 256, "k_convw: LDS");
-    if (!PL && use2) {
+    if (use2) {
         bool done2 = false;
         const int rc2 = launch_convw2(NN, TW, R, a, total_tiles, st, &done2);
         if (rc2 || done2) return rc2;
     }
-    const int grid = total_tiles < 256 ? total_tiles : 256;
-    void (*kern)(ConvWArgs, int) = k_convw<NN, TW, R, 0, PL>;
-#ifdef QGX_AB       // timing experiments: parts of the kernel switched off (wrong results)
-    if (g->opt_wino_exp == 1) kern = k_convw<NN, TW, R, 1, PL>;
-    else if (g->opt_wino_exp == 2) kern = k_convw<NN, TW, R, 2, PL>;
-    else if (g->opt_wino_exp == 4) kern = k_convw<NN, TW, R, 4, PL>;
-    else if (g->opt_wino_exp == 5) kern = k_convw<NN, TW, R, 5, PL>;
-    else if (g->opt_wino_exp == 6) kern = k_convw<NN, TW, R, 6, PL>;
-    else if (g->opt_wino_exp == 7) kern = k_convw<NN, TW, R, 7, PL>;
-    else if (g->opt_wino_exp == 8) kern = k_convw<NN, TW, R, 8, PL>;
-#endif
-    { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a, total_tiles);
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    return launch_conv_kernel(k_convw<NN, TW, R>, dim3(persistent_grid(256, total_tiles)), dim3(512), lds, st, a, total_tiles);
 }
 // tiles of 512 pixels: 8 x 64 (64 x 64, 128 x 128), 16 x 32 (96 x 96, 32 x 32); 16 x 16 at 48 x 48
 static int wino_tiles(int B, int N) {
@@ -1629,18 +1359,6 @@ static bool wino_applies(const qgx_generator *g, const LayerHost &L, int which, 
     const int tiles = wino_tiles(B, N), si = wino_size_index(N);
     const bool on = g->opt_wino == 1 || (g->opt_wino == 2 && si >= 0 && g->auto_wino_n[si]);
     return on && L.ww[which] && tiles > 0 && tiles >= g->opt_wino_min_tiles;
-}
-// A/B library only: layer 1 stores channel-planar rows and the Winograd layer's input transform runs on the matrix cores
-// (conv_wino.hpp PL).  Measured against the product's pixel-major form (bench_tools/ab_conv.py, wino_pl): 64 x 64 / 128 members
-// -3 us on layer 2 and -2...-4 us on layer 1 of 370; 96 x 96 302 vs 206 us, 128 x 128 230 vs 153 us (8-pixel octets make the x halo of
-// the column-tiled shapes 1.33x, and the kernels spill) — not in the product.
-static bool wino_planar(const qgx_generator *g) {
-#ifdef QGX_AB
-    return g->opt_wino_pl != 0;
-#else
-    (void)g;
-    return false;
-#endif
 }
 // The Winograd layer's tile rows for B members at N x N: the full shape of wino_tiles() or, at every size but 48 x 48, a
 // smaller one.  256 persistent workgroups take ceil(tiles / 256) rounds, so the shape is chosen by rounds x cost per tile:
@@ -1676,7 +1394,6 @@ struct Layer2Plan {
                             //   and no 8-row pair kernel for (7, 8) (8 tiles of 512 pixels would leave 248 CUs idle)
     bool wino = false;      // the Winograd form runs (then layer 1's range guard covers its input transform too) ...
     int which = 0;          //   ... with these weights of LayerHost::ww: 0 plain, 1 folded
-    bool planar = false;    //   ... on channel-planar rows (wino_planar)
     int tw = 0, rows = 0;   //   ... on tiles of rows x tw pixels
     bool wino2 = false;     //   ... as k_convw2
     int kernel = 0;         // 0 exact-f32 MFMA, 1 the 25-tap f16x3 kernel, 2 its split-K form, 3 k_convw, 4 k_convw2
@@ -1688,35 +1405,31 @@ static Layer2Plan plan_layer2(const qgx_generator *g, const NetHost &net, int B,
     p.which = p.fold ? 1 : 0;
     const int r2 = rows_h2(N);
     if (!x3 || r2 <= 0) return p;
-    p.tiny = g->opt_h2 == 3 && B * (N / r2) < g->opt_part_max_tiles;
+    p.tiny = B * (N / r2) < g->opt_part_max_tiles;
     p.wino = !p.tiny && g->opt_first_h && wino_applies(g, net.L[1], p.which, B, N);
     p.kernel = p.tiny ? 2 : 1;
     if (!p.wino) return p;
-    p.planar = wino_planar(g);
-    p.rows = p.planar ? (N == 64 ? 8 : 16) : wino_rows(g, B, N);
-    p.tw = N == 48 ? 16 : (N == 64 || (N == 128 && !p.planar) ? 64 : 32);   // (planar 64-column tiles at 128 x 128: raw + transformed patch > 160 KB)
-    p.wino2 = !p.planar && g->opt_wino2 && g->opt_wino_exp == 0 && convw2_takes(N, p.tw, p.rows);
+    p.rows = wino_rows(g, B, N);
+    p.tw = N == 48 ? 16 : (N == 64 || N == 128 ? 64 : 32);
+    p.wino2 = g->opt_wino2 && convw2_takes(N, p.tw, p.rows);
     p.kernel = p.wino2 ? 4 : 3;
     return p;
 }
 
 static int launch_convw(qgx_generator *g, int layer, const LayerHost &L, const Layer2Plan &p, const void *in, void *out, int B,
                         int N, hipStream_t st) {
-#define QGX_LW(NN, TW, R, PL) \
-    if (N == NN && p.tw == TW && p.rows == R && p.planar == PL) return launch_convw_n<NN, TW, R, PL>(g, layer, L, p.which, p.wino2, in, out, B, st);
-#ifdef QGX_AB
-    QGX_LW(32, 32, 16, true) QGX_LW(48, 16, 16, true) QGX_LW(64, 64, 8, true) QGX_LW(96, 32, 16, true) QGX_LW(128, 32, 16, true)
-#endif
-    QGX_LW(32, 32, 8, false) QGX_LW(32, 32, 16, false) QGX_LW(48, 16, 16, false) QGX_LW(64, 64, 4, false) QGX_LW(64, 64, 8, false)
-    QGX_LW(96, 32, 12, false) QGX_LW(96, 32, 16, false) QGX_LW(128, 64, 4, false) QGX_LW(128, 64, 8, false)
+#define QGX_LW(NN, TW, R) \
+    if (N == NN && p.tw == TW && p.rows == R) return launch_convw_n<NN, TW, R>(g, layer, L, p.which, p.wino2, in, out, B, st);
+    QGX_LW(32, 32, 8) QGX_LW(32, 32, 16) QGX_LW(48, 16, 16) QGX_LW(64, 64, 4) QGX_LW(64, 64, 8)
+    QGX_LW(96, 32, 12) QGX_LW(96, 32, 16) QGX_LW(128, 64, 4) QGX_LW(128, 64, 8)
 #undef QGX_LW
     QGX_REQUIRE(false, "generator: layer 1 was stored for the Winograd layer, which did not run (N=%d)", N);
 }
 
 // Layers 5-8 of the 16-bit path.  `pairs` bit 0: layers (5, 6), bit 1: layers (7, 8) as ONE launch of the pair kernel on R-row
 // strips of an NN x NN grid (the intermediate activation stays in LDS), else as two kernels.  `cur` holds layer 4's output,
-// `oth` takes a layer's output; which buffer ends up with which layer is what qgx_debug_read_act and "stop_layer" rely on.
-template <int NS, int NN, int R>
+// `oth` takes a layer's output; which buffer ends up with which layer is what qgx_debug_read_act relies on.
+template <int NN, int R>
 static int layers_5_to_8(qgx_generator *g, const NetHost &net, int pairs, float *cur, float *oth, float *yc, int Bc, int N,
                          hipStream_t st) {
     int rc;
@@ -1724,15 +1437,14 @@ static int layers_5_to_8(qgx_generator *g, const NetHost &net, int pairs, float 
         if ((rc = launch_convh_pair<32, false, false, NN, R>(g, 4, net.L[4], net.L[5], cur, oth, Bc, N, 0, st))) return rc;
         std::swap(cur, oth);
     } else {
-        if ((rc = conv3x3_half<32, 32, NS, false>(g, 4, net.L[4], cur, oth, Bc, N, st))) return rc;
-        if ((rc = conv3x3_half<32, 32, NS, false>(g, 5, net.L[5], oth, cur, Bc, N, st))) return rc;
+        if ((rc = conv3x3_half<32, 32, false>(g, 4, net.L[4], cur, oth, Bc, N, st))) return rc;
+        if ((rc = conv3x3_half<32, 32, false>(g, 5, net.L[5], oth, cur, Bc, N, st))) return rc;
     }
     if (pairs & 2) return launch_convh_pair<32, true, false, NN, R>(g, 6, net.L[6], net.L[7], cur, yc, Bc, N, net.n_out, st);
-    if ((rc = conv3x3_half<32, 32, NS, true>(g, 6, net.L[6], cur, oth, Bc, N, st))) return rc;
+    if ((rc = conv3x3_half<32, 32, true>(g, 6, net.L[6], cur, oth, Bc, N, st))) return rc;
     return launch_conv_last(g, net.L[7], oth, yc, Bc, N, net.n_out, st);
 }
 
-template <int NS>
 static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N,
                             hipStream_t st) {
     int rc;
@@ -1748,36 +1460,22 @@ static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x
         LayerHost L0 = net.L[0], L1 = net.L[1];
         if (p.fold) {
             L0.scale = L0.ones; L0.shift = L0.zeros;
-            L1.wh[1] = L1.whF; L1.wh_unscale[1] = L1.whF_unscale; L1.bias = L1.biasF; L1.wh16 = L1.wh16F;
+            L1.wh = L1.whF; L1.wh_unscale = L1.whF_unscale; L1.bias = L1.biasF;
         }
-        if (NS == 2 && g->opt_first_h) {
-            rc = net.n_in == 4 ? launch_convh_first<4>(g, L0, xc, A, Bc, N, st, p.wino, p.wino && p.planar)
-                               : launch_convh_first<2>(g, L0, xc, A, Bc, N, st, p.wino, p.wino && p.planar);
-        } else if (net.n_in == 4) rc = launch_conv<4, 128, 5, 4, true, false, 2, NS>(g, 0, net.L[0], xc, A, Bc, N, 128, st);
-        else rc = launch_conv<2, 128, 5, 2, true, false, 2, NS>(g, 0, net.L[0], xc, A, Bc, N, 128, st);
+        if (g->opt_first_h) {
+            rc = net.n_in == 4 ? launch_convh_first<4>(g, L0, xc, A, Bc, N, st, p.wino)
+                               : launch_convh_first<2>(g, L0, xc, A, Bc, N, st, p.wino);
+        } else rc = launch_conv_first(g, net.L[0], net.n_in, 2, 2, xc, A, Bc, N, st);
         if (rc) return rc;
-#ifdef QGX_AB
-        if (g->opt_stop_layer == 1) return QGX_OK;
-#endif
         bool done1 = false;
         if (p.tiny && (rc = launch_convh2_part<128, 64, 5, false>(g, 1, L1, A, Bb, Bc, N, st, done1))) return rc;
         if (!done1 && p.wino) {
             if ((rc = launch_convw(g, 1, L1, p, A, Bb, Bc, N, st))) return rc;
             done1 = true;
         }
-#ifdef QGX_AB
-        if (!done1 && NS == 2 && g->opt_h4 && (rc = launch_convh4(g, 1, L1, A, Bb, Bc, N, st, done1))) return rc;
-        if (!done1 && NS == 2 && g->opt_h3 && (rc = launch_convh3(g, 1, L1, A, Bb, Bc, N, st, done1))) return rc;
-#endif
-        if (!done1 && NS == 2 && (g->opt_h2 & 2) && (rc = launch_convh2<128, 64, 5, false>(g, 1, L1, A, Bb, Bc, N, st, done1))) return rc;
-#ifdef QGX_AB
-        if (!done1 && (rc = launch_convh<128, 64, 5, NS, false>(g, 1, L1, A, Bb, Bc, N, st))) return rc;
-        if (g->opt_stop_layer == 2) return QGX_OK;
-#else
+        if (!done1 && (rc = launch_convh2<128, 64, 5, false>(g, 1, L1, A, Bb, Bc, N, st, done1))) return rc;
         QGX_REQUIRE(done1, "generator: no f16x3 kernel for N=%d", N);
-#endif
-        const bool pairs_ok = NS == 2;                         // the pair kernels: f16x3
-        // ... and the fused (7, 8) pair writes at most two channels: a flux-form net takes layer 7's kernel and the VALU last layer
+        // the fused (7, 8) pair writes at most two channels: a flux-form net takes layer 7's kernel and the VALU last layer
         const int no78 = net.n_out <= 2 ? ~0 : ~2, tiny_no78 = net.n_out <= 2 ? ~0 : ~1;
         if (p.tiny) {
             // (local names: the 64-channel activation of layer 2 is in Bb; `cur` holds a layer's input, `oth` takes its output)
@@ -1785,39 +1483,39 @@ static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x
             // Layers (3, 4), (5, 6) and (7, 8) each as ONE launch on 2-row strips ("tiny_pairs" bits 2, 1, 0): a single member is
             // a chain of launch latencies, and a strip's fixed costs — layer B's 36 KB of MFMA weights above all — are cheaper
             // than a kernel boundary there; for (3, 4) the one launch also replaces split-K and its combine kernel
-            const int tp = pairs_ok && N == 64 ? g->opt_tiny_pairs & tiny_no78 : 0;
+            const int tp = N == 64 ? g->opt_tiny_pairs & tiny_no78 : 0;
             if (tp & 4) {
                 if ((rc = launch_convh_pair<64, false, false, 64, 2>(g, 2, net.L[2], net.L[3], cur, oth, Bc, N, 0, st))) return rc;
                 std::swap(cur, oth);
             } else {
                 bool done2 = false;
                 if ((rc = launch_convh2_part<64, 32, 3, false>(g, 2, net.L[2], cur, oth, Bc, N, st, done2))) return rc;
-                if (!done2 && (rc = conv3x3_half<64, 32, NS, false>(g, 2, net.L[2], cur, oth, Bc, N, st))) return rc;
-                if ((rc = conv3x3_half<32, 32, NS, false>(g, 3, net.L[3], oth, cur, Bc, N, st))) return rc;
+                if (!done2 && (rc = conv3x3_half<64, 32, false>(g, 2, net.L[2], cur, oth, Bc, N, st))) return rc;
+                if ((rc = conv3x3_half<32, 32, false>(g, 3, net.L[3], oth, cur, Bc, N, st))) return rc;
             }
-            if ((rc = layers_5_to_8<NS, 64, 2>(g, net, ((tp >> 1) & 1) | ((tp & 1) << 1), cur, oth, yc, Bc, N, st))) return rc;
+            if ((rc = layers_5_to_8<64, 2>(g, net, ((tp >> 1) & 1) | ((tp & 1) << 1), cur, oth, yc, Bc, N, st))) return rc;
             continue;
         }
         // 3x3 layers fused pairwise at 64 x 64; "fuse" bits: 1 = layers (5, 6), 2 = layers (7, 8), 4 = layers (3, 4) — the
         // 64-channel pair measured slower fused
-        const int fuse = pairs_ok && N == 64 ? g->opt_fuse & no78 : 0;
+        const int fuse = N == 64 ? g->opt_fuse & no78 : 0;
         if (fuse & 4) {
             if ((rc = launch_convh_pair<64, false, false>(g, 2, net.L[2], net.L[3], Bb, A, Bc, N, 0, st))) return rc;
         } else {
-            if ((rc = conv3x3_half<64, 32, NS, false>(g, 2, net.L[2], Bb, A, Bc, N, st))) return rc;
-            if ((rc = conv3x3_half<32, 32, NS, false>(g, 3, net.L[3], A, Bb, Bc, N, st))) return rc;
+            if ((rc = conv3x3_half<64, 32, false>(g, 2, net.L[2], Bb, A, Bc, N, st))) return rc;
+            if ((rc = conv3x3_half<32, 32, false>(g, 3, net.L[3], A, Bb, Bc, N, st))) return rc;
         }
         // here the activation is in A (fused pair) or Bb (two kernels)
         float *cur = (fuse & 4) ? A : Bb, *oth = (fuse & 4) ? Bb : A;
         if (fuse) {
             // (4-row strips for the pairs, as the Winograd layer's small shape, measured slower at 8 ... 48 members: 25.4 -> 30.8 us at
             // 16, 26.3 -> 47.4 at 24 — a strip's fixed costs, layer B's 36 KB of weights above all, do not halve with its rows)
-            rc = layers_5_to_8<NS, 64, 8>(g, net, fuse & 3, cur, oth, yc, Bc, N, st);
+            rc = layers_5_to_8<64, 8>(g, net, fuse & 3, cur, oth, yc, Bc, N, st);
         } else {
             // 96 x 96: the pair kernel on 4-row strips (a 6-row intermediate patch of 98 columns is 85 KB); "fuse96" bits as "fuse".
             // Every other grid: two kernels per pair
-            const int fuse96 = pairs_ok && N == 96 && Bc * 24 >= 256 ? g->opt_fuse96 & no78 : 0;
-            rc = layers_5_to_8<NS, 96, 4>(g, net, fuse96 & 3, cur, oth, yc, Bc, N, st);
+            const int fuse96 = N == 96 && Bc * 24 >= 256 ? g->opt_fuse96 & no78 : 0;
+            rc = layers_5_to_8<96, 4>(g, net, fuse96 & 3, cur, oth, yc, Bc, N, st);
         }
         if (rc) return rc;
     }
@@ -1828,20 +1526,9 @@ static int cnn_forward_half(qgx_generator *g, const NetHost &net, const float *x
 static int cnn_convs(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N, hipStream_t st) {
     int rc;
     if (net.generic) return cnng_convs(g, net, x, y, B, N, st);      // any other architecture than the shipped one: conv_generic.hip
-    if (g->opt_precision && half_path_ok(g, B, N))
-#ifdef QGX_AB
-        return g->opt_precision == 1 ? cnn_forward_half<1>(g, net, x, y, B, N, st) : cnn_forward_half<2>(g, net, x, y, B, N, st);
-#else
-        return cnn_forward_half<2>(g, net, x, y, B, N, st);
-#endif
+    if (half_path_ok(g, B, N)) return cnn_forward_half(g, net, x, y, B, N, st);
     float *A = g->work().actA, *Bb = g->work().actB;
-    if (net.n_in == 4) rc = g->opt_first_split == 2 ? launch_conv<4, 128, 5, 4, true, false, 2>(g, 0, net.L[0], x, A, B, N, 128, st)
-                       : g->opt_first_split == 4 ? launch_conv<4, 128, 5, 4, true, false, 4>(g, 0, net.L[0], x, A, B, N, 128, st)
-                                                 : launch_conv<4, 128, 5, 4, true, false, 1>(g, 0, net.L[0], x, A, B, N, 128, st);
-    else rc = g->opt_first_split == 2 ? launch_conv<2, 128, 5, 2, true, false, 2>(g, 0, net.L[0], x, A, B, N, 128, st)
-            : g->opt_first_split == 4 ? launch_conv<2, 128, 5, 2, true, false, 4>(g, 0, net.L[0], x, A, B, N, 128, st)
-                                      : launch_conv<2, 128, 5, 2, true, false, 1>(g, 0, net.L[0], x, A, B, N, 128, st);
-    if (rc) return rc;
+    if ((rc = launch_conv_first(g, net.L[0], net.n_in, g->opt_first_split, 0, x, A, B, N, st))) return rc;
     // calibration runs record the largest stored activation of every layer (launch_absmax keeps a running maximum
     // in calib_dev[2 * layer + 1]: it updates word [1] of the pair it is given)
     auto rec = [&](int layer, const float *buf, int ch) {
@@ -1876,9 +1563,6 @@ int cnn_forward(qgx_generator *g, const NetHost &net, const float *x, float *y, 
     float *F = g->work().F;
     QGX_REQUIRE(F && g->work().cap_elems >= (size_t)B * N * N, "flux-form net: the flux buffer is not reserved");
     if (const int rc = cnn_convs(g, net, x, F, B, N, st)) return rc;
-#ifdef QGX_AB
-    if (g->opt_stop_layer) return QGX_OK;
-#endif
     return fluxdiv_forward(F, y, B, N, st);
 }
 
@@ -1893,12 +1577,7 @@ bool cnn_size_ok(const qgx_generator *g, const NetHost &net, int B, int N) {
     if (B < 1 || R <= 0 || N % R) return false;
     if (net.flux() && !fluxdiv_size_ok(N)) return false;
     if (net.generic) return cnng_size_ok(net, B, N);
-    if (g->opt_precision && half_path_ok(g, B, N)) {
-#ifdef QGX_AB
-        if (rows_h2(N) <= 0) return true;      // kernels of the A/B library's experiments: their launchers decide
-#endif
-        return rows_h2(N) > 0 && N % 4 == 0;
-    }
+    if (half_path_ok(g, B, N)) return N % 4 == 0;      // (launch_convh_first's float4 rows)
     constexpr size_t LIM = 160 * 1024;
     auto patch = [&](int rows, int ks, int stride) { return (size_t)(rows + ks - 1) * N * stride * sizeof(float); };
     if (patch(R, 5, net.n_in) > LIM) return false;                                        // layer 1: planar input
@@ -2085,8 +1764,7 @@ static int calibrate(qgx_generator *g) {
         // layer 1 with an identity BatchNorm = what the folded f16x3 variant stores
         LayerHost L0 = net.L[0];
         L0.scale = L0.ones; L0.shift = L0.zeros;
-        rc = net.n_in == 4 ? launch_conv<4, 128, 5, 4, true, false, 2>(g, 0, L0, w.X, w.actA, B, N, 128, nullptr)
-                           : launch_conv<2, 128, 5, 2, true, false, 2>(g, 0, L0, w.X, w.actA, B, N, 128, nullptr);
+        rc = launch_conv_first(g, L0, net.n_in, 2, 0, w.X, w.actA, B, N, nullptr);
         if (rc) break;
         launch_absmax(w.actA, (size_t)B * npix * 128, cd + 16, nullptr);
     }
@@ -2225,40 +1903,23 @@ extern "C" int qgx_generator_set_option(qgx_generator *g, const char *name, int 
     else if (!strcmp(name, "last_valu")) g->opt_last_valu = value ? 1 : 0;
     else if (!strcmp(name, "small")) g->opt_small = value ? 1 : 0;
     else if (!strcmp(name, "v3")) g->opt_v3 = value;   // -1 auto, 0 off, 1 = slice per tap row, 2 = per chunk
-#ifndef QGX_AB
-    else if (!strcmp(name, "res") || !strcmp(name, "h3") || !strcmp(name, "h4") || !strcmp(name, "half_nw") ||
-             !strcmp(name, "h2") || (!strcmp(name, "precision") && value == 1))
-        QGX_REQUIRE(false, "generator option '%s'=%d selects a kernel of the A/B library only (make ab, QGX_LIB=libqgx_ab.so)", name, value);
-#endif
-    else if (!strcmp(name, "precision")) { QGX_REQUIRE(value == 0 || value == 1 || value == 3, "precision must be 0 (f32), 1 (f16) or 3 (f16x3)"); g->opt_precision = value; }
+    else if (!strcmp(name, "precision")) { QGX_REQUIRE(value == 0 || value == 3, "precision must be 0 (f32) or 3 (f16x3)"); g->opt_precision = value; }
     else if (!strcmp(name, "member_chunk")) { QGX_REQUIRE(value >= 0, "member_chunk must be >= 0"); g->opt_member_chunk = value; }
-    else if (!strcmp(name, "res")) g->opt_res = value ? 1 : 0;
-    else if (!strcmp(name, "h2")) g->opt_h2 = value & 3;
     else if (!strcmp(name, "pair")) g->opt_pair = value ? 1 : 0;
     else if (!strcmp(name, "fuse")) g->opt_fuse = value & 7;
     else if (!strcmp(name, "fuse96")) g->opt_fuse96 = value & 3;
     else if (!strcmp(name, "small_tiles")) g->opt_small_tiles = value ? 1 : 0;
     else if (!strcmp(name, "tiny_pairs")) { QGX_REQUIRE(value >= 0 && value <= 7, "tiny_pairs: bits 0 (layers 7, 8), 1 (layers 5, 6), 2 (layers 3, 4)"); g->opt_tiny_pairs = value; }
-#ifdef QGX_AB
-    else if (!strcmp(name, "pair_lp")) g->opt_pair_lp = value;
-#endif
-    else if (!strcmp(name, "h3")) g->opt_h3 = value ? 1 : 0;
     else if (!strcmp(name, "last_rows")) g->opt_last_rows = value;
     else if (!strcmp(name, "part_max_tiles")) g->opt_part_max_tiles = value;
     else if (!strcmp(name, "fold")) g->opt_fold = value ? 1 : 0;
     else if (!strcmp(name, "wino")) { QGX_REQUIRE(value >= 0 && value <= 2, "wino must be 0 (never), 1 (every specialised grid) or 2 (per grid size, as calibrated)"); g->opt_wino = value; }
     else if (!strcmp(name, "wino2")) g->opt_wino2 = value ? 1 : 0;
-#ifdef QGX_AB
-    else if (!strcmp(name, "wino_exp")) g->opt_wino_exp = value;
-    else if (!strcmp(name, "wino_pl")) g->opt_wino_pl = value;
-    else if (!strcmp(name, "stop_layer")) g->opt_stop_layer = value;
-#endif
     else if (!strcmp(name, "h2_rows96")) { QGX_REQUIRE(value == 0 || value == 12 || value == 16, "h2_rows96 must be 0 (auto), 12 or 16"); g->opt_h2_rows96 = value; }
     else if (!strcmp(name, "wino_rows64")) { QGX_REQUIRE(value == 0 || value == 4 || value == 8, "wino_rows64 must be 0 (auto), 4 or 8"); g->opt_wino_rows64 = value; }
     else if (!strcmp(name, "wino_rows96")) { QGX_REQUIRE(value == 0 || value == 12 || value == 16, "wino_rows96 must be 0 (auto), 12 or 16"); g->opt_wino_rows96 = value; }
     else if (!strcmp(name, "wino_min_tiles")) { QGX_REQUIRE(value >= 1, "wino_min_tiles must be >= 1"); g->opt_wino_min_tiles = value; }
     else if (!strcmp(name, "h2_grid")) g->opt_h2_grid = value;
-    else if (!strcmp(name, "h4")) g->opt_h4 = value;
     else if (!strcmp(name, "prio_alt")) g->opt_prio_alt = value;
     else if (!strcmp(name, "h2_w8")) g->opt_h2_w8 = value & 3;
     else if (!strcmp(name, "h2_tw32")) g->opt_h2_tw32 = value ? 1 : 0;
@@ -2266,7 +1927,6 @@ extern "C" int qgx_generator_set_option(qgx_generator *g, const char *name, int 
     else if (!strcmp(name, "h2_w8_min96")) g->opt_h2_w8_min96 = value;
     else if (!strcmp(name, "half_min_tiles")) { QGX_REQUIRE(value >= 1, "half_min_tiles must be >= 1"); g->opt_half_min_tiles = value; }
     else if (!strcmp(name, "first_h")) g->opt_first_h = value ? 1 : 0;
-    else if (!strcmp(name, "half_nw")) { QGX_REQUIRE(value == 4 || value == 8, "half_nw must be 4 or 8"); g->opt_half_nw = value; }
     else if (!strcmp(name, "ascale_log2")) { QGX_REQUIRE(value >= -24 && value <= 24, "ascale_log2 must be in -24..24"); g->opt_ascale = ldexpf(1.f, value); }
     else if (!strcmp(name, "prof_every")) { QGX_REQUIRE(value >= 1, "prof_every must be >= 1"); g->prof_every = value; }
     else if (!strcmp(name, "auto")) { g->opt_precision = g->auto_precision; g->opt_fold = g->auto_fold; g->opt_ascale = ldexpf(1.f, g->auto_ascale_log2); g->opt_wino = 2; }
@@ -2287,7 +1947,7 @@ extern "C" int qgx_debug_read_act(qgx_generator *g, int which, void *dst_dev, si
 }
 #endif
 #ifdef QGX_STAMPS
-// diagnostic builds only (bench_tools/conv_stamps.py): where the s_memtime trace of k_convh_res goes
+// diagnostic builds only (bench_tools/conv_stamps.py): where the clock-stamp trace of layer `layer` goes
 extern "C" int qgx_debug_set_stamps(qgx_generator *g, void *buf, int layer) {
     g->stamps = (unsigned long long *)buf;
     g->stamp_layer = layer;

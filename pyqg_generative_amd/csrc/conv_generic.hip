@@ -338,17 +338,8 @@ static int launch_convg(qgx_generator *g, int layer, const LayerHost &L, bool fi
     a.N = N; a.R = R; a.ks = L.ks; a.cin = L.cin; a.cinp = L.cinp; a.coutp = L.coutp; a.cstore = L.cstore;
     a.planar_in = first; a.final = last;
     dim3 grid(B * (N / R), ny), block(256);
-#define QGX_LG(NTV, MTV)                                                                             \
-    {                                                                                                \
-        auto kern = k_convg<NTV, MTV>;                                                                 \
-        { const int lrc_ = ensure_dynamic_lds((const void *)kern, (int)lds); if (lrc_) return lrc_; } \
-        hipLaunchKernelGGL(kern, grid, block, lds, st, a);                                           \
-    }
-    if (R * N / 32 > 8) { if (nt == 2) QGX_LG(2, 3) else QGX_LG(1, 3) }
-    else if (nt == 2) QGX_LG(2, 2) else QGX_LG(1, 2)
-#undef QGX_LG
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    auto kern = R * N / 32 > 8 ? (nt == 2 ? k_convg<2, 3> : k_convg<1, 3>) : (nt == 2 ? k_convg<2, 2> : k_convg<1, 2>);
+    return launch_conv_kernel(kern, grid, block, lds, st, a);
 }
 
 // the n_layers convolutions: x planar (B, n_in, N, N) -> y planar (B, n_out, N, N); activations alternate actA, actB

@@ -1,38 +1,34 @@
 // Hidden conv layers on the 16-bit matrix cores (v_mfma_f32_32x32x16_f16, f32 accumulate).
 // Included by conv.hip (inside namespace qgx, after ConvArgs / conv_smem).
 //
-// Two arithmetic modes share one kernel:
-//   NS = 2  "f16x3": every f32 operand x is carried as the pair hi = f16(x), lo = f16(x - hi)
-//           (22 significant bits) and a product a*b is evaluated as a_hi*b_hi + a_hi*b_lo + a_lo*b_hi
-//           with three MFMAs into one f32 accumulator; the dropped a_lo*b_lo term is 2^-22 relative,
-//           i.e. the result carries f32-class accuracy at 16/3 of the f32 MFMA rate.
-//   NS = 1  "f16": plain f16 operands (the precision class of TF32, which is what the reference's
-//           PyTorch convolutions use by default on its own GPUs), one MFMA per product.
+// The arithmetic is "f16x3": every f32 operand x is carried as the pair hi = f16(x), lo = f16(x - hi)
+// (22 significant bits) and a product a*b is evaluated as a_hi*b_hi + a_hi*b_lo + a_lo*b_hi with three
+// MFMAs into one f32 accumulator; the dropped a_lo*b_lo term is 2^-22 relative, i.e. the result carries
+// f32-class accuracy at 16/3 of the f32 MFMA rate.  (A plain-f16 mode, one MFMA per product, was removed
+// with the other A/B-only variants: DESIGN.md 3.2b.)
 // Weights are pre-scaled by a per-layer power of two so that neither part is subnormal; the
 // epilogue removes the scale exactly.
 //
-// Activation layout in HBM: [B][N][N][C/8][NS][8] f16 — per pixel, per group of 8 channels, the hi
-// octet followed (NS = 2) by the lo octet.  A channel chunk (32 channels for NS = 1, 16 for NS = 2)
-// is 64 contiguous bytes of a pixel's record = four 16-byte units = exactly the K = 16 operand
-// fragments of the MFMA: lane half h reads unit (2j + h) [NS = 1, j = K step] or (2h + j) [NS = 2,
-// j = part].
+// Activation layout in HBM: [B][N][N][C/8][2][8] f16 — per pixel, per group of 8 channels, the hi
+// octet followed by the lo octet.  A 16-channel chunk is 64 contiguous bytes of a pixel's record = four
+// 16-byte units = exactly the K = 16 operand fragments of the MFMA: lane half h reads unit (2h + j),
+// j = part.
 //
 // The MFMA roles are swapped with respect to the f32 kernels: A = weights (rows = output channels),
 // B = pixels (columns), so that an accumulator lane owns ONE pixel and 4 consecutive output channels
 // per register quad; one v_permlane32_swap per register pair assembles whole 8-channel octets and the
 // epilogue (bias + ReLU + BatchNorm affine + hi/lo split) stores 16 bytes per lane.
 //
-// One workgroup = 8 waves owns R full-width rows (16 or 24 M-tiles of 32 pixels), is persistent over
-// its tiles, and takes BOTH operands from LDS: the (R+K-1)-row patch of one channel chunk (pixel
-// stride 80 B: conflict-free ds_read_b128) and the weight slice of TPS taps (double buffered).  The
-// next chunk's patch and the next weight slice are fetched into registers while the current one is
-// consumed and written to LDS at the stage boundary.
+// A workgroup owns a tile of R rows, is persistent over its tiles, and takes BOTH operands from LDS:
+// the (R+K-1)-row patch of one channel chunk (pixel stride 80 B: conflict-free ds_read_b128) and the
+// weight slice of TPS taps.  The next chunk's patch and the next weight slice are fetched into
+// registers while the current one is consumed and written to LDS at the stage boundary.
 #pragma once
 
 // (h8, h2, u32x4, pack_h2, range_guard: conv_types.hpp)
 
 struct ConvHArgs {
-    const void *in;        // [B][N][N][CIN/8][NS][8] f16
+    const void *in;        // [B][N][N][CIN/8][2][8] f16
     void *out;             // same with COUT, or NHWC f32 (OUTF32)
     const void *w;         // [chunk][tap][j][h][COUT][8] f16 (slices of TPS taps are contiguous)
     const float *bias, *scale, *shift;
@@ -78,7 +74,7 @@ struct ConvHArgs {
 // lane (li, h) owns pixel li; register r holds output channel cb + (r & 3) + 8 (r >> 2) + 4 h.
 // guard_mul: the consumer's amplification of the stored values before ITS 16-bit split (the Winograd layer's input
 // transform: up to 16) — the guard then fires at 65504 / guard_mul
-template <int NS, bool OUTF32>
+template <bool OUTF32>
 __device__ __forceinline__ void store_tile_t(const f32x16 &acc, int cb, int h, char *pix, const float *bias,
                                              const float *scale, const float *shift, float unscale, float ascale,
                                              unsigned *range, unsigned range_bit, float guard_mul = 1.f) {
@@ -120,308 +116,19 @@ __device__ __forceinline__ void store_tile_t(const f32x16 &acc, int cb, int h, c
             auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
             auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
             u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
-            *reinterpret_cast<u32x4 *>(pix + (size_t)g * 16 * NS) = o;
-            if constexpr (NS == 2) {
-                a0 = pack_h2(lo[0], lo[1]); a1 = pack_h2(lo[2], lo[3]);
-                b0 = pack_h2(lo[4], lo[5]); b1 = pack_h2(lo[6], lo[7]);
-                s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                u32x4 ol = {s0[0], s1[0], s0[1], s1[1]};
-                *reinterpret_cast<u32x4 *>(pix + (size_t)g * 32 + 16) = ol;
-            }
+            *reinterpret_cast<u32x4 *>(pix + (size_t)g * 32) = o;
+            a0 = pack_h2(lo[0], lo[1]); a1 = pack_h2(lo[2], lo[3]);
+            b0 = pack_h2(lo[4], lo[5]); b1 = pack_h2(lo[6], lo[7]);
+            s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+            s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+            u32x4 ol = {s0[0], s1[0], s0[1], s1[1]};
+            *reinterpret_cast<u32x4 *>(pix + (size_t)g * 32 + 16) = ol;
         }
     }
 }
-
-// Epilogue of one 32(pixels) x 32(out channels) accumulator tile in the UN-swapped layout (mfma(patch, weights)):
-// lane (li, h) owns output channel cb + li; register r holds pixel (r & 3) + 8 (r >> 2) + 4 h of the tile's 32
-// consecutive strip pixels.  Stores the channel-planar form the Winograd layer's MFMA input transform reads
-// (conv_wino.hpp): [b][y][c][hi | lo][x] f16 — after one v_permlane32_swap per register pair a lane holds 8 consecutive
-// pixels of its channel: lane half h stores the octets 2 m + h (m = 0, 1), 16 bytes of hi and 16 of lo each.
-// rowbase: the channel-0 hi row of the tile's first pixel's image row; p0: index of the tile's first pixel in the strip.
-__device__ __forceinline__ void store_tile_planar(const f32x16 &acc, int c, int h, char *strip, int p0, int N, int COUT,
-                                                  const float *bias, const float *scale, const float *shift, float unscale,
-                                                  float ascale, unsigned *range, unsigned range_bit, float guard_mul) {
-    const float bi = bias[c], sc = scale[c] * ascale, sh = shift[c] * ascale;     // ascale: a power of two, exact
-    float v[16];
-    float mx = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        v[r] = fmaxf(acc[r] * unscale + bi, 0.f) * sc + sh;
-        mx = fmaxf(mx, fabsf(v[r]));
-    }
-    range_guard(mx * guard_mul, range, range_bit);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        // registers 8 m .. 8 m + 3: pixels 16 m + 4 h + (0..3) ("a"), 8 m + 4 .. 8 m + 7: pixels 16 m + 8 + 4 h + (0..3) ("b")
-        unsigned ah[2], bh[2], al[2], bl[2];
-#pragma unroll
-        for (int e2 = 0; e2 < 2; ++e2) {
-            const float a0 = v[8 * m + 2 * e2], a1 = v[8 * m + 2 * e2 + 1], b0 = v[8 * m + 4 + 2 * e2], b1 = v[8 * m + 5 + 2 * e2];
-            const _Float16 a0h = (_Float16)a0, a1h = (_Float16)a1, b0h = (_Float16)b0, b1h = (_Float16)b1;
-            ah[e2] = pack_h2((float)a0h, (float)a1h); bh[e2] = pack_h2((float)b0h, (float)b1h);
-            al[e2] = pack_h2(a0 - (float)a0h, a1 - (float)a1h); bl[e2] = pack_h2(b0 - (float)b0h, b1 - (float)b1h);
-        }
-        auto s0 = __builtin_amdgcn_permlane32_swap(ah[0], bh[0], false, false);
-        auto s1 = __builtin_amdgcn_permlane32_swap(ah[1], bh[1], false, false);
-        const u32x4 oh = {s0[0], s1[0], s0[1], s1[1]};
-        s0 = __builtin_amdgcn_permlane32_swap(al[0], bl[0], false, false);
-        s1 = __builtin_amdgcn_permlane32_swap(al[1], bl[1], false, false);
-        const u32x4 ol = {s0[0], s1[0], s0[1], s1[1]};
-        const int px = p0 + 8 * (2 * m + h);                  // first of this lane's 8 consecutive strip pixels
-        const int y = px / N, x = px - y * N;
-        char *o = strip + (((size_t)y * COUT + c) * 2 * N + x) * 2;
-        *reinterpret_cast<u32x4 *>(o) = oh;
-        *reinterpret_cast<u32x4 *>(o + 2 * N) = ol;
-    }
-}
-
-#ifdef QGX_AB   // generic run-time-N kernel (and the plain-f16 mode): A/B builds only, see conv.hip
-template <int CIN, int COUT, int KS, int NS, int MT, int TPS, int PPT, bool OUTF32, int NW = 8, bool SWZ = false>
-__global__ __launch_bounds__(NW * 64) void k_convh(ConvHArgs a, int total_tiles) {
-    constexpr int NTHR = NW * 64;
-    constexpr int NT = COUT / 32;
-    constexpr int P = KS / 2, T = KS * KS;
-    constexpr int CC = NS == 1 ? 32 : 16;
-    constexpr int NCH = CIN / CC;
-    constexpr int PIXB = CIN * 2 * NS;                  // bytes of one input pixel record
-    constexpr int OPIXB = OUTF32 ? COUT * 4 : COUT * 2 * NS;
-    // LDS bytes per patch pixel: 64 payload + 16 pad, or (SWZ) 64 with the unit index XOR-swizzled by
-    // bits 2..3 of the pixel index — both make every 16-lane ds_read_b128 group conflict-free
-    constexpr int PSTR = SWZ ? 64 : 80;
-    constexpr int TAPB = 4 * COUT * 16;                 // weight bytes per tap: [j][h][cout][8 f16]
-    constexpr int WSB = TPS * TAPB;
-    constexpr int NSL = T / TPS;
-    constexpr int WU = WSB / 16;
-    constexpr int WPT = (WU + NTHR - 1) / NTHR;
-    static_assert(T % TPS == 0 && COUT % 32 == 0 && CIN % CC == 0, "shape");
-    const int N = a.N, R = a.R;
-    const int PR = R + KS - 1;
-    const int patch_bytes = PR * N * PSTR;
-    const int PU = PR * N * 4;                          // 16-byte units of the patch payload
-    char *const lds0 = conv_smem;
-    char *const wlds0 = lds0 + patch_bytes;
-    // epilogue parameters (bias | BN scale | BN shift) live in LDS: a global load in the epilogue would put a
-    // full memory latency, and a wait on the tile's own output stores, on the critical path of every tile
-    float *const ep = reinterpret_cast<float *>(wlds0 + 2 * WSB);
-    const char *const inb = reinterpret_cast<const char *>(a.in);
-    const char *const wb = reinterpret_cast<const char *>(a.w);
-    const int tiles_per_img = N / R;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 31, h = lane >> 5;
-    const int n_my = blockIdx.x < (unsigned)total_tiles ? (total_tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
-    const int ntiles = R * N / 32;
-
-#define QGX_HP_LOAD(TI, CH, V)                                                                              \
-    {                                                                                                       \
-        const int tile_ = blockIdx.x + (TI) * gridDim.x;                                                    \
-        const int b_ = tile_ / tiles_per_img;                                                               \
-        const int y0_ = (tile_ - b_ * tiles_per_img) * R;                                                   \
-        _Pragma("unroll") for (int u = 0; u < PPT; ++u) {                                                   \
-            int it_ = u * NTHR + threadIdx.x;                                                                \
-            it_ = it_ < PU ? it_ : PU - 1; /* clamped: branch-free, the store is predicated instead */      \
-            const int un_ = it_ & 3, pl_ = it_ >> 2;                                                        \
-            const int pr_ = pl_ / N, x_ = pl_ - pr_ * N;                                                    \
-            int gy_ = y0_ - P + pr_;                                                                        \
-            gy_ = gy_ < 0 ? gy_ + N : (gy_ >= N ? gy_ - N : gy_);                                           \
-            V[u] = *reinterpret_cast<const f32x4 *>(                                                        \
-                inb + (((size_t)b_ * N + gy_) * N + x_) * PIXB + (CH) * 64 + un_ * 16);                     \
-        }                                                                                                   \
-    }
-#define QGX_HP_STORE(V)                                                                                     \
-    {                                                                                                       \
-        _Pragma("unroll") for (int u = 0; u < PPT; ++u) {                                                   \
-            const int it_ = u * NTHR + threadIdx.x;                                                          \
-            if (it_ < PU)                                                                                   \
-                *reinterpret_cast<f32x4 *>(lds0 + (it_ >> 2) * PSTR +                                       \
-                                           (SWZ ? ((it_ & 3) ^ ((it_ >> 4) & 3)) : (it_ & 3)) * 16) = V[u];  \
-        }                                                                                                   \
-    }
-#define QGX_HW_LOAD(CH, SL, V)                                                                              \
-    {                                                                                                       \
-        const f32x4 *src_ = reinterpret_cast<const f32x4 *>(wb + ((size_t)(CH) * NSL + (SL)) * WSB);        \
-        _Pragma("unroll") for (int u = 0; u < WPT; ++u) {                                                   \
-            const int it_ = u * NTHR + threadIdx.x;                                                          \
-            V[u] = src_[it_ < WU ? it_ : WU - 1];                                                           \
-        }                                                                                                   \
-    }
-#define QGX_HW_STORE(BUF, V)                                                                                \
-    {                                                                                                       \
-        _Pragma("unroll") for (int u = 0; u < WPT; ++u) {                                                   \
-            const int it_ = u * NTHR + threadIdx.x;                                                          \
-            if (it_ < WU) *reinterpret_cast<f32x4 *>((BUF) + it_ * 16) = V[u];                              \
-        }                                                                                                   \
-    }
-
-    if (n_my == 0) return;
-    int stamp_i = 0;
-    (void)stamp_i;
-    QGX_STAMP()
-    for (int i = threadIdx.x; i < 3 * COUT; i += NTHR)
-        ep[i] = i < COUT ? a.bias[i] : (i < 2 * COUT ? a.scale[i - COUT] : a.shift[i - 2 * COUT]);
-    // ---- prologue: first chunk's patch and first weight slice, synchronously
-    {
-        f32x4 pv[PPT];
-        QGX_HP_LOAD(0, 0, pv)
-        QGX_HP_STORE(pv)
-        f32x4 wv[WPT];
-        QGX_HW_LOAD(0, 0, wv)
-        QGX_HW_STORE(wlds0, wv)
-    }
-    __syncthreads();
-
-    int py[MT], px[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        int tile = wave + NW * mt;
-        if (tile >= ntiles) tile = wave % ntiles;
-        const int p = tile * 32 + li;
-        py[mt] = p / N;
-        px[mt] = p - py[mt] * N;
-    }
-    // lane-dependent parts of the fragment addresses: unit u0 (+ j*PJ bytes for fragment j)
-    const int u0 = NS == 1 ? h : 2 * h;
-    constexpr int PJ = NS == 1 ? 32 : 16;
-#define QGX_HP_ADDR(PL) (SWZ ? (PL) * 64 + ((u0 ^ (((PL) >> 2) & 3)) * 16) : (PL) * 80 + u0 * 16)
-#define QGX_HP_FRAG(AOFF, J) (SWZ ? ((AOFF) ^ ((J) * PJ)) : ((AOFF) + (J) * PJ))
-    const int wofs = (h * COUT + li) * 16;              // + (j*2*COUT + nt*32)*16
-    f32x16 acc[MT][NT];
-    int cur_w = 0;
-    for (int ti = 0; ti < n_my; ++ti) {
-        for (int ch = 0; ch < NCH; ++ch) {
-            if (ch == 0) {
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
-            }
-            const int nch = ch + 1 < NCH ? ch + 1 : 0;
-            const int nti = ch + 1 < NCH ? ti : ti + 1;
-            const bool have_next_chunk = nti < n_my;
-            // ---- next chunk's patch: into registers now, into LDS when this chunk is consumed
-            f32x4 pv[PPT];
-            QGX_HP_LOAD(have_next_chunk ? nti : ti, have_next_chunk ? nch : ch, pv)
-#pragma unroll
-            for (int sl = 0; sl < NSL; ++sl) {
-                f32x4 wv[WPT];
-                const bool last_stage = !have_next_chunk && sl == NSL - 1;
-                {
-                    const int wch = sl + 1 < NSL ? ch : (have_next_chunk ? nch : ch);
-                    const int wsl = sl + 1 < NSL ? sl + 1 : (have_next_chunk ? 0 : sl);
-                    QGX_HW_LOAD(wch, wsl, wv)
-                }
-                QGX_STAMP()
-                // ---- K loop over the TPS taps of this slice, fragments requested one tap ahead
-                const char *wl = wlds0 + cur_w * WSB + wofs;
-                const int tap0 = sl * TPS;
-                int ky = tap0 / KS, kx = tap0 - ky * KS;
-                int aoff[MT];
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) {
-                    int col = px[mt] + kx - P;
-                    col = col < 0 ? col + N : (col >= N ? col - N : col);
-                    aoff[mt] = QGX_HP_ADDR((py[mt] + ky) * N + col);
-                }
-                h8 Pn[MT][2], Wn[NT][2];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        Wn[nt][j] = *reinterpret_cast<const h8 *>(wl + (j * 2 * COUT + nt * 32) * 16);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) Pn[mt][j] = *reinterpret_cast<const h8 *>(lds0 + QGX_HP_FRAG(aoff[mt], j));
-                for (int tl = 0; tl < TPS; ++tl) {
-                    const bool last_tap = tl == TPS - 1;
-                    int nkx = kx + 1, nky = ky;
-                    if (nkx == KS) { nkx = 0; ++nky; }
-                    int aoff_n[MT];
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        int col = px[mt] + nkx - P;
-                        col = col < 0 ? col + N : (col >= N ? col - N : col);
-                        aoff_n[mt] = last_tap ? aoff[mt] : QGX_HP_ADDR((py[mt] + nky) * N + col);
-                    }
-                    const char *wl_n = last_tap ? wl : wl + TAPB;
-                    h8 Pc[MT][2], Wc[NT][2];
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) { Pc[mt][0] = Pn[mt][0]; Pc[mt][1] = Pn[mt][1]; }
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) { Wc[nt][0] = Wn[nt][0]; Wc[nt][1] = Wn[nt][1]; }
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-                            Wn[nt][j] = *reinterpret_cast<const h8 *>(wl_n + (j * 2 * COUT + nt * 32) * 16);
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) Pn[mt][j] = *reinterpret_cast<const h8 *>(lds0 + QGX_HP_FRAG(aoff_n[mt], j));
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) {
-                            if constexpr (NS == 1) {
-                                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[nt][0], Pc[mt][0], acc[mt][nt], 0, 0, 0);
-                                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[nt][1], Pc[mt][1], acc[mt][nt], 0, 0, 0);
-                            } else {
-                                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[nt][1], Pc[mt][0], acc[mt][nt], 0, 0, 0);
-                                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[nt][0], Pc[mt][1], acc[mt][nt], 0, 0, 0);
-                                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[nt][0], Pc[mt][0], acc[mt][nt], 0, 0, 0);
-                            }
-                        }
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) aoff[mt] = aoff_n[mt];
-                    wl = wl_n;
-                    kx = nkx; ky = nky;
-                }
-
-                QGX_STAMP()
-                // ---- retire the prefetches
-                if (sl == NSL - 1) {
-                    __syncthreads();                     // every wave is done with this chunk's patch
-                    if (have_next_chunk) QGX_HP_STORE(pv)
-                }
-                if (!last_stage) QGX_HW_STORE(wlds0 + (cur_w ^ 1) * WSB, wv)
-                __syncthreads();
-                QGX_STAMP()
-                cur_w ^= 1;
-                if (sl == NSL - 1 && ch == NCH - 1) {
-                    // ---- epilogue of this tile, AFTER the prefetches were retired: its stores then drain during the
-                    // next stage instead of being waited for (vmcnt counts loads and stores together, in order)
-                    const int tile_g = blockIdx.x + ti * gridDim.x;
-                    const int b = tile_g / tiles_per_img;
-                    const int y0 = (tile_g - b * tiles_per_img) * R;
-                    char *ob = reinterpret_cast<char *>(a.out) + ((size_t)b * N * N + (size_t)y0 * N) * OPIXB;
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        const int tile = wave + NW * mt;
-                        if (tile >= ntiles) continue;
-                        char *pix = ob + (size_t)(tile * 32 + li) * OPIXB;
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt)
-                            store_tile_t<NS, OUTF32>(acc[mt][nt], nt * 32, h, pix, ep, ep + COUT, ep + 2 * COUT, a.unscale, a.ascale, a.range, a.range_bit);
-                    }
-                }
-            }
-        }
-    }
-#undef QGX_HP_LOAD
-#undef QGX_HP_STORE
-#undef QGX_HW_LOAD
-#undef QGX_HW_STORE
-#undef QGX_HP_ADDR
-#undef QGX_HP_FRAG
-}
-
-#endif  // QGX_AB
 
 // ---- f16x3 hidden layers, compile-time grid size: 4 waves x 2 workgroups per CU ---------------------------
-// Same arithmetic and data layouts as k_convh<NS = 2>, built so that TWO workgroups share a CU and run
+// The f16x3 arithmetic and data layouts above, built so that TWO workgroups share a CU and run
 // out of phase (one's barriers, LDS staging and operand latency under the other's MFMAs): that needs
 // <= 256 registers per wave, which the generic kernel misses because hipcc hoists its 25 x MT
 // loop-invariant per-lane tap addresses into registers.  Here the LDS patch carries a wrapped halo of
@@ -730,7 +437,7 @@ __global__ __launch_bounds__(NW * 64, TWO ? 2 : 1) void k_convh2(ConvHArgs a, in
                             char *pix = ob + (size_t)((p / TW) * N + p % TW) * OPIXB;
 #pragma unroll
                             for (int nt = 0; nt < NT; ++nt)
-                                store_tile_t<2, OUTF32>(acc[mt][nt], nt * 32, h, pix, ep, ep + COUT, ep + 2 * COUT, a.unscale, a.ascale, a.range, a.range_bit);
+                                store_tile_t<OUTF32>(acc[mt][nt], nt * 32, h, pix, ep, ep + COUT, ep + 2 * COUT, a.unscale, a.ascale, a.range, a.range_bit);
                         }
                     }
                 }
@@ -814,7 +521,7 @@ struct ConvHFirstArgs {
     unsigned range_bit;
 };
 
-template <int NIN, int MT, int PPT, int NW = 4, bool PLANAR = false>
+template <int NIN, int MT, int PPT, int NW = 4>
 __global__ __launch_bounds__(NW * 64) void k_convh_first(ConvHFirstArgs a, int total_tiles) {
     constexpr int NTHR = NW * 64;
     constexpr int KS = 5, P = 2, T = 25, COUT = 128;
@@ -906,13 +613,8 @@ __global__ __launch_bounds__(NW * 64) void k_convh_first(ConvHFirstArgs a, int t
         const int mt = e >> 1, nt = e & 1;
         const int tile = wave + NW * mt;
         if (tile >= ntiles) return;
-        if constexpr (PLANAR) {
-            store_tile_planar(ac[mt][nt], half_of * 64 + nt * 32 + li, h, obase, tile * 32, N, COUT, ep, ep + COUT, ep + 2 * COUT,
-                              a.unscale, a.ascale, a.range, a.range_bit, a.guard_mul);
-            return;
-        }
         char *pix = obase + (size_t)(tile * 32 + li) * (COUT * 4);
-        store_tile_t<2, false>(ac[mt][nt], half_of * 64 + nt * 32, h, pix, ep, ep + COUT, ep + 2 * COUT, a.unscale, a.ascale, a.range, a.range_bit, a.guard_mul);
+        store_tile_t<false>(ac[mt][nt], half_of * 64 + nt * 32, h, pix, ep, ep + COUT, ep + 2 * COUT, a.unscale, a.ascale, a.range, a.range_bit, a.guard_mul);
     };
     for (int ti = 0; ti < n_my; ++ti) {
         const bool have_next = ti + 1 < n_my;
@@ -971,15 +673,9 @@ __global__ __launch_bounds__(NW * 64) void k_convh_first(ConvHFirstArgs a, int t
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                     for (int nt = 0; nt < 2; ++nt) {
-                        if constexpr (PLANAR) {     // operands exchanged: the tile comes out transposed, lane = output channel
-                            acc[half][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ph[mt], W[nt][1], acc[half][mt][nt], 0, 0, 0);
-                            acc[half][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Pl[mt], W[nt][0], acc[half][mt][nt], 0, 0, 0);
-                            acc[half][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ph[mt], W[nt][0], acc[half][mt][nt], 0, 0, 0);
-                        } else {
-                            acc[half][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W[nt][1], Ph[mt], acc[half][mt][nt], 0, 0, 0);
-                            acc[half][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W[nt][0], Pl[mt], acc[half][mt][nt], 0, 0, 0);
-                            acc[half][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W[nt][0], Ph[mt], acc[half][mt][nt], 0, 0, 0);
-                        }
+                        acc[half][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W[nt][1], Ph[mt], acc[half][mt][nt], 0, 0, 0);
+                        acc[half][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W[nt][0], Pl[mt], acc[half][mt][nt], 0, 0, 0);
+                        acc[half][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W[nt][0], Ph[mt], acc[half][mt][nt], 0, 0, 0);
                     }
                 if (have_prev) {
 #pragma unroll
@@ -1004,173 +700,3 @@ __global__ __launch_bounds__(NW * 64) void k_convh_first(ConvHFirstArgs a, int t
 #undef QGX_F_LOAD
 #undef QGX_F_STORE
 }
-
-#ifdef QGX_AB   // resident-weight 3x3 kernel: measured no faster than k_convh2, A/B builds only
-// ---- 3x3 hidden layers with RESIDENT weights (f16x3) ------------------------------------------------------
-// The 3x3 layers are small (<= 73.7 KB of hi/lo weights), so a persistent 8-wave workgroup keeps the
-// whole weight set in LDS and stages only the input patch: 32 channels (128 bytes: 4 octets x hi/lo) per
-// pixel and chunk, unit index XOR-swizzled by bits 1..3 of the pixel index (conflict-free
-// ds_read_b128 at a 128-byte pixel stride).  The next chunk's / tile's patch is fetched into registers
-// at the start of a chunk, i.e. a whole 32-channel chunk (~3.5 us) ahead of its use, which is what the
-// 16-channel kernel above lacked on these memory-latency-bound layers; two barriers per chunk.
-template <int CIN, int COUT, int MT, int PPT, bool OUTF32>
-__global__ __launch_bounds__(512) void k_convh_res(ConvHArgs a, int total_tiles) {
-    constexpr int NW = 8, NTHR = 512, KS = 3, P = 1, T = 9;
-    constexpr int NT = COUT / 32;
-    constexpr int NCH = CIN / 32;
-    constexpr int PIXB = CIN * 4;
-    constexpr int OPIXB = OUTF32 ? COUT * 4 : COUT * 4;
-    constexpr int WBYTES = (CIN / 16) * T * 4 * COUT * 16;
-    const int N = a.N, R = a.R;
-    const int PR = R + KS - 1;
-    const int PU = PR * N * 8;                          // 16-byte units of one patch chunk
-    char *const wl0 = conv_smem;
-    char *const lds0 = conv_smem + WBYTES;
-    float *const ep = reinterpret_cast<float *>(lds0 + PR * N * 128);   // bias | scale | shift
-    const char *const inb = reinterpret_cast<const char *>(a.in);
-    const int tiles_per_img = N / R;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 31, h = lane >> 5;
-    const int n_my = blockIdx.x < (unsigned)total_tiles ? (total_tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
-    const int ntiles = R * N / 32;
-    if (n_my == 0) return;
-    int stamp_i = 0;
-    (void)stamp_i;
-    QGX_STAMP()
-
-#define QGX_RP_LOAD(TI, CH, V)                                                                              \
-    {                                                                                                       \
-        const int tile_ = blockIdx.x + (TI) * gridDim.x;                                                    \
-        const int b_ = tile_ / tiles_per_img;                                                               \
-        const int y0_ = (tile_ - b_ * tiles_per_img) * R;                                                   \
-        _Pragma("unroll") for (int u = 0; u < PPT; ++u) {                                                   \
-            int it_ = u * NTHR + threadIdx.x;                                                                \
-            it_ = it_ < PU ? it_ : PU - 1;                                                                  \
-            const int un_ = it_ & 7, pl_ = it_ >> 3;                                                        \
-            const int pr_ = pl_ / N, x_ = pl_ - pr_ * N;                                                    \
-            int gy_ = y0_ - P + pr_;                                                                        \
-            gy_ = gy_ < 0 ? gy_ + N : (gy_ >= N ? gy_ - N : gy_);                                           \
-            V[u] = *reinterpret_cast<const f32x4 *>(                                                        \
-                inb + (((size_t)b_ * N + gy_) * N + x_) * PIXB + (CH) * 128 + un_ * 16);                    \
-        }                                                                                                   \
-    }
-#define QGX_RP_STORE(V)                                                                                     \
-    {                                                                                                       \
-        _Pragma("unroll") for (int u = 0; u < PPT; ++u) {                                                   \
-            const int it_ = u * NTHR + threadIdx.x;                                                          \
-            if (it_ < PU)                                                                                   \
-                *reinterpret_cast<f32x4 *>(lds0 + (it_ >> 3) * 128 + (((it_ & 7) ^ ((it_ >> 4) & 7)) * 16)) = V[u]; \
-        }                                                                                                   \
-    }
-
-    for (int i = threadIdx.x; i < 3 * COUT; i += NTHR)
-        ep[i] = i < COUT ? a.bias[i] : (i < 2 * COUT ? a.scale[i - COUT] : a.shift[i - 2 * COUT]);
-    // ---- prologue: the whole weight set (once) and the first patch chunk
-    {
-        f32x4 pv[PPT], wtmp[(WBYTES / 16 + NTHR - 1) / NTHR];
-        QGX_RP_LOAD(0, 0, pv)
-        QGX_BULK_LOAD(wtmp, a.w, WBYTES / 16, NTHR)
-        QGX_RP_STORE(pv)
-        QGX_BULK_STORE(wtmp, wl0, WBYTES / 16, NTHR)
-    }
-    __syncthreads();
-    QGX_STAMP()
-
-    int py[MT], px[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        int tile = wave + NW * mt;
-        if (tile >= ntiles) tile = wave % ntiles;
-        const int p = tile * 32 + li;
-        py[mt] = p / N;
-        px[mt] = p - py[mt] * N;
-    }
-    const char *const wlane = wl0 + (h * COUT + li) * 16;
-    f32x16 acc[MT][NT];
-    for (int ti = 0; ti < n_my; ++ti) {
-        for (int ch = 0; ch < NCH; ++ch) {
-            if (ch == 0) {
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
-            }
-            const int nch = ch + 1 < NCH ? ch + 1 : 0;
-            const int nti = ch + 1 < NCH ? ti : ti + 1;
-            const bool have_next = nti < n_my;
-            f32x4 pv[PPT];
-            QGX_RP_LOAD(have_next ? nti : ti, have_next ? nch : ch, pv)
-
-            // ---- K loop: 9 taps x 2 K=16 steps (octet pairs 0-1 / 2-3 of the chunk), one step ahead
-            // fragment address of step s = 2 tap + t: hi at base[tap] ^ (t * 64), lo at hi ^ 16
-            h8 Pn[MT][2], Wn[NT][2];
-#define QGX_RP_FRAGS(S)                                                                                     \
-            {                                                                                               \
-                constexpr int tap_ = (S) >> 1, t_ = (S) & 1, ky_ = tap_ / 3, kx_ = tap_ - 3 * ky_;          \
-                _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) {                                         \
-                    int col = px[mt] + kx_ - P;                                                             \
-                    col = col < 0 ? col + N : (col >= N ? col - N : col);                                   \
-                    const int pl_ = (py[mt] + ky_) * N + col;                                               \
-                    const int hi_ = pl_ * 128 + ((((2 * h) ^ ((pl_ >> 1) & 7)) * 16) ^ (t_ * 64));          \
-                    Pn[mt][0] = *reinterpret_cast<const h8 *>(lds0 + hi_);                                  \
-                    Pn[mt][1] = *reinterpret_cast<const h8 *>(lds0 + (hi_ ^ 16));                           \
-                }                                                                                           \
-                _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                           \
-                    _Pragma("unroll") for (int part = 0; part < 2; ++part)                                  \
-                        Wn[nt][part] = *reinterpret_cast<const h8 *>(                                       \
-                            wlane + ((size_t)(((ch * 2 + t_) * T + tap_) * 4 + part * 2) * COUT + nt * 32) * 16); \
-            }
-            QGX_STAMP()
-            QGX_RP_FRAGS(0)
-#define QGX_RP_STEP(S)                                                                                      \
-            {                                                                                               \
-                h8 Pc[MT][2], Wc[NT][2];                                                                    \
-                _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) { Pc[mt][0] = Pn[mt][0]; Pc[mt][1] = Pn[mt][1]; } \
-                _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) { Wc[nt][0] = Wn[nt][0]; Wc[nt][1] = Wn[nt][1]; } \
-                if constexpr ((S) + 1 < 2 * T) QGX_RP_FRAGS((S) + 1)                                        \
-                __builtin_amdgcn_sched_barrier(0);                                                          \
-                _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                           \
-                    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                     \
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[nt][1], Pc[mt][0], acc[mt][nt], 0, 0, 0); \
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[nt][0], Pc[mt][1], acc[mt][nt], 0, 0, 0); \
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[nt][0], Pc[mt][0], acc[mt][nt], 0, 0, 0); \
-                    }                                                                                       \
-            }
-            QGX_RP_STEP(0) QGX_RP_STEP(1) QGX_RP_STEP(2) QGX_RP_STEP(3) QGX_RP_STEP(4) QGX_RP_STEP(5)
-            QGX_RP_STEP(6) QGX_RP_STEP(7) QGX_RP_STEP(8) QGX_RP_STEP(9) QGX_RP_STEP(10) QGX_RP_STEP(11)
-            QGX_RP_STEP(12) QGX_RP_STEP(13) QGX_RP_STEP(14) QGX_RP_STEP(15) QGX_RP_STEP(16) QGX_RP_STEP(17)
-#undef QGX_RP_STEP
-#undef QGX_RP_FRAGS
-            QGX_STAMP()
-
-            QGX_STAMP()
-            __syncthreads();                             // every wave is done with this chunk's patch
-            QGX_STAMP()
-            if (have_next) QGX_RP_STORE(pv)
-            QGX_STAMP()
-            __syncthreads();
-            // epilogue AFTER the prefetch was retired: its stores drain during the next chunk's K loop
-            if (ch == NCH - 1) {
-                const int tile_g = blockIdx.x + ti * gridDim.x;
-                const int b = tile_g / tiles_per_img;
-                const int y0 = (tile_g - b * tiles_per_img) * R;
-                char *ob = reinterpret_cast<char *>(a.out) + ((size_t)b * N * N + (size_t)y0 * N) * OPIXB;
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) {
-                    const int tile = wave + NW * mt;
-                    if (tile >= ntiles) continue;
-                    char *pix = ob + (size_t)(tile * 32 + li) * OPIXB;
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-                        store_tile_t<2, OUTF32>(acc[mt][nt], nt * 32, h, pix, ep, ep + COUT, ep + 2 * COUT, a.unscale, a.ascale, a.range, a.range_bit);
-                }
-            }
-            QGX_STAMP()
-        }
-    }
-#undef QGX_RP_LOAD
-#undef QGX_RP_STORE
-}
-#endif  // QGX_AB

@@ -32,7 +32,7 @@ struct ConvPairArgs {
     unsigned long long *stamps;   // diagnostic builds (-DQGX_STAMPS) only
 };
 
-template <int CINA, int NN, bool LAST, bool BOUTF32, bool LP = (CINA == 32), int RR = 8>
+template <int CINA, int NN, bool LAST, bool BOUTF32, int RR = 8>
 __global__ __launch_bounds__(512) void k_convh_pair(ConvPairArgs a, int total_tiles) {
     constexpr int NW = 8, NTHR = 512, N = NN, R = RR, T = 9;
     constexpr int NCA = CINA / 16;
@@ -130,10 +130,10 @@ __global__ __launch_bounds__(512) void k_convh_pair(ConvPairArgs a, int total_ti
         epA[i] = i < 32 ? a.biasA[i] : (i < 64 ? a.scaleA[i - 32] : a.shiftA[i - 64]);
         epB[i] = i < 32 ? a.biasB[i] : (i < 64 ? a.scaleB[i - 32] : a.shiftB[i - 64]);
     }
-    // LP (two input chunks = the two 64-byte halves of a pixel's 128-byte line): fetching the halves in different
+    // LP (CINA = 32: two input chunks = the two 64-byte halves of a pixel's 128-byte line): fetching the halves in different
     // chunk iterations brought every line from HBM twice (FETCH_SIZE 178 MB for a 100 MB halo-amplified input), so
     // both halves of the NEXT tile are loaded together during phase B and the second waits in registers for its turn
-    static_assert(!LP || NCA == 2, "line-pair prefetch: two chunks");
+    constexpr bool LP = CINA == 32;
     f32x4 pvB[LP ? PPT : 1];
     {
         f32x4 pv[PPT], wv[WPT], wtmp[(WB_BYTES / 16 + NTHR - 1) / NTHR];
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(512) void k_convh_pair(ConvPairArgs a, int total_ti
                 } else {
                     constexpr int OPIXB = 32 * 4;
                     char *pix = reinterpret_cast<char *>(a.out) + ((size_t)b * N * N + (size_t)y0 * N + p) * OPIXB;
-                    store_tile_t<2, BOUTF32>(accB[mt], 0, h, pix, epB, epB + 32, epB + 64, a.unscaleB, BOUTF32 ? 1.f : a.ascale, a.range, a.range_bit << 1);
+                    store_tile_t<BOUTF32>(accB[mt], 0, h, pix, epB, epB + 32, epB + 64, a.unscaleB, BOUTF32 ? 1.f : a.ascale, a.range, a.range_bit << 1);
                 }
             }
         }

@@ -72,9 +72,7 @@ __device__ __forceinline__ void wino_bt8(const float (&x)[8][4], int e, float (&
     v[5] = a5 + b5; v[6] = a5 - b5;
 }
 
-// EXP (A/B library, timing experiments only — the results are wrong; 6 no output stores, 7 = 1 + 2, 8 = 2 + 6): 1 no input transform, 2 no MFMAs, 4 weights loaded
-// once, 5 no raw-patch copy
-template <int NN, int TW, int R, int EXP = 0, bool PL = false>
+template <int NN, int TW, int R>
 __global__ __launch_bounds__(512) void k_convw(ConvWArgs a, int total_tiles) {
     constexpr int N = NN, CIN = 128, COUT = 64, NCH = CIN / 16, KY = 5;
     constexpr int NQT = TW / 4;                     // quads per tile row
@@ -90,29 +88,16 @@ __global__ __launch_bounds__(512) void k_convw(ConvWArgs a, int total_tiles) {
     // consecutive pairs without padding); the RAW patch of the NEXT chunk, transposed to [row][unit][column slot] with
     // slot = SQ (xl & 3) + (xl >> 2) for the local column xl = x - (x0 - 2) (full-width tiles: xl = x), so that the
     // transform's reads of consecutive quads are consecutive 16-byte slots
-    // PL (A/B library only — measured, not faster overall: conv.hip::wino_planar; planar input, conv_half.hpp::store_tile_planar: [b][y][c][hi | lo][x] f16): the input transform runs on the
-    // matrix cores.  BT contracts over PIXELS, so with pixel-contiguous rows the raw patch feeds an MFMA directly:
-    // A = activations, 32 rows = (2 patch rows) x (16 channels), K = 32 pixels of the window 16 Q - 8 ... 16 Q + 23 around the
-    // quad group Q (two K = 16 steps, hi and lo: 4 MFMAs), B = the constant banded matrix BT shifted per quad
-    // (32 columns = 4 quads x 8 positions; every entry exact in f16).  The accumulator tile comes out with lane =
-    // (position, quad), register = channel: one 64-byte record of the transformed patch per lane after the hi / lo split.
-    // Raw patch in LDS: [row][channel][hi | lo][XO octets of 8 pixels] (window x0 - 8 ... x0 + TW + 7, or the whole wrapped
-    // row), RS bytes per (row, channel) and RYS per row chosen so that the A-fragment reads are bank-conflict-free.
-    constexpr int XO = FULLW ? N / 8 : (TW + 16) / 8;
-    constexpr int RS = 2 * XO * 16 + 16, RYS = 16 * RS + 128;
-    static_assert(!PL || !FULLW || (XO & (XO - 1)) == 0, "wrapped octet index");
     constexpr int REC = 64;
-    constexpr int VPS = PR * NQT * REC;             // bytes between positions (PL: a record's unit index is XORed with p & 3 as well,
-                                                    // so that the transform's record writes of four positions spread over the banks)
+    constexpr int VPS = PR * NQT * REC;             // bytes between positions
     constexpr int VT_BYTES = 8 * VPS;
     constexpr int MREC = COUT * 4 + 16;             // output staging: bytes per (p, pair) record
     constexpr int A_BYTES = VT_BYTES > 8 * 32 * MREC ? VT_BYTES : 8 * 32 * MREC;
-    constexpr int RAW_BYTES = PL ? PR * RYS : PR * 4 * PW * 16;
+    constexpr int RAW_BYTES = PR * 4 * PW * 16;
     constexpr int NITEM = PR * NQT * 2;             // transform items (row, quad, octet) per chunk
-    constexpr int NUNIT = PL ? PR * 32 * XO : PR * PW * 4;   // 16-byte units of a chunk's raw patch
+    constexpr int NUNIT = PR * PW * 4;               // 16-byte units of a chunk's raw patch
     constexpr int UPT = (NUNIT + 511) / 512;        // ... per thread
     static_assert(32 % NQT == 0 && R % RM == 0 && N % TW == 0 && N % R == 0 && NITEM <= 512 && UPT <= 8, "tile shape");
-    static_assert(!PL || (PR % 2 == 0 && NQT % 4 == 0 && (PR / 2) * (NQT / 4) >= 8), "MFMA input transform: row pairs x quad groups");
     char *const vt = conv_smem;
     char *const rawb = conv_smem + A_BYTES;
     float *const ep = reinterpret_cast<float *>(conv_smem + A_BYTES + RAW_BYTES);         // bias | scale | shift | AT'[4][8]
@@ -132,14 +117,13 @@ __global__ __launch_bounds__(512) void k_convw(ConvWArgs a, int total_tiles) {
     constexpr int NHALF = 2 * NITEM;
     // B fragment of this lane: pair li = (row li / NQT, quad li % NQT) of an M-tile, octet h (units 2h | 2h + 1, swizzled)
     const int fq = li % NQT, fr = li / NQT;
-    const int psw = PL ? (p & 3) : 0;
-    const int fbase = p * VPS + (fr * NQT + fq) * REC + (((2 * h) ^ psw ^ (((fr * NQT + fq) >> 2) & 3)) * 16);
+    const int fbase = p * VPS + (fr * NQT + fq) * REC + (((2 * h) ^ (((fr * NQT + fq) >> 2) & 3)) * 16);
     auto frag = [&](int row_off) -> int {        // byte offset of the hi unit of patch row fr + row_off; the lo unit is ^ 16
         if constexpr (NQT == 16) return fbase + row_off * NQT * REC;                         // swizzle: the quad alone
         else if constexpr (NQT == 8) return (fbase + row_off * NQT * REC) ^ ((row_off & 1) * 32);   // ... and the row's parity
         else {
             const int prow = fr + row_off;
-            return p * VPS + (prow * NQT + fq) * REC + (((2 * h) ^ psw ^ (((prow * NQT + fq) >> 2) & 3)) * 16);
+            return p * VPS + (prow * NQT + fq) * REC + (((2 * h) ^ (((prow * NQT + fq) >> 2) & 3)) * 16);
         }
     };
     // A-fragment base: [p][part][h][cout][8] within a (chunk, ky) slice of 8 * 4 * 64 * 16 bytes
@@ -155,32 +139,18 @@ __global__ __launch_bounds__(512) void k_convw(ConvWArgs a, int total_tiles) {
         int u_ = (J) * 512 + (int)threadIdx.x;                                                                  \
         u_ = u_ < NUNIT ? u_ : NUNIT - 1;                                                                       \
         const int b_ = (TILE) / tiles_per_img, tr_ = (TILE) - b_ * tiles_per_img;                               \
-        if constexpr (PL) {                                                                                     \
-            /* unit = (row, channel, hi | lo, octet): consecutive lanes read consecutive 16-byte octets of a 2 N-byte plane row */ \
-            const int oc_ = u_ % XO, hl_ = (u_ / XO) & 1, c_ = (u_ / (2 * XO)) & 15, r_ = u_ / (32 * XO);         \
-            int gy_ = (tr_ / XT) * R - 2 + r_, go_ = FULLW ? oc_ : (tr_ % XT) * (TW / 8) - 1 + oc_;             \
-            gy_ = gy_ < 0 ? gy_ + N : (gy_ >= N ? gy_ - N : gy_);                                               \
-            go_ = go_ < 0 ? go_ + N / 8 : (go_ >= N / 8 ? go_ - N / 8 : go_);                                   \
-            DST = *reinterpret_cast<const f32x4 *>(inb + (((((size_t)b_ * N + gy_) * CIN + (CH) * 16 + c_) * 2 + hl_) * N + go_ * 8) * 2); \
-        } else {                                                                                                \
-            const int un_ = u_ & 3, xl_ = (u_ >> 2) % PW, r_ = u_ / (4 * PW);                                   \
-            int gy_ = (tr_ / XT) * R - 2 + r_, gx_ = FULLW ? xl_ : (tr_ % XT) * TW - 2 + xl_;                   \
-            gy_ = gy_ < 0 ? gy_ + N : (gy_ >= N ? gy_ - N : gy_);                                               \
-            gx_ = gx_ < 0 ? gx_ + N : (gx_ >= N ? gx_ - N : gx_);                                               \
-            DST = *reinterpret_cast<const f32x4 *>(inb + (((size_t)b_ * N + gy_) * N + gx_) * PIXB + (CH) * 64 + un_ * 16); \
-        }                                                                                                       \
+        const int un_ = u_ & 3, xl_ = (u_ >> 2) % PW, r_ = u_ / (4 * PW);                                       \
+        int gy_ = (tr_ / XT) * R - 2 + r_, gx_ = FULLW ? xl_ : (tr_ % XT) * TW - 2 + xl_;                       \
+        gy_ = gy_ < 0 ? gy_ + N : (gy_ >= N ? gy_ - N : gy_);                                                   \
+        gx_ = gx_ < 0 ? gx_ + N : (gx_ >= N ? gx_ - N : gx_);                                                   \
+        DST = *reinterpret_cast<const f32x4 *>(inb + (((size_t)b_ * N + gy_) * N + gx_) * PIXB + (CH) * 64 + un_ * 16); \
     }
 #define QGX_RAW_STORE(J, SRC)                                                                                   \
     {                                                                                                           \
         const int u_ = (J) * 512 + (int)threadIdx.x;                                                            \
         if (u_ < NUNIT) {                                                                                       \
-            if constexpr (PL) {                                                                                 \
-                const int oc_ = u_ % XO, hl_ = (u_ / XO) & 1, c_ = (u_ / (2 * XO)) & 15, r_ = u_ / (32 * XO);     \
-                *reinterpret_cast<f32x4 *>(rawb + r_ * RYS + c_ * RS + (hl_ * XO + oc_) * 16) = SRC;            \
-            } else {                                                                                            \
-                const int un_ = u_ & 3, xl_ = (u_ >> 2) % PW, r_ = u_ / (4 * PW);                               \
-                *reinterpret_cast<f32x4 *>(rawb + (((r_ * 4 + un_) * PW) + (xl_ & 3) * SQ + (xl_ >> 2)) * 16) = SRC;   \
-            }                                                                                                   \
+            const int un_ = u_ & 3, xl_ = (u_ >> 2) % PW, r_ = u_ / (4 * PW);                                   \
+            *reinterpret_cast<f32x4 *>(rawb + (((r_ * 4 + un_) * PW) + (xl_ & 3) * SQ + (xl_ >> 2)) * 16) = SRC;       \
         }                                                                                                       \
     }
 
@@ -191,23 +161,6 @@ __global__ __launch_bounds__(512) void k_convw(ConvWArgs a, int total_tiles) {
         _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                          \
             Wn[nt][j] = *reinterpret_cast<const h8 *>(wb + (size_t)(S) * WSLICE + wofs + j * 2 * COUT * 16 + nt * 32 * 16);
     QGX_W_LOAD(0)
-    // PL: the B operand of the transform, column n = li = (position li >> 2, quad-in-group li & 3), K index k = 16 ks + 8 h + e
-    // = pixel 16 Q - 8 + k; quad j reads the pixels 16 Q + 4 j - 2 ... + 5, i.e. d = k - 6 - 4 j in 0..7
-    h8 Bt[2];
-    if constexpr (PL) {
-        constexpr float BT8[8][8] = {{-1.f, 0.f, 5.25f, 0.f, -5.25f, 0.f, 1.f, 0.f},   {0.f, 1.f, 1.f, -4.25f, -4.25f, 1.f, 1.f, 0.f},
-                                     {0.f, -1.f, 1.f, 4.25f, -4.25f, -1.f, 1.f, 0.f},  {0.f, .5f, .25f, -2.5f, -1.25f, 2.f, 1.f, 0.f},
-                                     {0.f, -.5f, .25f, 2.5f, -1.25f, -2.f, 1.f, 0.f},  {0.f, 2.f, 4.f, -2.5f, -5.f, .5f, 1.f, 0.f},
-                                     {0.f, -2.f, 4.f, 2.5f, -5.f, -.5f, 1.f, 0.f},     {0.f, -1.f, 0.f, 5.25f, 0.f, -5.25f, 0.f, 1.f}};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int d = 16 * ks + 8 * h + e - 6 - 4 * (li & 3);
-                const float bv = d >= 0 && d < 8 ? BT8[li >> 2][d & 7] : 0.f;
-                Bt[ks][e] = (_Float16)bv;
-            }
-    }
     {   // prologue: the first tile's first chunk, synchronously
         f32x4 r0[UPT];
 #pragma unroll
@@ -223,64 +176,10 @@ __global__ __launch_bounds__(512) void k_convw(ConvWArgs a, int total_tiles) {
         for (int ch = 0; ch < NCH; ++ch) {
             // ---- input transform of this chunk: raw patch (LDS) -> float32 BT -> hi / lo -> transformed patch (LDS) ----
             __syncthreads();        // the raw patch has landed; every wave is done reading the previous transformed patch
-            if constexpr (PL) {
-                constexpr int NQG = NQT / 4, NTT = (PR / 2) * NQG;                      // (row pair, quad group) tiles of 32 x 32
-                if (EXP != 1 && EXP != 7) {
-                    const int ayl = (li >> 2) & 1, ac = (li & 3) + 4 * (li >> 3);         // A row li = (patch row parity, channel)
-                    // one tile at a time (the 128 accumulator registers of the tile stay live through this phase), the next
-                    // tile's four fragments in flight under this tile's MFMAs and hi / lo split.  (Software-pipelining the
-                    // chains of two tiles needs 16 more registers: 324 bytes of scratch at 64 x 64.)
-                    h8 An[4];
-#define QGX_TA_LOAD(TT)                                                                                         \
-                    {                                                                                           \
-                        const int rp_ = (TT) / NQG, Q_ = (TT) - rp_ * NQG;                                      \
-                        const char *rowp_ = rawb + (2 * rp_ + ayl) * RYS + ac * RS;                             \
-                        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                      \
-                            const int oc_ = FULLW ? ((2 * Q_ - 1 + 2 * ks + h) & (XO - 1)) : 2 * Q_ + 2 * ks + h; \
-                            An[ks] = *reinterpret_cast<const h8 *>(rowp_ + oc_ * 16);                           \
-                            An[2 + ks] = *reinterpret_cast<const h8 *>(rowp_ + (XO + oc_) * 16);                \
-                        }                                                                                       \
-                    }
-                    QGX_TA_LOAD(p)
-#pragma nounroll
-                    for (int tt = p; tt < NTT; tt += 8) {                                  // wave-uniform
-                        const h8 A0 = An[0], A1 = An[1], A2 = An[2], A3 = An[3];
-                        if (tt + 8 < NTT) QGX_TA_LOAD(tt + 8)
-                        // two independent chains (hi, lo) of two MFMAs instead of one of four
-                        f32x16 tv, tl;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) { tv[r] = 0.f; tl[r] = 0.f; }
-                        tv = __builtin_amdgcn_mfma_f32_32x32x16_f16(A0, Bt[0], tv, 0, 0, 0);
-                        tl = __builtin_amdgcn_mfma_f32_32x32x16_f16(A2, Bt[0], tl, 0, 0, 0);
-                        tv = __builtin_amdgcn_mfma_f32_32x32x16_f16(A1, Bt[1], tv, 0, 0, 0);
-                        tl = __builtin_amdgcn_mfma_f32_32x32x16_f16(A3, Bt[1], tl, 0, 0, 0);
-                        // lane (li, h): position li >> 2, quad 4 Q + (li & 3), patch row 2 rp + h; register r = channel r
-                        const int rp = tt / NQG, Q = tt - rp * NQG;
-                        const int pair = (2 * rp + h) * NQT + 4 * Q + (li & 3);
-                        char *dst = vt + (li >> 2) * VPS + pair * REC;
-                        const int sw = ((pair >> 2) ^ (li >> 2)) & 3;
-#pragma unroll
-                        for (int o = 0; o < 2; ++o) {
-                            unsigned hw[4], lw[4];
-#pragma unroll
-                            for (int e2 = 0; e2 < 4; ++e2) {
-                                const float v0 = tv[8 * o + 2 * e2] + tl[8 * o + 2 * e2], v1 = tv[8 * o + 2 * e2 + 1] + tl[8 * o + 2 * e2 + 1];
-                                hw[e2] = pack_h2(v0, v1);
-                                lw[e2] = pack_h2(mix_rest<0>(hw[e2], v0), mix_rest<1>(hw[e2], v1));
-                            }
-                            const int uh = ((2 * o) ^ sw) * 16;
-                            const u32x4 oh = {hw[0], hw[1], hw[2], hw[3]}, ol = {lw[0], lw[1], lw[2], lw[3]};
-                            *reinterpret_cast<u32x4 *>(dst + uh) = oh;
-                            *reinterpret_cast<u32x4 *>(dst + (uh ^ 16)) = ol;
-                        }
-                    }
-#undef QGX_TA_LOAD
-                }
-            } else {
 #pragma nounroll
             for (int rep = 0; rep < (NHALF + 511) / 512; ++rep) {
                 const int hi_ = rep * 512 + (int)threadIdx.x;
-                if (hi_ < NHALF && EXP != 1 && EXP != 7) {
+                if (hi_ < NHALF) {
                     const int it_t = hi_ % NQT, it_o = (hi_ / NQT) & 1, hf = (hi_ / (2 * NQT)) & 1, it_r = hi_ / (4 * NQT);
                     const int it_sw = ((it_r * NQT + it_t) >> 2) & 3;
                     const char *src = rawb + (size_t)(it_r * 4 + it_o * 2) * PW * 16;
@@ -320,7 +219,6 @@ __global__ __launch_bounds__(512) void k_convw(ConvWArgs a, int total_tiles) {
                     }
                 }
             }
-            }
             __syncthreads();
             if (ch == 0) {
 #pragma unroll
@@ -336,19 +234,19 @@ __global__ __launch_bounds__(512) void k_convw(ConvWArgs a, int total_tiles) {
             f32x4 rw0, rw1;
             // ---- 5 row offsets x MT M-tiles x 2 output-channel tiles x 3 MFMAs ----
 #pragma unroll
-            for (int ky = 0; ky < (EXP == 2 || EXP == 7 || EXP == 8 ? 0 : KY); ++ky) {
+            for (int ky = 0; ky < KY; ++ky) {
                 h8 Wc[2][2];
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) { Wc[nt][0] = Wn[nt][0]; Wc[nt][1] = Wn[nt][1]; }
                 {
                     int s = ch * KY + ky + 1;
                     if (s == NCH * KY) s = 0;                  // the next tile starts over
-                    if (EXP != 4) QGX_W_LOAD(s)
+                    QGX_W_LOAD(s)
                 }
                 // raw copy, two units per thread at a time: loaded in blocks 0, 2 and 4, stored at the END of blocks 1, 3 and 4 —
                 // two blocks (~1.6 us) of flight for four of the six units instead of one for all of them (a store at the
                 // end of the block that issued the load made the wave wait out the HBM latency there); the same 8 registers
-                if (more && EXP != 5) {                        // AFTER the weight loads: vmcnt retires in order
+                if (more) {                        // AFTER the weight loads: vmcnt retires in order
                     if (ky == 0) { QGX_RAW_LOAD(0, n_tile, n_ch, rw0) if (UPT > 1) QGX_RAW_LOAD(1, n_tile, n_ch, rw1) }
                     if (ky == 2 && UPT > 2) { QGX_RAW_LOAD(2, n_tile, n_ch, rw0) if (UPT > 3) QGX_RAW_LOAD(3, n_tile, n_ch, rw1) }
                     if (ky == 4 && UPT > 4) { QGX_RAW_LOAD(4, n_tile, n_ch, rw0) if (UPT > 5) QGX_RAW_LOAD(5, n_tile, n_ch, rw1) }
@@ -375,7 +273,7 @@ __global__ __launch_bounds__(512) void k_convw(ConvWArgs a, int total_tiles) {
                         acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[nt][0], Ph, acc[mt][nt], 0, 0, 0);
                     }
                 }
-                if (more && EXP != 5) {
+                if (more) {
                     if (ky == 1) { QGX_RAW_STORE(0, rw0) if (UPT > 1) QGX_RAW_STORE(1, rw1) }
                     if (ky == 3 && UPT > 2) { QGX_RAW_STORE(2, rw0) if (UPT > 3) QGX_RAW_STORE(3, rw1) }
                     if (ky == 4 && UPT > 4) { QGX_RAW_STORE(4, rw0) if (UPT > 5) QGX_RAW_STORE(5, rw1) }
@@ -449,7 +347,6 @@ __global__ __launch_bounds__(512) void k_convw(ConvWArgs a, int total_tiles) {
                         lw[e2] = pack_h2(mix_rest<0>(hw[e2], v0), mix_rest<1>(hw[e2], v1));
                     }
                     const u32x2 oh = {hw[0], hw[1]}, ol = {lw[0], lw[1]};
-                    if ((EXP == 6 || EXP == 8) && mx >= 0.f) continue;       // experiment: no output stores
                     *reinterpret_cast<u32x2 *>(o + (size_t)j * OPIXB) = oh;
                     *reinterpret_cast<u32x2 *>(o + (size_t)j * OPIXB + 16) = ol;
                 }
@@ -461,10 +358,9 @@ __global__ __launch_bounds__(512) void k_convw(ConvWArgs a, int total_tiles) {
 #undef QGX_RAW_STORE
 }
 
-// LDS bytes of k_convw<NN, TW, R, ., PL>
-constexpr size_t convw_lds_bytes(int NN, int TW, int R, bool PL = false) {
-    const size_t xo = TW == NN ? NN / 8 : (TW + 16) / 8;
+// LDS bytes of k_convw<NN, TW, R>
+constexpr size_t convw_lds_bytes(int NN, int TW, int R) {
     const size_t vtb = (size_t)8 * (R + 4) * (TW / 4) * 64, st = (size_t)8 * 32 * (64 * 4 + 16);
-    const size_t raw = PL ? (size_t)(R + 4) * (16 * (2 * xo * 16 + 16) + 128) : (size_t)(R + 4) * 4 * (TW == NN ? NN : TW + 4) * 16;
+    const size_t raw = (size_t)(R + 4) * 4 * (TW == NN ? NN : TW + 4) * 16;
     return (vtb > st ? vtb : st) + raw + (3 * 64 + 32) * sizeof(float);
 }

@@ -6,8 +6,7 @@
 // SIMD a packed-f32 instruction takes 29 cycles instead of 5 (bench_tools/coissue.hip, MI355X_MICROARCH.md
 // "price of one filler beside MFMAs").  Replaces, for this one layer, the arithmetic of AndrewCNN.forward
 // (cnn_tools.py:125-176, circular padding cnn_tools.py:79-98) exactly as conv_wino.hpp does.
-#include "common.hpp"
-#include <unordered_map>
+#include "generator.hpp"
 
 namespace qgx {
 
@@ -19,20 +18,7 @@ template <int NN, int TW, int R>
 static int launch_convw2_n(const ConvWArgs &a, int total_tiles, hipStream_t st) {
     constexpr size_t lds = convw2_lds_bytes(NN, TW, R);
     static_assert(lds <= 160 * 1024 - 256, "k_convw2: LDS");
-    void (*kern)(ConvWArgs, int) = k_convw2<NN, TW, R>;
-    {   // the dynamic-LDS cap of a kernel is raised once per kernel, device and host thread (conv.hip::ensure_dynamic_lds)
-        static thread_local int seen[16] = {0};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (!seen[dev & 15]) {
-            QGX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            seen[dev & 15] = 1;
-        }
-    }
-    const int grid = total_tiles < 256 ? total_tiles : 256;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a, total_tiles);
-    QGX_HIP(hipGetLastError());
-    return QGX_OK;
+    return launch_conv_kernel(k_convw2<NN, TW, R>, dim3(persistent_grid(256, total_tiles)), dim3(512), lds, st, a, total_tiles);
 }
 
 // the tile shapes this kernel is built for (those where it measured faster than k_convw: bench_tools/wino2_dev.hip)

@@ -3,7 +3,8 @@
 // generator.hip owns the handle: lifecycle, workspaces, the model-independent kernels around a net (input assembly,
 // output scaling, range words, moments), generator_forward's dispatch over the model kinds, and the C ABI that is not
 // AndrewCNN-specific.  conv.hip owns the AndrewCNN engine: kernels, weight packers, launchers, cnn_forward, the range
-// and Winograd calibration, the kernel-selection options (every opt_* field below), the per-layer profiler, and the C
+// and Winograd calibration, the kernel-selection options (every opt_* field below; the variants that lost
+// their measurements are no longer carried: DESIGN.md 3.2), the per-layer profiler, and the C
 // ABI that only makes sense for AndrewCNN nets.  Between them: the functions declared at the end of this file.
 // The U-Net and the ANN are opaque back ends of the same kind (common.hpp: UNet, Ann).
 #pragma once
@@ -19,24 +20,23 @@ struct LayerHost {
     // input; 8 for the planar first layer), and the channels stored per output pixel (cout padded to 8; the last layer: cout)
     int cinp = 0, cstore = 0;
     LastWeights wv_host[2];   // last layer, VALU kernel layout (kernel argument): output channels (0, 1), and (2, 3) of a flux-form net
-    float *wl16 = nullptr, *wl8 = nullptr;   // k_conv3 layout [chunk][tap][g8][h][coutp][4], 16- / 8-channel chunks
+    float *wl16 = nullptr;                   // k_conv3 layout [chunk][tap][g8][h][coutp][4], 16-channel chunks
     float *w = nullptr, *w32 = nullptr, *bias = nullptr, *scale = nullptr, *shift = nullptr;   // w: 16-ch chunks (or planar), w32: 32-ch chunks
-    void *wh[2] = {nullptr, nullptr};        // conv_half.hpp layouts: [0] f16 (NS = 1), [1] f16 hi/lo (NS = 2)
-    float wh_unscale[2] = {1.f, 1.f};        // 2^-s of the power-of-two weight pre-scale
+    void *wh = nullptr;                      // conv_half.hpp layout: f16 hi/lo
+    float wh_unscale = 1.f;                  // 2^-s of the power-of-two weight pre-scale
     // layer 2 with layer 1's BatchNorm folded in (W' = W alpha[c_in], b' = b + sum W beta'[c_in]; exact under circular
     // padding): layer 1 then stores ReLU output, half of which is exactly zero -> a sparser MFMA operand
-    void *whF = nullptr, *wh16F = nullptr; float whF_unscale = 1.f; float *biasF = nullptr;
+    void *whF = nullptr; float whF_unscale = 1.f; float *biasF = nullptr;
     // layer 2 as a 1-D Winograd convolution F(4, 5) along x (conv_wino.hpp): transformed weights, [0] plain, [1] with layer
     // 1's BatchNorm folded in; per-position 2^-s of the power-of-two pre-scale
     void *ww[2] = {nullptr, nullptr};
     float ww_unscale[2][8] = {{1, 1, 1, 1, 1, 1, 1, 1}, {1, 1, 1, 1, 1, 1, 1, 1}};
     float *ones = nullptr, *zeros = nullptr; // layer 1: identity BatchNorm for the folded variant
-    void *wh16 = nullptr;                    // k_convh3 (16x16x32 MFMA): [chunk32][tap][part][octet][cout][8] f16
     void *whf = nullptr;                     // first layer, f16x3: [step][part][h][128][8] f16
     float whf_unscale = 1.f;
     // every device allocation of a layer: a packer that adds a layout adds its pointer here
     void free_device() {
-        void *ptrs[] = {w, w32, wl16, wl8, bias, scale, shift, wh[0], wh[1], whF, wh16F, biasF, ww[0], ww[1], ones, zeros, wh16, whf};
+        void *ptrs[] = {w, w32, wl16, bias, scale, shift, wh, whF, biasF, ww[0], ww[1], ones, zeros, whf};
         for (void *p : ptrs) if (p) (void)hipFree(p);
     }
 };
@@ -111,16 +111,12 @@ struct qgx_generator {
     int opt_h2_w8_min96 = 1024;    // 5x5 layer at 96 x 96: minimum tile count for the 8-wave x-tiled kernel
     int opt_h2_w8 = 3;             // k_convh2 as one 8-wave workgroup per CU: bit 0 the 5x5 layer, bit 1 the 3x3 layers (64 x 64)
     int opt_prio_alt = 1;          // k_convh2 with two workgroups per CU: alternate their wave priority per tile
-    int opt_h4 = 0;                // 5x5 layer: k_convh4 (full-line patch chunks, 8 waves, R = 8)
     int opt_h2_grid = 0;           // k_convh2: persistent workgroups per launch (0 = one or two per CU by LDS size)
     int opt_wino = 2;              // f16x3: the 5x5 layer as a 1-D Winograd convolution F(4, 5) along x (k_convw): 0 never, 1 on every
                                    //   specialised grid, 2 = per grid size, where calibrate_wino() admitted it
     int auto_wino_n[5] = {0, 0, 0, 0, 0};            //   ... what calibrate_wino() decided for N = 32, 48, 64, 96, 128 and the errors it measured
     float wino_err_n[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    int opt_stop_layer = 0;        //   A/B library, debugging: return after this many layers (the activation buffers keep their outputs)
     int opt_wino2 = 1;             //   ... as k_convw2 (conv_wino2.hpp: transform under the MFMAs, bit-identical) where that kernel exists; 0 = k_convw
-    int opt_wino_pl = 0;           //   A/B library: 1 = channel-planar layer-1 output and the MFMA input transform (measured: see wino_planar)
-    int opt_wino_exp = 0;          //   A/B library: timing experiments (conv_wino.hpp EXP)
     int opt_h2_rows96 = 0;         // 3x3 layers at 96 x 96: tile rows, 0 = by tile-count quantisation, 12 (6 waves), 16 (8 waves)
     int opt_wino_rows64 = 0;       //   ... its tile shape at 64 x 64, 128 x 128 and 32 x 32: 0 = by tile-count quantisation, 4 = the half-height
                                    //   shape (4 x 64 tiles; 8 x 32 at 32 x 32), 8 = the full one
@@ -131,21 +127,16 @@ struct qgx_generator {
     int opt_part_max_tiles = 96;   // f16x3: split K on the wide layers below this many quarter-height tiles (crossover against the Winograd
                                    //   layer's half-height shape: 6 members at 64 x 64 — forward 166.8 -> 158.0 us —, 4 at 96 x 96: 217.5 -> 184.3)
     int opt_last_rows = 0;         // VALU last layer: rows per workgroup (0 = automatic)
-    int opt_h3 = 0;                // 5x5 layer on 16x16x32 MFMAs (k_convh3): measured no faster in the full kernel
     int opt_half_min_tiles = 1;
     int opt_tiny_pairs = 7;        // tiny ensembles at 64 x 64 (split-K path): bit 0 layers (7, 8), bit 1 layers (5, 6), bit 2 layers (3, 4) as ONE fused launch on 2-row strips
-    int opt_pair_lp = 1;           // A/B library only: 0 = the pair kernels fetch the two halves of a line in different chunk iterations
     int opt_small_tiles = 1;       // 64 x 64, at most 4 members: half-height tiles (small_tiles())
     int opt_fuse96 = 2;            // ... at 96 x 96 (4-row strips): bit 0 (5,6), 1 (7,8)
     int opt_fuse = 3;              // f16x3, 64x64: 3x3 layers fused pairwise (k_convh_pair): bit 0 (5,6), 1 (7,8), 2 (3,4)
     int opt_pair = 1;              // 3x3 k_convh2: fetch both 64-byte halves of a pixel's 128-byte line together
-    int opt_h2 = 3;                // bit 1: k_convh2 for the 5x5 layer, bit 0: for the 3x3 layers (64x64 grids)
-    int opt_res = 1;               // f16x3 3x3 layers: resident-weight kernel where its tile fits in LDS
     int opt_member_chunk = 0;      // 16-bit path: members per sub-batch (0 = whole ensemble)
-    int opt_half_nw = 8;           // 16-bit hidden layers: 4 waves x 2 workgroups per CU, or 8 x 1
     int opt_first_h = 1;           // f16x3 path: first layer on the 16-bit cores too (0: exact-f32 MFMA first layer)
-    int opt_precision = 3;         // 0 = exact f32 MFMA, 1 = f16 MFMA, 3 = f16x3 split (f32-class accuracy; default
-                                   // wherever the ensemble fills the 8-wave tiles, see half_path_ok)
+    int opt_precision = 3;         // 0 = exact f32 MFMA, 3 = f16x3 split (f32-class accuracy; the default on the grids
+                                   // k_convh2 is specialised for, see half_path_ok)
     float opt_ascale = 1.f;        // power-of-two pre-scale of stored 16-bit activations (chosen by calibrate())
     unsigned *calib_dev = nullptr; // calibration only: per-layer max |activation| of the exact-f32 evaluation
     float calib_max[10] = {0};     // [0..6] stored (post-BatchNorm) activations, [8] layer 1 before its BatchNorm
@@ -182,6 +173,19 @@ bool cnng_size_ok(const NetHost &net, int B, int N);
 // conv.hip helpers the generic launchers share
 int ensure_dynamic_lds(const void *kern, int bytes);
 int choose_rows(int N);
+
+// One launch of a conv-family kernel (conv.hip, conv_generic.hip, conv_wino2.hip): raises the kernel's dynamic-LDS cap
+// (ensure_dynamic_lds: once per kernel, device and host thread), launches, and reports a refused launch.  Tile shapes,
+// argument structs and ProfScope stay with the launchers.
+template <typename... Params, typename... Args>
+int launch_conv_kernel(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args &...args) {
+    if (lds > 0) { if (const int rc = ensure_dynamic_lds((const void *)kern, (int)lds)) return rc; }
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    QGX_HIP(hipGetLastError());
+    return QGX_OK;
+}
+// at most `cap` persistent workgroups, never more than total_tiles
+inline int persistent_grid(int cap, int total_tiles) { return cap < total_tiles ? cap : total_tiles; }
 
 // The profiler's bracket around one launcher: begin() records the start event of a pair when `layer` is the profiled one,
 // and the stop event is recorded when the scope is left on ANY path, so that qgx_generator_profile_read never meets a

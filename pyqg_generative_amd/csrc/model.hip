@@ -207,7 +207,7 @@ extern "C" const char *qgx_last_error(void) { return g_err; }
 #define QGX_SOURCE_HASH "unknown"
 #endif
 #ifdef QGX_AB
-extern "C" const char *qgx_version(void) { return "qgx 0.2 (gfx950) src " QGX_SOURCE_HASH " +ab"; }   // A/B library: every kernel variant
+extern "C" const char *qgx_version(void) { return "qgx 0.2 (gfx950) src " QGX_SOURCE_HASH " +ab"; }   // A/B library: the product plus the test hooks
 #else
 extern "C" const char *qgx_version(void) { return "qgx 0.2 (gfx950) src " QGX_SOURCE_HASH; }
 #endif

@@ -32,6 +32,95 @@ def test_fixture_matches_the_float64_restatement(name, N):
         assert np.abs(got.mean(axis=(-2, -1))).max() < 1e-9 * np.abs(got).max()
 
 
+@pytest.mark.parametrize('name,N', [(n, N) for n, c in AR.EDGE_CASES.items() for N in c['sizes']])
+def test_edge_truth_is_the_references_float64_forward(name, N):
+    """the truth of the generic engine's edge cases (AR.edge_truth: plain numpy in float64 on seeded weights and inputs) against the
+    reference's own AndrewCNN in float64 at 256 seeded positions of its output (generator_arch_edges.npz): two float64 evaluations
+    of sums of at most 6400 terms, 1e-12 of max|y|"""
+    from pyqg_generative_amd import weights
+    d = AR.edge_fixture()
+    net = AR.edge_net(name)
+    assert weights.net_checksum(net) == str(d[f'{name}_checksum'])
+    assert [w.shape[-1] for w in net['conv_w']] == AR.edge_kernels(name)
+    got, want, ymax = AR.edge_truth(name, N), d[f'{name}_y_{N}'], float(d[f'{name}_ymax_{N}'])
+    assert got.shape == (AR.EDGE_T, 2, N, N) and got.dtype == np.float64 and want.shape == (AR.EDGE_SAMPLES,)
+    pos = AR.edge_positions(name, N)
+    assert len(np.unique(pos // (N * N))) == 2 * AR.EDGE_T          # both members, both channels
+    err = np.abs(got.reshape(-1)[pos] - want).max() / ymax
+    print(f'\nedge case {name} N={N}: restatement vs the reference in float64 {err:.2e} (max|y| {ymax:.3g})')
+    assert err < 1e-12
+    assert abs(np.abs(got).max() / ymax - 1) < 1e-12
+    if AR.EDGE_CASES[name]['div']:
+        assert np.abs(got.mean(axis=(-2, -1))).max() < 1e-9 * ymax
+
+
+# csrc/conv_generic.hip at the commit that retired the A/B-only conv kernels, restated: tiles_per_wg (l. 293), rows_generic
+# (l. 299-309), launch_convg's choice of the instantiation (l. 331-341) and cnn_pack_net_arch's padding (l. 255-256)
+def _tiles_per_wg(ntf):
+    return 2 if ntf % 2 == 0 else 1
+
+
+def _rows_generic(B, N, ny):
+    cap = 256 if 256 % N == 0 else 384
+    best = 0
+    for R in range(1, N + 1):
+        if N % R or (R * N) % 32:
+            continue
+        if R * N > cap:
+            break
+        best = R
+    while best > 1 and best % 2 == 0 and ((best // 2) * N) % 32 == 0 and B * (N // best) * ny < 256:
+        best //= 2
+    return best
+
+
+def _launches(name, N, B):
+    """(N, R, M-tiles per wave, NT, ny, chunks of input channels as (full, rest)) of every convolution of the case"""
+    from pyqg_generative_amd import weights
+    c = AR.EDGE_CASES[name] if name in AR.EDGE_CASES else AR.CASES[name]
+    ch = [c['n_in']] + list(c['hidden_channels']) + [4 if c['div'] else 2]
+    ks = AR.edge_kernels(name) if name in AR.EDGE_CASES else weights.arch_kernels(c['hidden_channels'])
+    out = []
+    for l in range(len(ch) - 1):
+        cinp = 8 if l == 0 else -(-ch[l] // 8) * 8
+        ntf = -(-ch[l + 1] // 32)
+        nt = _tiles_per_wg(ntf)
+        R = _rows_generic(B, N, ntf // nt)
+        out.append((N, R, 3 if R * N // 32 > 8 else 2, nt, ntf // nt, (cinp // 32, cinp % 32), ks[l]))
+    return out
+
+
+ALL_TILE_SHAPES = {16: [16, 8, 4, 2], 32: [8, 4, 2, 1], 48: [8, 4, 2], 64: [4, 2, 1], 96: [4, 2, 1], 128: [2, 1]}
+
+
+def test_edge_cases_reach_every_launch_shape_of_the_generic_engine():
+    """what tests/test_gpu_arch.py launches (AR.launch_table) against what the rule can give: all 19 (N, R) tile shapes, both M-tile
+    counts per wave with both NT, every (NT, ny) of 1 ... 8 output tiles, the chunk counts, and a 5x5 layer over 256 channels"""
+    # the rule's own range: every member count at every size gives one of the 19 shapes, and each is given by some count
+    for N, Rs in ALL_TILE_SHAPES.items():
+        assert {_rows_generic(B, N, 1) for B in range(1, 600)} == set(Rs), N
+        for ny in (2, 3, 4, 5, 7):
+            assert {_rows_generic(B, N, ny) for B in range(1, 600)} <= set(Rs), (N, ny)
+    runs = [s for name, N, B in AR.launch_table() for s in _launches(name, N, B)]
+    assert {(N, R) for N, R, *_ in runs} == {(N, R) for N, Rs in ALL_TILE_SHAPES.items() for R in Rs}
+    assert len({(N, R) for N, R, *_ in runs}) == 19
+    assert {(mt, nt) for _, _, mt, nt, *_ in runs} == {(2, 1), (2, 2), (3, 1), (3, 2)}
+    assert {(nt, ny) for _, _, _, nt, ny, *_ in runs} == {(1, 1), (2, 1), (1, 3), (2, 2), (1, 5), (2, 3), (1, 7), (2, 4)}
+    chunks = {ck for *_, ck, _ in runs}
+    assert {(3, 0), (6, 0), (7, 0), (8, 0), (1, 8), (0, 8), (0, 16), (0, 24), (2, 0), (4, 0)} <= chunks
+    assert (8, 0, 5) in {(ck[0], ck[1], ks) for *_, ck, ks in runs}          # 25 taps x 256 channels: K = 6400
+    # the ladder of each (case, N) walks every R of that size, and the two below-threshold counts take the smaller tile
+    for (name, N), Bs in AR.LADDER.items():
+        if name != 'E':
+            assert {_launches(name, N, B)[0][1] for B in Bs} == set(ALL_TILE_SHAPES[N]), (name, N)
+            assert all(len({s[1] for s in _launches(name, N, B)}) == 1 for B in Bs)          # ny = 1 throughout: one R per launch
+    assert _launches('I', 32, 63)[0][1] == 4 and _launches('I', 32, 64)[0][1] == 8
+    assert _launches('I', 96, 10)[0][1] == 2 and _launches('I', 96, 11)[0][1] == 4
+    # E at 16 x 16: its wide layers (ny = 4) and its last layer (ny = 1) change shape at different counts
+    assert [tuple(s[1] for s in _launches('E', 16, B)) for B in AR.LADDER[('E', 16)]] == \
+        [(2, 2, 2), (2, 2, 2), (4, 4, 2), (8, 8, 2), (16, 16, 4)]
+
+
 def test_state_dict_key_layout_follows_the_flags():
     from pyqg_generative_amd import weights
     s = weights.arch_shapes(2, [24, 40, 12, 20], batch_norm=False, bias=False)

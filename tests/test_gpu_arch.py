@@ -1,7 +1,10 @@
 """GPU: AndrewCNN nets of any hidden_channels on the generic engine (csrc/conv_generic.hip, qgx_generator_create_arch): forward
 against the reference's own AndrewCNN (tests/golden/generator_arch.npz), every launch variant and member count, the shipped
 architecture through the new entry point bit for bit, online steps with AR1 and deterministic sampling, the model classes from
-temporary folders, guard bands around the padded widths, and the grid sizes refused before anything is launched."""
+temporary folders, guard bands around the padded widths, and the grid sizes refused before anything is launched.  The edge cases
+of arch_restatement.EDGE_CASES (widths 1 ... 256, 1 ... 8 output tiles, every chunk count, the missing flag combinations, kernel
+sizes [3, 5, 5]) against the float64 restatement at every admitted grid size, every tile shape of rows_generic bit for bit
+against the one-member launch, and the online and deterministic paths with a generic handle at 32, 64 and 96."""
 import ctypes as C
 
 import numpy as np
@@ -57,8 +60,7 @@ def _members(name, N, B):
 #   A / D at 64 x 64 with 16 members: the full tile of 8 M-tiles, MT = 2;  with 1 member: R = 1, two M-tiles
 #   B at 48 x 48 with 44 members: the full tile of 12 M-tiles, MT = 3 (with NT = 1 and NT = 2);  with 22: R = 4, 6 M-tiles on
 #   MT = 2 (two waves one tile short);  with 1: R = 2, three M-tiles
-SHAPES = [(n, 16, B) for n in AR.CASES for B in (1, 3, 40)] + [('A', 64, 1), ('A', 64, 16), ('B', 48, 1), ('B', 48, 22), ('B', 48, 44),
-                                                                ('D', 64, 1), ('D', 64, 16)]
+SHAPES = AR.SHAPES          # (listed there: the coverage test of tests/test_arch_cpu.py counts them with the edge cases' launches)
 
 
 @pytest.mark.parametrize('name,N,B', SHAPES)
@@ -81,6 +83,86 @@ def test_results_do_not_depend_on_the_member_count(gens):
     y16 = gens['A'].cnn_forward(xd)
     y1 = gens['A'].cnn_forward(xd[:1].contiguous())
     assert torch.equal(y16[:1], y1)
+
+
+# ---- edge cases of the generic engine (AR.EDGE_CASES) ----------------------------------------------------------------------
+def _edge_generator(name):
+    import pyqg_generative_amd as qa
+    xs, ys = AR.scales()
+    return qa.Generator(AR.EDGE_KIND[name], [AR.edge_net(name)], xs, ys)
+
+
+@pytest.fixture(scope='module')
+def edge_gens():
+    """name -> the case's handle, made on first use and shared"""
+    made = {}
+
+    def get(name):
+        if name not in made:
+            made[name] = _edge_generator(name)
+        return made[name]
+    yield get
+    for g in made.values():
+        g.close()
+
+
+def _cnn_forward_between_canaries(gen, xd, what):
+    """qgx_cnn_forward of net 0 with y between guard bands, written completely -> y (B, 2, N, N) float32 on the device"""
+    import redzone
+    from pyqg_generative_amd._lib import lib, check
+    from pyqg_generative_amd.engine import _ptr, _stream
+    B, _, N, _ = xd.shape
+    gen.check_size(B, N, 0)
+    assert xd.dtype == torch.float32 and xd.is_contiguous() and xd.shape[1] == gen.n_in
+    gy = redzone.guarded((B, 2, N, N), torch.float32, 'cuda')
+    check(lib.qgx_cnn_forward(gen._h, 0, _ptr(xd), _ptr(gy.t), B, N, _stream()))
+    torch.cuda.synchronize()
+    gy.check(written=True, what=what)
+    return gy.t
+
+
+def _check_against_truth(name, y, y64, what):
+    err = np.abs(y - y64).max() / np.abs(y64).max()
+    print(f'\nARCH edge case {what}: vs float64 {err:.2e}' + (' (above a third of the bound)' if err > GEN_TOL / 3 else ''))
+    assert err < GEN_TOL, what
+    if AR.EDGE_CASES[name]['div']:
+        assert np.abs(y.astype('float64').mean(axis=(-2, -1))).max() < 1e-6 * np.abs(y64).max(), what
+    return err
+
+
+@pytest.mark.parametrize('name,N', [(n, N) for n, c in AR.EDGE_CASES.items() for N in c['sizes']])
+def test_edge_case_forward_matches_the_float64_truth(edge_gens, name, N):
+    """qgx_cnn_forward against the float64 restatement (pinned to the reference's AndrewCNN in tests/test_arch_cpu.py): 2e-5 of
+    max|y|, where the restatement's own float32 evaluation stays within 1.3e-6; y between canaries, written completely"""
+    x, y64 = AR.edge_members(name, N, AR.EDGE_T)
+    y = _cnn_forward_between_canaries(edge_gens(name), torch.as_tensor(x).cuda(), f'{name} N={N} y').cpu().numpy()
+    assert y.shape == (AR.EDGE_T, 2, N, N)
+    _check_against_truth(name, y, y64, f'{name} N={N} B={AR.EDGE_T}')
+
+
+@pytest.mark.parametrize('name,N', list(AR.LADDER))
+def test_every_tile_shape_gives_the_same_bits_and_meets_the_truth(name, N):
+    """the member counts of AR.LADDER walk every rows-per-workgroup R that rows_generic gives at this size (tests/test_arch_cpu.py
+    computes which), up and then down on ONE fresh handle (its workspaces grow, then are reused for smaller launches): three fixed
+    members, placed first, in the middle and last, come out bit for bit as in their one-member launches — the tile shape does not
+    enter the summation order — and every member meets the float64 truth"""
+    Bs = AR.LADDER[(name, N)]
+    gen = _edge_generator(name)
+    xa, ya = AR.edge_members(name, N, max(max(Bs), 4))
+    fixed = (0, 1, 3)          # members of `xa`: the two inputs and a shifted one
+    assert Bs[0] == 1 and len(Bs) > 1
+    # the one-member launches: the smallest tile of this size
+    alone = [_cnn_forward_between_canaries(gen, torch.as_tensor(xa[f:f + 1].copy()).cuda(), f'{name} N={N} alone y') for f in fixed]
+    for B in Bs + Bs[-2::-1]:
+        where = {0: 0} if B == 1 else {0: 0, B // 2: 1, B - 1: 2}
+        x, y64 = xa[:B].copy(), ya[:B].copy()
+        for pos, f in where.items():
+            x[pos], y64[pos] = xa[fixed[f]], ya[fixed[f]]
+        y = _cnn_forward_between_canaries(gen, torch.as_tensor(x).cuda(), f'{name} N={N} B={B} y')
+        for pos, f in where.items():
+            assert torch.equal(y[pos], alone[f][0]), (B, pos)
+        _check_against_truth(name, y.cpu().numpy(), y64, f'{name} N={N} B={B} (ladder)')
+    gen.close()
 
 
 def test_generic_handle_is_exact_f32_only(gens):
@@ -177,24 +259,34 @@ def _eddy_like_q(rs, B, N):
     return q / q.std(axis=(-2, -1), keepdims=True) * AR.scales()[0].astype('float64').reshape(1, 2, 1, 1)
 
 
-@pytest.mark.parametrize('name,sampling,B,opts', [('A', 'AR1', 3, {}), ('A', 'AR1', 2, dict(streams=2)), ('A', 'constant', 2, dict(genfuse=0)),
-                                                  ('A', 'deterministic', 2, {}), ('B', 'AR1', 3, {}), ('B', 'AR1', 2, dict(streams=2))],
-                         ids=['gan-ar1', 'gan-ar1-halves', 'gan-const-unfused', 'gan-deterministic', 'ols-ar1', 'ols-ar1-halves'])
-def test_online_forcing_is_the_generators_own(gens, name, sampling, B, opts):
-    """three steps at 16 x 16: the forcing the (fused) step applied equals qgx_generator_forward / _forward_mean on the state and
-    the latent noise read back from the engine — bit for bit, as the fused prologue is against separate kernels
-    (test_gpu_div.py::test_fused_step_prologue_is_bit_identical); the two-halves schedule runs the second workspace"""
+@pytest.mark.parametrize('name,N,sampling,B,opts,M', [
+    ('A', 16, 'AR1', 3, {}, 4), ('A', 16, 'AR1', 2, dict(streams=2), 4), ('A', 16, 'constant', 2, dict(genfuse=0), 4),
+    ('A', 16, 'deterministic', 2, {}, 4), ('B', 16, 'AR1', 3, {}, 4), ('B', 16, 'AR1', 2, dict(streams=2), 4),
+    # edge case I at the sizes ensembles run at: R = 2 of the 64 x 64 ladder; 130 members (full tiles, an odd half); the AUTOMATIC
+    # halves at 96 x 96 (16 members: R = 4 as a whole, 8 per half: R = 2, each half in its own workspace); the unfused prologue at
+    # 96 x 96; deterministic sampling with M = 128 realisations of 2 members: one pseudo-batch of 256 at 32 x 32 (R = 8)
+    ('I', 64, 'AR1', 4, {}, 4), ('I', 64, 'constant', 130, {}, 4), ('I', 96, 'AR1', 16, {}, 4), ('I', 96, 'AR1', 3, dict(genfuse=0), 4),
+    ('I', 32, 'deterministic', 2, {}, 128)],
+    ids=['gan-ar1', 'gan-ar1-halves', 'gan-const-unfused', 'gan-deterministic', 'ols-ar1', 'ols-ar1-halves',
+         'thin-64-ar1', 'thin-64-const-130', 'thin-96-ar1-auto-halves', 'thin-96-ar1-unfused', 'thin-32-deterministic-256'])
+def test_online_forcing_is_the_generators_own(gens, edge_gens, name, N, sampling, B, opts, M):
+    """three steps (the first table's nets at 16 x 16, the thin edge case at 32, 64 and 96): the forcing the (fused) step applied
+    equals qgx_generator_forward / _forward_mean on the state and the latent noise read back from the engine — bit for bit, as the
+    fused prologue is against separate kernels (test_gpu_div.py::test_fused_step_prologue_is_bit_identical); the two-halves
+    schedule runs the second workspace"""
     import pyqg_generative_amd as qa
     import pyqg_generative_amd._lib as L
-    N, M, seed, off = 16, 4, 21, 5
-    gen = gens[name]
+    seed, off = 21, 5
+    gen = gens[name] if name in gens else edge_gens(name)
     q0 = _eddy_like_q(np.random.RandomState(3 + B), B, N)
-    e = qa.EnsembleEngine(nx=N, n_members=B, dt=14400.)
+    e = qa.EnsembleEngine(nx=N, n_members=B, dt=14400. * 16 / N)
     for k, v in opts.items():
         e.set_option(k, v)
     e.set_q(q0)
-    if 'streams' in opts:
-        assert e.step_streams(gen, sampling=sampling) == 2
+    if 'streams' in opts or (N, B) == (96, 16):
+        assert e.step_streams(gen, sampling=sampling) == 2          # at 96 x 96 with 16 ... 64 members: with no option set
+    else:
+        assert e.step_streams(gen, sampling=sampling) == 1
     for s in range(3):
         q_pre = e.get(L.F_Q).clone()
         e.step(1, generator=gen, sampling=sampling, nsteps_decor=1, seed=seed, member_offset=off, n_mean=M)
@@ -206,7 +298,7 @@ def test_online_forcing_is_the_generators_own(gens, name, sampling, B, opts):
         else:
             want = gen.forward(q_pre, e.get(L.F_Z).contiguous(), demean=True)
         diff = (S - want).abs().max().item() / want.abs().max().item()
-        print(f'\nARCH online {name} {sampling} B={B} {opts} step {s}: |S - forward| / max {diff:.1e}')
+        print(f'\nARCH online {name} N={N} {sampling} B={B} {opts} step {s}: |S - forward| / max {diff:.1e}')
         assert torch.equal(S, want), (s, diff)
         assert S.abs().max().item() > 0
     assert e.tc == 3
@@ -220,6 +312,41 @@ def test_online_forcing_is_the_generators_own(gens, name, sampling, B, opts):
             gen.forward_mean(e.get(L.F_Q), 4)
         assert e.tc == 3
     e.close()
+
+
+S_TOL = 2e-5            # tests/test_gpu_deterministic.py's bound on a deterministic forcing, of max|S| per member and layer
+
+
+def test_forward_mean_of_a_generic_net_matches_the_float64_truth(edge_gens):
+    """qgx_generator_forward_mean with a generic handle (edge case I, 32 x 32, 2 members, M = 5 realisations: one pseudo-batch of
+    10) against y_std * mean_j AR.forward([q / x_std, z_j]) in float64, z_j from the Philox streams the device draws
+    (tests/test_gpu_deterministic.py::_realisations); de-mean off and on"""
+    from oracle import samplers_ref, gen_ref
+    N, B, M, seed, off, t = 32, 2, 5, 31, 7, 3
+    gen, net = edge_gens('I'), AR.edge_net('I')
+    xs, ys = AR.scales()
+    q = _eddy_like_q(np.random.RandomState(29), B, N)
+    X = q.astype('float32') / xs.reshape(1, 2, 1, 1)
+    assert X.dtype == np.float32
+    raw = np.empty((B, 2, N, N))
+    for b in range(B):
+        z = np.stack([samplers_ref.philox_normal(seed, off + b, t | (j + 1) << 32, 2 * N * N)[0].reshape(2, N, N) for j in range(M)])
+        x = np.concatenate([np.broadcast_to(X[b], (M, 2, N, N)), z], axis=1)
+        raw[b] = AR.forward(net, x).mean(axis=0) * ys.astype('float64').reshape(2, 1, 1)
+    dem = np.stack([gen_ref.demean(r) for r in raw])
+    scale = np.abs(dem).max(axis=(-2, -1), keepdims=True)
+    qd = torch.as_tensor(q).cuda().contiguous()
+    kw = dict(seed=seed, member_offset=off, step=t)
+    Sraw = gen.forward_mean(qd, M, demean=False, **kw).cpu().numpy()
+    S = gen.forward_mean(qd, M, demean=True, **kw).cpu().numpy()
+    e_raw, e_dem = (np.abs(Sraw - raw) / scale).max(), (np.abs(S - dem) / scale).max()
+    print(f'\nARCH forward_mean I N={N} B={B} M={M}: raw {e_raw:.2e}, de-meaned {e_dem:.2e}')
+    assert e_raw < S_TOL and e_dem < S_TOL
+    assert np.abs(S.mean(axis=(-2, -1))).max() < 1e-14 * scale.max() * N * N
+    # neither the de-meaning nor the mean over realisations is a rounding-level step of this case
+    assert (np.abs(Sraw - dem) / scale).max() > 10 * S_TOL
+    one = gen.forward_mean(qd, 1, demean=False, **kw).cpu().numpy()
+    assert (np.abs(one - raw) / scale).max() > 10 * S_TOL
 
 
 # ---- the model classes ------------------------------------------------------------------------------------------------------

@@ -523,6 +523,12 @@ int qgx_histogram(const void *x_dev, int is_double, int64_t R, int64_t T, int64_
  * includes. */
 #include "qgx_stats.h"
 
+/* ---- training ----------------------------------------------------------------
+ * Training of ANNModel's stencil network on the device (models/ann_model.py:34-52 fit, tools/cnn_tools.py:645-700 train):
+ * stencil rows, a fused loss / gradient kernel, Adam.  The trainer handle and its entry points are declared and documented
+ * in qgx_train.h, which this header includes. */
+#include "qgx_train.h"
+
 /* ---- latent noise ------------------------------------------------------------
  * z <- a z + b xi with xi ~ N(0,1) from Philox4x32-10 (stochastic_pyqg.py:43-49).  z: (B, n_per_member) float or double,
  * n_per_member a positive multiple of 4; a == 0 overwrites z (its previous contents are not read).  Counter of the four

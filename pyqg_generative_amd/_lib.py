@@ -169,6 +169,21 @@ STATS_SYMBOLS = [
     ('qgx_flow_features', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 ]
+# what include/qgx_train.h declares: stencil rows and the trainer of ANNModel's network (tools/train_ANN.py)
+TRAIN_PARAMS, TRAIN_GRAD, TRAIN_M, TRAIN_V = range(4)
+_BATCH = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float]   # t, x, y, idx, n, scales
+TRAIN_SYMBOLS = [
+    ('qgx_ann_rows', C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ('qgx_ann_trainer_create', C.c_int, [C.POINTER(qgx_ann_weights), C.c_int, C.POINTER(C.c_void_p)]),
+    ('qgx_ann_trainer_destroy', C.c_int, [C.c_void_p]),
+    ('qgx_ann_trainer_size', C.c_int64, [C.c_void_p]),
+    ('qgx_ann_trainer_grad', C.c_int, _BATCH + [C.c_void_p, C.c_void_p]),
+    ('qgx_ann_trainer_adam', C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    ('qgx_ann_trainer_step', C.c_int, _BATCH + [C.c_double, C.c_void_p, C.c_void_p]),
+    ('qgx_ann_trainer_loss', C.c_int, _BATCH + [C.c_void_p, C.c_void_p]),
+    ('qgx_ann_trainer_read', C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    ('qgx_ann_trainer_write', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+]
 
 
 def _load():
@@ -182,7 +197,7 @@ def _load():
     # Load torch's first — torch finds no GPU when it is handed the other runtime.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS:
+    for name, res, args in SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS + TRAIN_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -24,7 +24,8 @@ class ANNModel(Parameterization):
         self.folder = folder
         # the reference builds an untrained net without read (ann_model.py:29-31) or without net.pt (:68-70), for fit()
         if not read:
-            raise NotImplementedError('ANNModel(read=False) is an untrained net for fit(); there is no training here: '
+            raise NotImplementedError('ANNModel(read=False) is an untrained net for fit(); training is '
+                                      'tools.train_ANN.fit_ann, which writes the model folder and returns the model: here, '
                                       'give a trained model folder (net.pt, scale.json)')
         path = os.path.join(folder, 'net.pt')
         if not os.path.exists(path):
@@ -52,7 +53,8 @@ class ANNModel(Parameterization):
         return self
 
     def fit(self, *args, **kw):
-        raise NotImplementedError('ANNModel.fit: training is not part of this package (load a trained model folder)')
+        raise NotImplementedError('ANNModel.fit: training is tools.train_ANN.fit_ann(ds_train, ds_test, ...), which writes '
+                                  'the model folder and returns the ANNModel read from it')
 
     def generate_latent_noise(self, ny, nx):
         return 0

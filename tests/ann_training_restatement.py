@@ -1,0 +1,179 @@
+"""Test-side restatement of ANNModel's training (pyqg_generative/models/ann_model.py:34-52 fit; tools/cnn_tools.py:321-339
+xarray_to_stencil, :373-396 prepare_data_ANN, :184-210 ANN, :555-602 AverageLoss, :645-700 train), written from their
+semantics in numpy and torch-CPU, for any dtype.  A plain helper module: the tests of tests/test_ann_training_cpu.py and
+tests/test_gpu_ann_training.py compare the device path with it.
+
+Also the data recipe those tests share: band-limited random images of unit variance, targets from a seeded teacher net
+(its output divided by its std) plus 0.1 white noise.
+"""
+import numpy as np
+import torch
+
+STEP = 3
+
+
+# ---- rows and scales ------------------------------------------------------------------------------------------------
+def stencil_rows(img, s, step=1):
+    """img (n_img, N, N) -> (R, s * s): for j, i over the multiples of `step` below N (j outer), the n_img stencils of
+    size s x s centred on (j, i) of the periodically padded images, flattened dy-major"""
+    img = np.asarray(img)
+    n, N = img.shape[0], img.shape[-1]
+    h = s // 2
+    p = np.pad(img, [(0, 0), (h, h), (h, h)], mode='wrap')
+    out = []
+    for j in range(0, N, step):
+        for i in range(0, N, step):
+            out.append(p[:, j:j + s, i:i + s].reshape(n, s * s))
+    return np.concatenate(out, axis=0)
+
+
+def prepare_data(images, s):
+    """images: [(q (n, N, N), forcing (n, N, N)), ...] -> X (R, s * s), Y (R, 1), x_scale, y_scale: the population std of
+    the centre feature and of the targets, in float64, cast to float32, as Python floats"""
+    X = np.concatenate([stencil_rows(q, s, STEP) for q, _ in images], axis=0)
+    Y = np.concatenate([stencil_rows(f, 1, STEP) for _, f in images], axis=0)
+    x_scale = float(X[:, s * s // 2].astype('float64').std().astype('float32'))
+    y_scale = float(Y.astype('float64').std().astype('float32'))
+    return X, Y, x_scale, y_scale
+
+
+# ---- the net ----------------------------------------------------------------------------------------------------------
+class TorchANN(torch.nn.Module):
+    """Linear -> ReLU -> ... -> Linear on rows; scale_invariant: |x|^2 layers(x / |x|)"""
+
+    def __init__(self, net, dtype=torch.float32):
+        super().__init__()
+        layers = []
+        n = len(net['w'])
+        for l in range(n):
+            w = torch.as_tensor(np.asarray(net['w'][l], dtype=np.float32))
+            lin = torch.nn.Linear(w.shape[1], w.shape[0])
+            with torch.no_grad():
+                lin.weight.copy_(w)
+                lin.bias.copy_(torch.as_tensor(np.asarray(net['b'][l], dtype=np.float32)))
+            layers.append(lin)
+            if l + 1 < n:
+                layers.append(torch.nn.ReLU())
+        self.layers = torch.nn.Sequential(*layers)
+        self.scale_invariant = bool(net['scale_invariant'])
+        self.to(dtype)
+
+    def forward(self, x):
+        if self.scale_invariant:
+            norm = torch.norm(x, dim=-1, p=2, keepdim=True)
+            return norm ** 2 * self.layers(x / norm)
+        return self.layers(x)
+
+    def loss(self, x, y):
+        return torch.nn.functional.mse_loss(self.forward(x), y)
+
+    def packed(self):
+        """parameters in state-dict order as one float64 vector"""
+        return np.concatenate([p.detach().double().numpy().reshape(-1) for p in self.parameters()])
+
+
+def min_abs_preactivation(net, x):
+    """per row of x (float64): the smallest |pre-activation| over every hidden neuron of the float64 net"""
+    m = TorchANN(net, torch.float64)
+    a = torch.as_tensor(x, dtype=torch.float64)
+    if m.scale_invariant:
+        a = a / torch.norm(a, dim=-1, p=2, keepdim=True)
+    least = torch.full((a.shape[0],), float('inf'), dtype=torch.float64)
+    with torch.no_grad():
+        for layer in list(m.layers)[:-1]:
+            a = layer(a)
+            if isinstance(layer, torch.nn.Linear):
+                least = torch.minimum(least, a.abs().min(dim=1).values)
+    return least.numpy()
+
+
+def normalised(X, Y, x_scale, y_scale, dtype):
+    """rows / scale as fit does it (float32 array / Python float), then cast"""
+    x = np.asarray(X, dtype=np.float32) / x_scale
+    y = np.asarray(Y, dtype=np.float32) / y_scale
+    assert x.dtype == np.float32 and y.dtype == np.float32
+    return torch.as_tensor(x).to(dtype), torch.as_tensor(y).reshape(-1, 1).to(dtype)
+
+
+# ---- the loop ---------------------------------------------------------------------------------------------------------
+def lr_sequence(num_epochs, lr, gamma=0.1):
+    """the learning rate of epochs 0 ... E - 1: it drops by gamma after the scheduler's m-th step for every milestone m in
+    [int(E / 2), int(3 E / 4), int(7 E / 8)] — once per occurrence of m in the list; a milestone 0 (E = 1) acts when the
+    scheduler is built, before the first epoch"""
+    E = int(num_epochs)
+    milestones = [int(E / 2), int(E * 3 / 4), int(E * 7 / 8)]
+    out, cur = [], float(lr) * gamma ** milestones.count(0)
+    for e in range(E):
+        out.append(cur)
+        cur = cur * gamma ** milestones.count(e + 1)
+    return out
+
+
+def train_loop(net, X, Y, Xt, Yt, x_scale, y_scale, batches, lr, dtype=torch.float64):
+    """batches[epoch] = [index array, ...].  Adam (torch defaults), the schedule above, per-epoch row-weighted mean of the
+    batch losses before each update, the test loss after the epoch.  Returns (log dict, packed parameters float64)."""
+    m = TorchANN(net, dtype)
+    x, y = normalised(X, Y, x_scale, y_scale, dtype)
+    xt, yt = normalised(Xt, Yt, x_scale, y_scale, dtype)
+    opt = torch.optim.Adam(m.parameters(), lr=lr)
+    E = len(batches)
+    lrs = lr_sequence(E, lr)
+    log = {'loss': [], 'loss_test': []}
+    for epoch in range(E):
+        for g in opt.param_groups:
+            g['lr'] = lrs[epoch]
+        total, count = 0.0, 0
+        for idx in batches[epoch]:
+            idx = torch.as_tensor(np.asarray(idx, dtype=np.int64))
+            opt.zero_grad()
+            loss = m.loss(x[idx], y[idx])
+            loss.backward()
+            opt.step()
+            total += float(loss.detach()) * len(idx)
+            count += len(idx)
+        log['loss'].append(total / count)
+        with torch.no_grad():
+            log['loss_test'].append(float(m.loss(xt, yt)))
+    return log, m.packed()
+
+
+# ---- the data recipe --------------------------------------------------------------------------------------------------
+def band_limited_images(n, N, seed):
+    """n random N x N float32 images of unit variance with power below a third of the Nyquist wavenumber"""
+    rs = np.random.RandomState(seed)
+    k = np.fft.fftfreq(N, 1.0 / N)
+    keep = (np.hypot(k[:, None], k[None, :N // 2 + 1]) <= N / 6.0) & (np.hypot(k[:, None], k[None, :N // 2 + 1]) > 0)
+    a = np.fft.irfft2(np.fft.rfft2(rs.randn(n, N, N)) * keep, s=(N, N))
+    a /= a.std(axis=(-2, -1), keepdims=True)
+    return a.astype(np.float32)
+
+
+def teacher_targets(q, teacher, seed):
+    """teacher's output at every point of the images q (n, N, N), divided by its std, plus 0.1 white noise; float32"""
+    n, N = q.shape[0], q.shape[-1]
+    s = int(teacher['stencil_size'])
+    rows = stencil_rows(q, s, 1)                                    # row (j N + i) n + img
+    with torch.no_grad():
+        y = TorchANN(teacher, torch.float64)(torch.as_tensor(rows, dtype=torch.float64)).numpy().reshape(N, N, n)
+    y = np.moveaxis(y, -1, 0)
+    y = y / y.std() + 0.1 * np.random.RandomState(seed).randn(n, N, N)
+    return y.astype(np.float32)
+
+
+def teacher_student_images(n, N, seed, s=3, scale_invariant=False):
+    """(q, forcing) images of the recipe; ONE teacher per (s, scale_invariant), weights.synthetic_ann(s, [24, 24],
+    scale_invariant, 1000), so that training and test data of different seeds follow the same law"""
+    from pyqg_generative_amd import weights
+    q = band_limited_images(n, N, seed)
+    teacher = weights.synthetic_ann(s, [24, 24], scale_invariant, 1000)
+    return q, teacher_targets(q, teacher, seed + 1)
+
+
+def as_dataset(q, f, n_run):
+    """images (n, N, N) as a dataset with dims (run, time, lev, y, x), lev = 2, on the package's dataset backend"""
+    from pyqg_generative_amd.tools.simulate import dataset_backend
+    xr = dataset_backend()
+    n, N = q.shape[0], q.shape[-1]
+    shape = (n_run, n // (2 * n_run), 2, N, N)
+    dims = ['run', 'time', 'lev', 'y', 'x']
+    return xr.Dataset({'q': (dims, q.reshape(shape)), 'q_forcing_advection': (dims, f.reshape(shape))})

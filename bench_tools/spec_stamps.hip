@@ -230,8 +230,8 @@ int main(int argc, char **argv) {
     qgx_set_q(m, qd, 0);
     qgx_step(m, 3, nullptr, 0, 0);
     unsigned long long *st; hipMalloc(&st, 64 * 8); hipMemset(st, 0, 64 * 8);
-    StepArgs a; a.qh_in = m->qh[m->cur_q]; a.qh_out = m->qh[m->cur_q ^ 1]; a.q = m->q; a.S = m->S; a.dqh = m->dqh;
-    a.dq_new = m->dq[m->i_pp]; a.dq_p = m->dq[m->i_new]; a.dq_pp = m->dq[m->i_p]; a.ph = m->ph; a.u = m->u; a.v = m->v;
+    StepArgs a; a.qh_in = m->qh[m->bk.cur_q]; a.qh_out = m->qh[m->bk.cur_q ^ 1]; a.q = m->q; a.S = m->S; a.dqh = m->dqh;
+    a.dq_new = m->dq[m->bk.i_pp]; a.dq_p = m->dq[m->bk.i_new]; a.dq_pp = m->dq[m->bk.i_p]; a.ph = m->ph; a.u = m->u; a.v = m->v;
     a.dt1 = 1.9 * 14400; a.dt2 = -1.3 * 14400; a.dt3 = 0.4 * 14400; a.weight = 1; a.has_S = 1; a.demean = 1; a.diag = 0;
     const size_t lds = (size_t)N * (N + 1) * 16 + N * 4 + 16;
     hipFuncSetAttribute((const void *)k_step_small_stamped, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

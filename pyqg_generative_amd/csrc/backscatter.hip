@@ -274,7 +274,7 @@ int backscatter_prepare(qgx_model *m) {
 int backscatter_eval(qgx_model *m, const double2 *qh, double *S, double *ratio, hipStream_t st) {
     const SpecDev &d = m->d;
     BsArgs a;
-    a.qh = qh; a.smag = m->bs_const; a.back = m->bs_const + m->B; a.eps = m->bs_eps; a.S = S; a.ratio = ratio;
+    a.qh = qh; a.smag = m->bs_const; a.back = m->bs_const + m->cfg.n_members; a.eps = m->bs_eps; a.S = S; a.ratio = ratio;
     if (m->small) {
         QGX_BS_DISPATCH_N(d.N, hipLaunchKernelGGL(k_backscatter_small<NN>, dim3(d.B), dim3(BS_THREADS), bs_small_lds_bytes(d), st, d, a))
         QGX_HIP(hipGetLastError());

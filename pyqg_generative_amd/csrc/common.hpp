@@ -9,6 +9,7 @@
 #include <vector>
 #include <string>
 #include <memory>
+#include <tuple>
 #include "../../include/qgx.h"
 
 namespace qgx {
@@ -159,6 +160,35 @@ struct DiagAcc { double *KEspec, *Ensspec, *entspec, *APEflux, *KEflux, *APEgens
                         *Dissspec, *ENSDissspec, *ENSflux, *ENSgenspec, *ENSfrictionspec, *ENSparamspec; };
 constexpr int N_DIAGS = 16;
 
+// large grids (spectral_large.hip): complex work fields per member, of N rows at pitch N + large_zpad()
+constexpr int ZF = 3;   // zbuf: layers 0,1 and one scratch (S / q pair)
+constexpr int DZF = 4;  // dg_z: the fused diagnostics increment
+int large_zpad();
+
+// kernel.pyx::_forward_timestep: Euler, AB2, AB3 by start-up level
+inline void ab3_coefficients(int level, double dt, double out[3]) {
+    if (level == 0) { out[0] = dt; out[1] = 0.0; out[2] = 0.0; }
+    else if (level == 1) { out[0] = 1.5 * dt; out[1] = -0.5 * dt; out[2] = 0.0; }
+    else { out[0] = 23. / 12. * dt; out[1] = -16. / 12. * dt; out[2] = 5. / 12. * dt; }
+}
+
+// The stepping bookkeeping of a model: everything a step changes on the host.  It is saved, restored, compared and copied as
+// a whole (the run kernel's undo record, the two half-ensembles of qgx_step), so a field added here is carried everywhere.
+struct StepBook {
+    int64_t tc = 0, const_counter = 0, dg_count = 0;
+    int ablevel = 0, cur_q = 0;            // AB3 start-up level (0 Euler, 1 AB2, 2 AB3); qh[cur_q] is current
+    int i_new = 0, i_p = 1, i_pp = 2, i_x = 3;   // roles of dq[]
+    bool uv_stale = false;                 // the last step did not store ph, u, v (refresh_diag == 0): status inverts first
+    bool q_stale = false;                  // large-N path: q lags qh (unparameterized steps keep no real-space q)
+    bool z_double = false, have_noise = false, have_forcing = false;
+    uint64_t noise_step = 0;
+    const void *x_ready_gen = nullptr;     // the generator whose input the last step kernel assembled (GenFuse::X), or null
+    uint64_t x_ready_step = 0;             //   ... for this noise step
+    auto tie() const { return std::tie(tc, const_counter, dg_count, ablevel, cur_q, i_new, i_p, i_pp, i_x, uv_stale, q_stale,
+                                       z_double, have_noise, have_forcing, noise_step, x_ready_gen, x_ready_step); }
+    bool operator==(const StepBook &o) const { return tie() == o.tie(); }
+};
+
 }  // namespace qgx
 
 struct qgx_generator;
@@ -180,38 +210,24 @@ struct qgx_model {
     // a step that failed half-way (one half-ensemble advanced, the other not; a stream operation refused after the fork) leaves
     // device buffers and bookkeeping out of step: every later call on the handle fails loudly with this message
     std::string broken;
+    qgx::StepBook bk;               // the stepping bookkeeping (a half-ensemble advances a copy; sib_epoch is not part of it)
     // state (device)
     double *q = nullptr, *u = nullptr, *v = nullptr, *S = nullptr;
-    double2 *qh[2] = {nullptr, nullptr};   // ping-pong; qh[cur_q] is current
+    double2 *qh[2] = {nullptr, nullptr};   // ping-pong; qh[bk.cur_q] is current
     double2 *ph = nullptr, *dqh = nullptr; // dqh: spectral forcing of the last step (pyqg m.dqh)
     double2 *dq[4] = {nullptr, nullptr, nullptr, nullptr};   // AB3 tendency history; [3]: large grids, spare slot of the run kernel
     double2 *zbuf = nullptr;               // large-N path: (B,3,N,N) complex work array
-    bool q_stale = false;                  // large-N path: q lags qh (unparameterized steps keep no real-space q)
-    bool uv_stale = false;                 // the last step did not store ph, u, v (refresh_diag == 0): status inverts first
     void *team_ctl = nullptr;              // large-N path: census / barrier block of the XCD-resident step kernel
     int team_state = 0;                    //   0 not probed, 1 available, -1 not available
     bool team_pending = false;             //   a run was launched whose flags have not been read back yet
-    struct TeamUndo {                      //   bookkeeping as it was before the pending run (a run writes ONLY to buffers
-        int K = 0;                         //   that hold nothing live, so a run that raised a flag is undone by restoring
-        int cur_q, i_new, i_p, i_pp, i_x;  //   these and replayed on the three-launch path)
-        int64_t tc;
-        int ablevel;
-        bool uv_stale, q_stale;
+    struct TeamUndo {                      //   the record as it was before the pending run (a run writes ONLY to buffers that hold
+        int K = 0;                         //   nothing live, so a run that raised a flag is undone by restoring the record and
+        qgx::StepBook before;              //   replayed on the three-launch path)
     } team_undo;
     hipStream_t team_stream = nullptr;     //   the stream the pending run was launched on (its flag is read back there)
     int team_replays = 0;                  //   runs that raised a flag and were replayed
-    int cur_q = 0;
-    int i_new = 0, i_p = 1, i_pp = 2, i_x = 3;   // roles of dq[]
     void *z = nullptr;                     // latent noise (B,2,N,N) float or double
     void *xi = nullptr;                    // scratch white noise for AR1
-    bool z_double = false;
-    bool have_noise = false;
-    int64_t const_counter = 0;
-    bool have_forcing = false;
-    const void *x_ready_gen = nullptr;     // the generator whose input the last step kernel assembled (GenFuse::X), or null
-    uint64_t x_ready_step = 0;             //   ... for this noise step
-    int64_t tc = 0;
-    int ablevel = 0;
     // molecular viscosity (qgx_set_viscosity): one nu per member in device memory the model owns; a half-ensemble sees its slice
     double *visc_nu = nullptr;
     bool visc_on = false;
@@ -225,9 +241,8 @@ struct qgx_model {
     std::shared_ptr<std::vector<double>> bs_host;
     double2 *bs_spec[3] = {nullptr, nullptr, nullptr};
     double *bs_real[3] = {nullptr, nullptr, nullptr};
-    uint64_t noise_step = 0;
     // time-averaged diagnostics (diag.hip)
-    int64_t dg_start = 0, dg_count = 0;
+    int64_t dg_start = 0;
     int dg_every = 0;
     double *dg_R[7] = {};
     double *dg_S[7] = {};
@@ -246,6 +261,36 @@ struct qgx_model {
 };
 
 namespace qgx {
+// THE list of the model's device buffers with a leading member axis: f(pointer, bytes per member) for each, null ones
+// included.  qgx_step slices its half-ensembles with it and qgx_destroy frees what it yields: a new per-member buffer is
+// added here and nowhere else.  The sizes are those of qgx_create, diag_ensure_alloc, large_diag_fused, backscatter_prepare,
+// qgx_set_viscosity / _backscatter and step_sib_ensure.  z_elem: bytes of a latent-noise element in use (allocated: double).
+template <class F>
+void for_each_member_buffer(qgx_model &m, size_t z_elem, F &&f) {
+    const size_t N = (size_t)m.N, NK = (size_t)m.NK;
+    const size_t real = 2 * N * N * sizeof(double), spec = 2 * N * NK * sizeof(double2);
+    const size_t zfield = (N + (size_t)large_zpad()) * N * sizeof(double2);
+    f(m.q, real); f(m.u, real); f(m.v, real); f(m.S, real);
+    f(m.qh[0], spec); f(m.qh[1], spec); f(m.ph, spec); f(m.dqh, spec);
+    for (double2 *&p : m.dq) f(p, spec);
+    f(m.z, 2 * N * N * z_elem); f(m.xi, 2 * N * N * z_elem);
+    f(m.zbuf, ZF * zfield); f(m.dg_z, DZF * zfield);
+    for (double *&p : m.dg_R) f(p, real);
+    for (double *&p : m.dg_S) f(p, spec);                                           // (complex fields kept as doubles)
+    for (int i = 0; i < N_DIAGS; ++i) f(m.dg_acc[i], (i < 2 ? 2 : 1) * N * NK * sizeof(double));
+    f(m.visc_nu, sizeof(double));
+    // two planes, C_S then C_B, of one double per member: backscatter_eval finds the second cfg.n_members further on
+    f(m.bs_const, sizeof(double));
+    for (double2 *&p : m.bs_spec) f(p, spec);
+    for (double *&p : m.bs_real) f(p, real);
+    f(m.sib_flag, 4 * sizeof(unsigned long long));      // the flag words and the placement words of a member
+}
+
+// model.py::_calc_diagnostics: t >= dt, t >= tavestart, tc % taveints == 0 — is an increment due before step t?
+inline bool diag_due(const qgx_model *m, int64_t t) {
+    return m->dg_every > 0 && t >= 1 && t >= m->dg_start && t % m->dg_every == 0;
+}
+
 // generator entry used by the stepper (generator.hip)
 // optional sampler update z <- a z + b xi folded into the generator's input kernel
 struct NoiseUpdate {

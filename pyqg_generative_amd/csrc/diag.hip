@@ -120,7 +120,7 @@ int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st)
     const size_t nr = (size_t)d.B * 2 * d.N * d.N;
     int rc;
     if ((rc = diag_ensure_alloc(m))) return rc;
-    double2 *qh = m->qh[m->cur_q];
+    double2 *qh = m->qh[m->bk.cur_q];
     double *p = m->dg_R[0], *xi = m->dg_R[1], *R3 = m->dg_R[2], *R4 = m->dg_R[3], *R5 = m->dg_R[4];
     double2 *xih = (double2 *)m->dg_S[0], *S3 = (double2 *)m->dg_S[1], *S4 = (double2 *)m->dg_S[2],
             *S5 = (double2 *)m->dg_S[3], *Sh = (double2 *)m->dg_S[4], *S6 = (double2 *)m->dg_S[5], *S7 = (double2 *)m->dg_S[6];
@@ -128,16 +128,15 @@ int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st)
     c.del1 = m->cfg.delta / (m->cfg.delta + 1.); c.del2 = 1. / (m->cfg.delta + 1.);
     c.rdm2 = pow(m->cfg.rd, -2.0); c.Udiff = m->cfg.U1 - m->cfg.U2; c.rek = m->cfg.rek;
     c.invM2 = d.invN2 * d.invN2; c.H0 = d.H[0] / d.Htot; c.H1 = d.H[1] / d.Htot;
-    {   // the AB coefficients of the step this increment precedes (kernel.pyx::_forward_timestep; model.hip::model_step_once)
-        const double dt = m->cfg.dt;
-        if (m->ablevel == 0) { c.dt1 = dt; c.dt2 = 0.0; c.dt3 = 0.0; }
-        else if (m->ablevel == 1) { c.dt1 = 1.5 * dt; c.dt2 = -0.5 * dt; c.dt3 = 0.0; }
-        else { c.dt1 = 23. / 12. * dt; c.dt2 = -16. / 12. * dt; c.dt3 = 5. / 12. * dt; }
-        c.invdt = 1.0 / dt;
+    {   // the AB coefficients of the step this increment precedes (model.hip::model_step_once)
+        double ab[3];
+        ab3_coefficients(m->bk.ablevel, m->cfg.dt, ab);
+        c.dt1 = ab[0]; c.dt2 = ab[1]; c.dt3 = ab[2];
+        c.invdt = 1.0 / m->cfg.dt;
     }
     c.nu = m->visc_on ? m->visc_nu : nullptr;      // the viscous term is part of the parameterization's tendency
     c.nu_pv = m->visc_pv;
-    const double2 *dq_p = m->dq[m->i_new], *dq_pp = m->dq[m->i_p];       // T_{n-1}, T_{n-2}
+    const double2 *dq_p = m->dq[m->bk.i_new], *dq_pp = m->dq[m->bk.i_p];       // T_{n-1}, T_{n-2}
     DiagAcc a;
     a.KEspec = m->dg_acc[0]; a.Ensspec = m->dg_acc[1]; a.entspec = m->dg_acc[2]; a.APEflux = m->dg_acc[3];
     a.KEflux = m->dg_acc[4]; a.APEgenspec = m->dg_acc[5]; a.KEfrictionspec = m->dg_acc[6]; a.paramspec = m->dg_acc[7];
@@ -153,8 +152,8 @@ int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st)
                            (const double2 *)m->ph, (const double2 *)S3, (const double2 *)S4, (const double2 *)S5,
                            S ? (const double2 *)Sh : (const double2 *)nullptr, (const double2 *)S6, (const double2 *)S7, dq_p, dq_pp, a);
         QGX_HIP(hipGetLastError());
-        m->uv_stale = false;
-        m->dg_count += 1;
+        m->bk.uv_stale = false;
+        m->bk.dg_count += 1;
         return QGX_OK;
     }
     if (m->small && m->opts.diag_fused && m->opts.diag_reg && small_diag_increment_reg_ok(d)) {
@@ -164,8 +163,8 @@ int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st)
         const bool halves = m->opts.diag_reg == 3 || (m->opts.diag_reg == 1 && 2 * d.B <= 256);
         rc = small_diag_increment_reg(d, c, qh, m->ph, S, weight, m->q, dq_p, dq_pp, a, st, halves);
         if (rc) return rc;
-        m->uv_stale = true;
-        m->dg_count += 1;
+        m->bk.uv_stale = true;
+        m->bk.dg_count += 1;
         return QGX_OK;
     }
     if (m->small && m->opts.diag_fused) {
@@ -173,8 +172,8 @@ int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st)
         // workgroup per member (spectral_small.hip::k_diag_small) instead of a dozen launches
         rc = small_diag_increment(d, c, qh, m->ph, m->u, m->v, p, xi, S3, S4, S5, Sh, S6, S7, S, weight, m->q, dq_p, dq_pp, a, st);
         if (rc) return rc;
-        m->uv_stale = false;
-        m->dg_count += 1;
+        m->bk.uv_stale = false;
+        m->bk.dg_count += 1;
         return QGX_OK;
     }
     if (!m->small && large_diag_fused_ok(m)) {
@@ -187,7 +186,7 @@ int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st)
             Shp = Sh;
         }
         if ((rc = large_diag_fused(m, c, qh, Shp, dq_p, dq_pp, a, st))) return rc;
-        m->dg_count += 1;
+        m->bk.dg_count += 1;
         return QGX_OK;
     }
     // _invert: ph, u, v of the current state
@@ -212,7 +211,7 @@ int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st)
                        (const double2 *)m->ph, (const double2 *)S3, (const double2 *)S4, (const double2 *)S5, Shp,
                        (const double2 *)S6, (const double2 *)S7, dq_p, dq_pp, a);
     QGX_HIP(hipGetLastError());
-    m->dg_count += 1;
+    m->bk.dg_count += 1;
     return QGX_OK;
 }
 
@@ -228,11 +227,12 @@ extern "C" int qgx_diag_config(qgx_model *m, int64_t start_step, int every) {
     return QGX_OK;
 }
 
-extern "C" int64_t qgx_diag_count(const qgx_model *m) { return m ? m->dg_count : -1; }
+extern "C" int64_t qgx_diag_count(const qgx_model *m) { return m ? m->bk.dg_count : -1; }
 
 extern "C" int qgx_diag_reset(qgx_model *m) {
     QGX_REQUIRE(m, "qgx_diag_reset: null model");
-    m->dg_count = 0;
+    m->bk.dg_count = 0;
+    m->team_undo.before.dg_count = 0;      // (no settle here: a pending run's undo record must not bring the old count back)
     if (m->dg_acc[0]) {
         const size_t ns = (size_t)m->B * 2 * m->N * m->NK, n2 = (size_t)m->B * m->N * m->NK;
         for (int i = 0; i < N_DIAGS; ++i) QGX_HIP(hipMemset(m->dg_acc[i], 0, (i < 2 ? ns : n2) * sizeof(double)));
@@ -243,10 +243,10 @@ extern "C" int qgx_diag_reset(qgx_model *m) {
 extern "C" int qgx_diag_get(qgx_model *m, int diag, double *out_dev, void *stream) {
     QGX_NEEDS_STATE(m, "qgx_diag_get");
     QGX_REQUIRE(m && out_dev && diag >= 0 && diag < N_DIAGS, "qgx_diag_get: bad argument");
-    QGX_REQUIRE(m->dg_count > 0 && m->dg_acc[0], "qgx_diag_get: no diagnostics accumulated yet");
+    QGX_REQUIRE(m->bk.dg_count > 0 && m->dg_acc[0], "qgx_diag_get: no diagnostics accumulated yet");
     const size_t n = (size_t)m->B * (diag < 2 ? 2 : 1) * m->N * m->NK;
     hipLaunchKernelGGL(k_diag_scale_copy, dim3(1024), dim3(256), 0, (hipStream_t)stream,
-                       (const double *)m->dg_acc[diag], out_dev, n, 1.0 / (double)m->dg_count);
+                       (const double *)m->dg_acc[diag], out_dev, n, 1.0 / (double)m->bk.dg_count);
     QGX_HIP(hipGetLastError());
     return QGX_OK;
 }

@@ -25,7 +25,6 @@ int large_qh_to_q(qgx_model *m, const double2 *qh, double *q, hipStream_t st);
 int large_invert(qgx_model *m, hipStream_t st);
 int large_step(qgx_model *m, const StepArgs &a, hipStream_t st);
 int large_ensure_q(qgx_model *m, hipStream_t st);
-int large_zpad();
 int large_team_available(qgx_model *m, hipStream_t st);
 int large_team_check(qgx_model *m, hipStream_t st, unsigned *flag);
 int large_team_steps(qgx_model *m, int K, int ablevel0, const double coef[3][3], const double2 *qh_src, double2 *qh_dst,
@@ -34,18 +33,18 @@ int large_team_steps(qgx_model *m, int K, int ablevel0, const double coef[3][3],
 // One _step_forward: AB3 coefficient schedule of kernel.pyx::_forward_timestep, history rotation.
 // the arguments of step n that do not depend on its forcing; advances the AB3 start-up level
 static void step_args_begin(qgx_model *m, int diag, StepArgs &a) {
-    const double dt = m->cfg.dt;
-    if (m->ablevel == 0) { a.dt1 = dt; a.dt2 = 0.0; a.dt3 = 0.0; m->ablevel = 1; }
-    else if (m->ablevel == 1) { a.dt1 = 1.5 * dt; a.dt2 = -0.5 * dt; a.dt3 = 0.0; m->ablevel = 2; }
-    else { a.dt1 = 23. / 12. * dt; a.dt2 = -16. / 12. * dt; a.dt3 = 5. / 12. * dt; }
+    double ab[3];
+    ab3_coefficients(m->bk.ablevel, m->cfg.dt, ab);
+    a.dt1 = ab[0]; a.dt2 = ab[1]; a.dt3 = ab[2];
+    if (m->bk.ablevel < 2) m->bk.ablevel += 1;
     // Slots after step n-1: i_new = T_{n-1}, i_p = T_{n-2}, i_pp = dead.  T_n goes to the dead slot.
-    a.qh_in = m->qh[m->cur_q];
-    a.qh_out = m->qh[m->cur_q ^ 1];
+    a.qh_in = m->qh[m->bk.cur_q];
+    a.qh_out = m->qh[m->bk.cur_q ^ 1];
     a.q = m->q;
     a.dqh = m->dqh;
-    a.dq_new = m->dq[m->i_pp];
-    a.dq_p = m->dq[m->i_new];
-    a.dq_pp = m->dq[m->i_p];
+    a.dq_new = m->dq[m->bk.i_pp];
+    a.dq_p = m->dq[m->bk.i_new];
+    a.dq_pp = m->dq[m->bk.i_p];
     a.ph = m->ph; a.u = m->u; a.v = m->v;
     a.diag = diag;
     a.nu = m->visc_on ? m->visc_nu : nullptr;
@@ -80,11 +79,11 @@ static int model_step_once(qgx_model *m, bool has_S, const double *S, double wei
         rc = m->small ? small_step(m->d, m->opts, a, st) : large_step(m, a, st);
     }
     if (rc) return rc;
-    const int dead = m->i_pp;
-    m->i_pp = m->i_p; m->i_p = m->i_new; m->i_new = dead;
-    m->cur_q ^= 1;
-    m->tc += 1;
-    m->uv_stale = diag == 0;
+    const int dead = m->bk.i_pp;
+    m->bk.i_pp = m->bk.i_p; m->bk.i_p = m->bk.i_new; m->bk.i_new = dead;
+    m->bk.cur_q ^= 1;
+    m->bk.tc += 1;
+    m->bk.uv_stale = diag == 0;
     return QGX_OK;
 }
 
@@ -93,20 +92,20 @@ static int model_step_once(qgx_model *m, bool has_S, const double *S, double wei
 // live buffers (qh[cur], dq[i_new], dq[i_p]) and writes only buffers that hold nothing live (qh[cur ^ 1], dq[i_pp],
 // dq[i_x]), and the bookkeeping before it is kept in team_undo until its flag word has been read back (team_settle).
 static int model_step_run(qgx_model *m, int K, hipStream_t st) {
-    const double dt = m->cfg.dt;
-    const double coef[3][3] = {{dt, 0.0, 0.0}, {1.5 * dt, -0.5 * dt, 0.0}, {23. / 12. * dt, -16. / 12. * dt, 5. / 12. * dt}};
-    qgx_model::TeamUndo &u = m->team_undo;
-    u.K = K; u.cur_q = m->cur_q; u.i_new = m->i_new; u.i_p = m->i_p; u.i_pp = m->i_pp; u.i_x = m->i_x;
-    u.tc = m->tc; u.ablevel = m->ablevel; u.uv_stale = m->uv_stale; u.q_stale = m->q_stale;
+    double coef[3][3];
+    for (int level = 0; level < 3; ++level) ab3_coefficients(level, m->cfg.dt, coef[level]);
+    m->team_undo.K = K;
+    m->team_undo.before = m->bk;
+    const StepBook &u = m->team_undo.before;
     // before: i_new = T_{n-1}, i_p = T_{n-2}; after: T_{n+K-1} in the old i_pp, T_{n+K-2} in the old spare slot
-    int rc = large_team_steps(m, K, m->ablevel, coef, m->qh[m->cur_q], m->qh[m->cur_q ^ 1], m->dq[m->i_new],
-                              m->dq[m->i_p], m->dq[m->i_pp], m->dq[m->i_x], st);
-    if (rc) { u.K = 0; return rc; }
-    m->i_new = u.i_pp; m->i_p = u.i_x; m->i_pp = u.i_new; m->i_x = u.i_p;
-    m->cur_q ^= 1;
-    m->tc += K;
-    m->ablevel = m->ablevel + K > 2 ? 2 : m->ablevel + K;
-    m->uv_stale = true;
+    int rc = large_team_steps(m, K, m->bk.ablevel, coef, m->qh[m->bk.cur_q], m->qh[m->bk.cur_q ^ 1], m->dq[m->bk.i_new],
+                              m->dq[m->bk.i_p], m->dq[m->bk.i_pp], m->dq[m->bk.i_x], st);
+    if (rc) { m->team_undo.K = 0; return rc; }
+    m->bk.i_new = u.i_pp; m->bk.i_p = u.i_x; m->bk.i_pp = u.i_new; m->bk.i_x = u.i_p;
+    m->bk.cur_q ^= 1;
+    m->bk.tc += K;
+    m->bk.ablevel = m->bk.ablevel + K > 2 ? 2 : m->bk.ablevel + K;
+    m->bk.uv_stale = true;
     return QGX_OK;
 }
 
@@ -126,8 +125,9 @@ static int team_settle(qgx_model *m, hipStream_t caller) {
     m->team_state = -1;
     m->team_replays += 1;
     QGX_REQUIRE(u.K > 0, "XCD-resident step kernel raised flag %u and left no undo record: the model state is undefined", flag);
-    m->cur_q = u.cur_q; m->i_new = u.i_new; m->i_p = u.i_p; m->i_pp = u.i_pp; m->i_x = u.i_x;
-    m->tc = u.tc; m->ablevel = u.ablevel; m->uv_stale = u.uv_stale; m->q_stale = u.q_stale;
+    // (the whole record, where only the fields a run changes used to be restored: a run is launched on plain steps alone, which
+    // touch none of the sampler fields, and every entry point that writes the record settles first or writes the undo record too)
+    m->bk = u.before;
     for (int s = 0; s < u.K; ++s)
         if ((rc = model_step_once(m, false, nullptr, 1.0, 0, 0, st))) return rc;
     // the entry point that settles may work on another stream than the run was launched on: what it enqueues next (a copy out
@@ -135,6 +135,8 @@ static int team_settle(qgx_model *m, hipStream_t caller) {
     if (caller != st) QGX_HIP(hipStreamSynchronize(st));
     return QGX_OK;
 }
+
+#define QGX_SETTLE(m, st) do { if (int trc_ = team_settle(m, st)) return trc_; } while (0)
 
 static bool factor_radices(int N, int *rad, int &nrad) {
     // the same greedy plan as the device's compile-time pick_radix (fft_lds.hpp)
@@ -320,7 +322,7 @@ extern "C" int qgx_create(const qgx_config *cfg, qgx_model **out) {
     m->small = small_path_fits(N);
     if (m->small) rc = small_prepare(d);
     else {
-        rc = dalloc(m->zbuf, (size_t)B * 3 * (N + large_zpad()) * N);   // 3 complex work fields per member (spectral_large.hip ZF), padded rows
+        rc = dalloc(m->zbuf, (size_t)B * ZF * (N + large_zpad()) * N);   // complex work fields of padded rows (spectral_large.hip)
         if (!rc) rc = large_prepare(d);
     }
     if (rc) { qgx_destroy(m); return rc; }
@@ -331,15 +333,9 @@ extern "C" int qgx_create(const qgx_config *cfg, qgx_model **out) {
 extern "C" int qgx_destroy(qgx_model *m) {
     if (!m) return QGX_OK;
     (void)hipSetDevice(m->cfg.device);
-    void *ptrs[] = {m->t_filtr, m->t_wv2, m->t_a, m->t_kk, m->t_ll, m->t_tw, m->t_pos, m->q, m->u, m->v,
-                    m->S, m->qh[0], m->qh[1], m->ph, m->dqh, m->dq[0], m->dq[1], m->dq[2], m->dq[3], m->dg_z, m->zbuf, m->team_ctl,
-                    m->z, m->xi, m->visc_nu, m->bs_const, m->bs_spec[0], m->bs_spec[1], m->bs_spec[2],
-                    m->bs_real[0], m->bs_real[1], m->bs_real[2]};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (double *p : m->dg_R) if (p) (void)hipFree(p);
-    for (double *p : m->dg_S) if (p) (void)hipFree(p);
-    for (double *p : m->dg_acc) if (p) (void)hipFree(p);
-    if (m->sib_flag) (void)hipFree(m->sib_flag);
+    for_each_member_buffer(*m, sizeof(double), [](auto *p, size_t) { if (p) (void)hipFree(p); });
+    void *rest[] = {m->t_filtr, m->t_wv2, m->t_a, m->t_kk, m->t_ll, m->t_tw, m->t_pos, m->team_ctl};   // no member axis
+    for (void *p : rest) if (p) (void)hipFree(p);
     for (hipStream_t sst : m->adv_stream) if (sst) (void)hipStreamDestroy(sst);
     for (auto &evs : m->adv_event) for (hipEvent_t ev : evs) if (ev) (void)hipEventDestroy(ev);
     for (hipStream_t sst : m->sub_stream) if (sst) (void)hipStreamDestroy(sst);
@@ -355,16 +351,16 @@ extern "C" size_t qgx_field_bytes(const qgx_model *m, int field) {
         case QGX_F_Q: case QGX_F_U: case QGX_F_V: case QGX_F_S: case QGX_F_P: return nr * sizeof(double);
         case QGX_F_QH: case QGX_F_PH: case QGX_F_DQHDT: case QGX_F_DQHDT_P: case QGX_F_DQHDT_PP:
             return ns * sizeof(double2);
-        case QGX_F_Z: return nr * (m->z_double ? sizeof(double) : sizeof(float));
+        case QGX_F_Z: return nr * (m->bk.z_double ? sizeof(double) : sizeof(float));
         default: return 0;
     }
 }
 
 extern "C" int qgx_get(qgx_model *m, int field, void *out_dev, void *stream) {
     QGX_NEEDS_STATE(m, "qgx_get");
-    { int trc = team_settle(m, (hipStream_t)stream); if (trc) return trc; }
+    QGX_SETTLE(m, (hipStream_t)stream);
     QGX_REQUIRE(m && out_dev, "qgx_get: null argument");
-    if (m->uv_stale && (field == QGX_F_U || field == QGX_F_V || field == QGX_F_PH || field == QGX_F_P)) {
+    if (m->bk.uv_stale && (field == QGX_F_U || field == QGX_F_V || field == QGX_F_PH || field == QGX_F_P)) {
         // the steps since the last refresh stored no ph, u, v (refresh_diag == 0, every step of a run kernel): hand out
         // the fields of the CURRENT state rather than those of an older one (as qgx_status_ke_cfl does)
         int irc = qgx_invert(m, stream);
@@ -380,12 +376,12 @@ extern "C" int qgx_get(qgx_model *m, int field, void *out_dev, void *stream) {
         case QGX_F_U: src = m->u; break;
         case QGX_F_V: src = m->v; break;
         case QGX_F_S: src = m->S; break;
-        case QGX_F_QH: src = m->qh[m->cur_q]; break;
+        case QGX_F_QH: src = m->qh[m->bk.cur_q]; break;
         case QGX_F_PH: src = m->ph; break;
-        case QGX_F_DQHDT: src = m->dq[m->i_new]; break;
+        case QGX_F_DQHDT: src = m->dq[m->bk.i_new]; break;
         // kernel.pyx rotates by copy: after a step dqhdt_p == dqhdt and dqhdt_pp is the previous one
-        case QGX_F_DQHDT_P: src = m->dq[m->i_new]; break;
-        case QGX_F_DQHDT_PP: src = m->dq[m->i_p]; break;
+        case QGX_F_DQHDT_P: src = m->dq[m->bk.i_new]; break;
+        case QGX_F_DQHDT_PP: src = m->dq[m->bk.i_p]; break;
         case QGX_F_Z: src = m->z; break;
         default: QGX_REQUIRE(false, "qgx_get: unknown field %d", field);
     }
@@ -411,30 +407,30 @@ extern "C" int qgx_get_table(qgx_model *m, int table, double *out) {
 extern "C" int qgx_set_q(qgx_model *m, const double *q_dev, void *stream) {
     QGX_NEEDS_STATE(m, "qgx_set_q");
     QGX_REQUIRE(m && q_dev, "qgx_set_q: null argument");
-    { int trc = team_settle(m, (hipStream_t)stream); if (trc) return trc; }
+    QGX_SETTLE(m, (hipStream_t)stream);
     hipStream_t st = (hipStream_t)stream;
     QGX_HIP(hipMemcpyAsync(m->q, q_dev, qgx_field_bytes(m, QGX_F_Q), hipMemcpyDeviceToDevice, st));
-    m->q_stale = false;
-    return m->small ? small_q_to_qh(m->d, m->opts, m->q, m->qh[m->cur_q], st) : large_q_to_qh(m, m->q, m->qh[m->cur_q], st);
+    m->bk.q_stale = false;
+    return m->small ? small_q_to_qh(m->d, m->opts, m->q, m->qh[m->bk.cur_q], st) : large_q_to_qh(m, m->q, m->qh[m->bk.cur_q], st);
 }
 
 extern "C" int qgx_set_qh(qgx_model *m, const double *qh_dev, void *stream) {
     QGX_NEEDS_STATE(m, "qgx_set_qh");
     QGX_REQUIRE(m && qh_dev, "qgx_set_qh: null argument");
-    { int trc = team_settle(m, (hipStream_t)stream); if (trc) return trc; }
+    QGX_SETTLE(m, (hipStream_t)stream);
     hipStream_t st = (hipStream_t)stream;
-    QGX_HIP(hipMemcpyAsync(m->qh[m->cur_q], qh_dev, qgx_field_bytes(m, QGX_F_QH), hipMemcpyDeviceToDevice, st));
-    m->q_stale = false;
-    return m->small ? small_qh_to_q(m->d, m->opts, m->qh[m->cur_q], m->q, st) : large_qh_to_q(m, m->qh[m->cur_q], m->q, st);
+    QGX_HIP(hipMemcpyAsync(m->qh[m->bk.cur_q], qh_dev, qgx_field_bytes(m, QGX_F_QH), hipMemcpyDeviceToDevice, st));
+    m->bk.q_stale = false;
+    return m->small ? small_qh_to_q(m->d, m->opts, m->qh[m->bk.cur_q], m->q, st) : large_qh_to_q(m, m->qh[m->bk.cur_q], m->q, st);
 }
 
 extern "C" int qgx_invert(qgx_model *m, void *stream) {
     QGX_NEEDS_STATE(m, "qgx_invert");
-    { int trc = team_settle(m, (hipStream_t)stream); if (trc) return trc; }
+    QGX_SETTLE(m, (hipStream_t)stream);
     QGX_REQUIRE(m, "qgx_invert: null model");
     hipStream_t st = (hipStream_t)stream;
-    m->uv_stale = false;
-    return m->small ? small_invert(m->d, m->opts, m->qh[m->cur_q], m->ph, m->u, m->v, st) : large_invert(m, st);
+    m->bk.uv_stale = false;
+    return m->small ? small_invert(m->d, m->opts, m->qh[m->bk.cur_q], m->ph, m->u, m->v, st) : large_invert(m, st);
 }
 
 // kernel-path switches (ModelOpts, common.hpp): cross-checks and A/B timing; every combination computes the same step
@@ -478,7 +474,7 @@ extern "C" int qgx_set_option(qgx_model *m, const char *name, int value) {
     return QGX_OK;
 }
 
-extern "C" int64_t qgx_step_count(const qgx_model *m) { return m ? m->tc : -1; }
+extern "C" int64_t qgx_step_count(const qgx_model *m) { return m ? m->bk.tc : -1; }
 extern "C" int qgx_run_kernel_state(const qgx_model *m) { return m ? m->team_state : 0; }
 
 // Laplace(nu, PV) of pyqg_generative/tools/simulate.py:207-225 inside every step (spectral_elem.hpp::visc_add)
@@ -490,7 +486,7 @@ extern "C" int qgx_set_viscosity(qgx_model *m, const double *nu_host, int pv, vo
             QGX_REQUIRE(std::isfinite(nu_host[b]) && nu_host[b] >= 0.0, "qgx_set_viscosity: nu of member %d is %g (finite and >= 0 required)",
                         b, nu_host[b]);
     hipStream_t st = (hipStream_t)stream;
-    { int trc = team_settle(m, st); if (trc) return trc; }      // a pending run reads the array it was launched with
+    QGX_SETTLE(m, st);      // a pending run reads the array it was launched with
     if (!nu_host) { m->visc_on = false; m->visc_pv = 0; return QGX_OK; }
     if (!m->visc_nu) QGX_HIP(hipMalloc((void **)&m->visc_nu, (size_t)m->B * sizeof(double)));
     // ordered behind the steps already enqueued on `stream`; the caller's array is free on return
@@ -525,7 +521,7 @@ extern "C" int qgx_set_backscatter(qgx_model *m, const double *smag_host, const 
         }
     }
     hipStream_t st = (hipStream_t)stream;
-    { int trc = team_settle(m, st); if (trc) return trc; }
+    QGX_SETTLE(m, st);
     if (!smag_host) { m->bs_on = false; return QGX_OK; }
     if (!m->bs_const) QGX_HIP(hipMalloc((void **)&m->bs_const, (size_t)2 * m->B * sizeof(double)));
     { int prc = backscatter_prepare(m); if (prc) return prc; }
@@ -555,15 +551,15 @@ extern "C" int qgx_backscatter_forcing(qgx_model *m, double *S_dev, double *rati
     QGX_NEEDS_STATE(m, "qgx_backscatter_forcing");
     QGX_REQUIRE(m && S_dev, "qgx_backscatter_forcing: null argument");
     QGX_REQUIRE(m->bs_on, "qgx_backscatter_forcing: the closure is off (qgx_set_backscatter)");
-    { int trc = team_settle(m, (hipStream_t)stream); if (trc) return trc; }
-    return backscatter_eval(m, m->qh[m->cur_q], S_dev, ratio_dev, (hipStream_t)stream);
+    QGX_SETTLE(m, (hipStream_t)stream);
+    return backscatter_eval(m, m->qh[m->bk.cur_q], S_dev, ratio_dev, (hipStream_t)stream);
 }
 
 extern "C" int qgx_reset_time(qgx_model *m) {
     QGX_NEEDS_STATE(m, "qgx_reset_time");
     QGX_REQUIRE(m, "qgx_reset_time: null model");
-    { int trc = team_settle(m, nullptr); if (trc) return trc; }
-    m->tc = 0; m->ablevel = 0; m->have_noise = false; m->const_counter = 0; m->have_forcing = false;
+    QGX_SETTLE(m, nullptr);
+    m->bk.tc = 0; m->bk.ablevel = 0; m->bk.have_noise = false; m->bk.const_counter = 0; m->bk.have_forcing = false;
     const size_t ns = (size_t)m->B * 2 * m->N * m->NK;
     for (int i = 0; i < 4; ++i) if (m->dq[i]) QGX_HIP(hipMemset(m->dq[i], 0, ns * sizeof(double2)));
     return QGX_OK;
@@ -571,9 +567,9 @@ extern "C" int qgx_reset_time(qgx_model *m) {
 
 extern "C" int qgx_status_ke_cfl(qgx_model *m, double *out_dev, void *stream) {
     QGX_NEEDS_STATE(m, "qgx_status_ke_cfl");
-    { int trc = team_settle(m, (hipStream_t)stream); if (trc) return trc; }
+    QGX_SETTLE(m, (hipStream_t)stream);
     QGX_REQUIRE(m && out_dev, "qgx_status_ke_cfl: null argument");
-    if (m->uv_stale) {
+    if (m->bk.uv_stale) {
         // the steps since the last refresh stored no ph, u, v: a status of stale (or never written) fields would be
         // meaningless, so the CURRENT state is inverted first (pyqg reports the fields of its last _invert, one step back)
         int irc = qgx_invert(m, stream);
@@ -607,195 +603,187 @@ static int step_adv_ensure(qgx_model *m) {
     return QGX_OK;
 }
 
-// what a deterministic-sampling step refuses, with no HIP call and no write to the model
-static int step_mean_check(const qgx_model *m, const qgx_param *p) {
-    QGX_REQUIRE(p->n_mean >= 1, "qgx_step: deterministic sampling needs n_mean >= 1 realisations (n_mean = %d)", p->n_mean);
-    QGX_REQUIRE(!p->z_external_dev, "qgx_step: deterministic sampling draws its own realisations (z_external_dev)");
-    return generator_mean_check(p->gen, m->B, m->N, p->n_mean, m->opts.mean_chunk, m->noise_step);
-}
-
 // ---- the stepping loop: pyqg model.py::_step_forward with the plugin call of
 // pyqg_generative/models/parameterization.py:23-34 and samplers of stochastic_pyqg.py:30-72
-// the steps of one call on one stream, for the whole ensemble or for one half of it (qgx_step below)
-static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_diag, hipStream_t st) {
-    const int N = m->N, B = m->B;
-    if (p && p->gen) {
-        QGX_REQUIRE(p->sampling == QGX_SAMPLING_AR1 || p->sampling == QGX_SAMPLING_CONSTANT || p->sampling == QGX_SAMPLING_DETERMINISTIC,
-                    "qgx_step: unknown sampling %d", p->sampling);
-        if (p->sampling == QGX_SAMPLING_DETERMINISTIC) {
-            // (qgx_step asked all of this before anything was touched; a half-way refusal cannot happen here)
-            if (nsteps > 0) { if (const int drc = step_mean_check(m, p)) return drc; }
-        } else {
-            QGX_REQUIRE(!(p->sampling == QGX_SAMPLING_CONSTANT && p->nsteps < 1),
-                        "qgx_step: constant sampler needs nsteps >= 1");
-            QGX_REQUIRE(p->nsteps != 0, "qgx_step: nsteps == 0 is not a valid decorrelation time");
-            QGX_REQUIRE(!(p->z_external_dev && nsteps != 1), "qgx_step: external noise needs nsteps_to_run == 1");
-            QGX_REQUIRE(!(p->z_external_dev && !generator_takes_noise(p->gen)),
-                        "qgx_step: an OLS or ANN generator takes no latent noise (z_external_dev)");
-            m->z_double = generator_noise_is_double(p->gen);      // (deterministic sampling leaves the sampler state alone)
-        }
+// what the forcing source of one step hands to model_step_once
+struct StepForcing {
+    bool has_S = false;
+    const double *S = nullptr;
+    double weight = 1.0;
+    int demean = 0;                 // de-mean inside the step kernel
+    GenFuse gf;                     // work the step kernel does on the generator's behalf, if any of it is set
+    StepArgs pre;                   // have_pre: the step's first half is in flight on the side stream with these arguments,
+    bool have_pre = false;          //   and the AB3 level stood at ablevel_before when it was launched
+    int ablevel_before = 0;
+};
+
+// Run-kernel stretch: how many steps from step s of the call go to the XCD-resident kernel in one launch (0: none) — up to the
+// step that refreshes (psi, u, v), no diagnostics increment due inside it (one due before it is the loop's), at least team_min
+static int run_stretch(const qgx_model *m, int s, int nsteps, int refresh_diag) {
+    const int last = refresh_diag ? nsteps - 1 : nsteps;
+    int K = 0;
+    while (s + K < last && !(K > 0 && diag_due(m, m->bk.tc + K))) ++K;
+    return K >= m->opts.team_min ? K : 0;
+}
+
+// Unwinds the first half of a step that will not be completed.  It wrote a dead tendency slot only: the state is that of step
+// n - 1 once the side stream is joined (behind its event, or by waiting for it here) and the AB3 level is taken back
+enum FirstHalfJoin { JOIN_NOTHING, JOIN_EVENT, JOIN_SYNC };
+static void first_half_unwind(qgx_model *m, const StepForcing &f, hipStream_t st, FirstHalfJoin how) {
+    if (how == JOIN_EVENT) (void)hipStreamWaitEvent(st, m->adv_event[m->adv_slot][1], 0);
+    if (how == JOIN_SYNC) (void)hipStreamSynchronize(m->adv_stream[m->adv_slot]);
+    m->bk.ablevel = f.ablevel_before;
+}
+
+// The half of the step kernel that needs nothing of the forcing (inversion, advection products, their transform, the tendency
+// without its forcing term) on the side stream, under the generator's layers: on an ensemble that leaves CUs idle the step
+// is a chain of dependent launches, and this takes two of the step kernel's four transforms out of it.
+static int first_half_launch(qgx_model *m, hipStream_t st, StepForcing &f) {
+    const int sl = m->adv_slot;
+    f.ablevel_before = m->bk.ablevel;
+    step_args_begin(m, 0, f.pre);
+    hipError_t e = hipEventRecord(m->adv_event[sl][0], st);
+    if (e == hipSuccess) e = hipStreamWaitEvent(m->adv_stream[sl], m->adv_event[sl][0], 0);
+    if (e != hipSuccess) { first_half_unwind(m, f, st, JOIN_NOTHING); QGX_HIP(e); }
+    const int arc = small_step(m->d, m->opts, f.pre, m->adv_stream[sl], 1);
+    e = hipEventRecord(m->adv_event[sl][1], m->adv_stream[sl]);
+    if (arc || e != hipSuccess) {
+        first_half_unwind(m, f, st, JOIN_SYNC);
+        if (arc) return arc;
+        QGX_HIP(e);
     }
-    const bool det = p && p->gen && p->sampling == QGX_SAMPLING_DETERMINISTIC;
+    f.have_pre = true;
+    return QGX_OK;
+}
+
+// Forcing source, deterministic sampling (parameterization.py:27-28): the de-meaned mean of n_mean realisations for the current
+// PV on every step; never deferred into the step kernel, no next-input epilogue; z, have_noise, const_counter are not touched
+static int forcing_mean(qgx_model *m, const qgx_param *p, hipStream_t st, StepForcing &f) {
+    if (!m->small) { int qrc = large_ensure_q(m, st); if (qrc) return qrc; }
+    int rc = generator_forward_mean(p->gen, m->q, m->S, m->B, m->N, p->n_mean, m->opts.mean_chunk, p->demean, p->seed,
+                                    p->member_offset, m->bk.noise_step, st);
+    if (rc) return rc;
+    m->bk.noise_step += 1;
+    m->bk.have_forcing = true;
+    f.has_S = true; f.S = m->S; f.weight = p->weight;
+    return QGX_OK;
+}
+
+// Forcing source: a generator behind the AR1 or the constant sampler (step s of nsteps; diag_now: the step refreshes psi, u, v)
+static int forcing_sampled(qgx_model *m, const qgx_param *p, int s, int nsteps, int diag_now, hipStream_t st, StepForcing &f) {
+    StepBook &k = m->bk;
     // OLS (generate_latent_noise returns 0, ols_model.py:65-66): the sampler only decides when the forcing is recomputed —
     // AR1 on every step, constant on steps 1, n+1, 2n+1, ... (stochastic_pyqg.py:30-72) — with no draw and no write to z
-    const bool noisy = p && p->gen && generator_takes_noise(p->gen);
+    const bool noisy = generator_takes_noise(p->gen);
+    const bool fusable = m->opts.genfuse != 0 && m->small && small_layer_split(m->d, m->opts) && !k.z_double;
+    bool compute = true, draw = true;
+    double a = 0.0, b = 1.0;
+    if (p->sampling == QGX_SAMPLING_AR1) {
+        if (k.have_noise) {
+            if (p->nsteps > 0) {
+                a = 1.0 - 1.0 / p->nsteps;
+                b = sqrt(1.0 / p->nsteps * (2.0 - 1.0 / p->nsteps));
+            } else { a = 1.0; b = 0.0; }
+        }
+    } else {
+        if (k.have_noise) {
+            if (k.const_counter % p->nsteps == 0) k.const_counter = 1;
+            else { k.const_counter += 1; compute = false; draw = false; }
+        } else k.const_counter = 1;
+    }
+    NoiseUpdate nu;
+    if (draw) {
+        nu.xi_ext = p->z_external_dev; nu.seed = p->seed; nu.member_offset = p->member_offset;
+        nu.step = k.noise_step; nu.a = a; nu.b = b;
+        k.noise_step += 1;
+        k.have_noise = true;
+    }
+    if (compute) {
+        if (!m->small) { int qrc = large_ensure_q(m, st); if (qrc) return qrc; }
+        const bool due = diag_due(m, k.tc);
+        // the first half on the side stream: not on steps that refresh (psi, u, v) or increment the diagnostics
+        if (step_adv_applies(m) && !diag_now && !due) { if (int arc = first_half_launch(m, st, f)) return arc; }
+        // Small grids in layer-split form, GAN / VAE / OLS: the generator's output kernel rides in the step kernel's
+        // prologue (unless this step's diagnostics need S first) and the next step's input kernel in its epilogue
+        // (below; GenFuse, common.hpp)
+        const bool input_ready = fusable && draw && k.x_ready_gen == (const void *)p->gen && k.x_ready_step == nu.step;
+        k.x_ready_gen = nullptr;
+        // a redraw always comes with a recompute; the sampler update rides in the input kernel (OLS: nothing to draw)
+        int rc = generator_forward(p->gen, m->q, noisy ? m->z : nullptr, m->S, m->B, m->N, p->demean, st,
+                                   draw && noisy ? &nu : nullptr, fusable && !due ? &f.gf : nullptr, input_ready);
+        if (rc) {
+            if (f.have_pre) first_half_unwind(m, f, st, JOIN_EVENT);
+            return rc;
+        }
+        k.have_forcing = true;
+    }
+    // the next step's input in this step kernel's epilogue, more steps to come in this call: GAN / VAE when it draws
+    // white-in-time Philox noise (a draw on every step); OLS whenever the next step recomputes the forcing (AR1: every
+    // step; constant: the step after the counter reached nsteps) — also behind a step that holds its forcing.  ANN: never,
+    // its kernel reads q itself (ann.hip)
+    const bool next_input = generator_reads_q(p->gen) ? false
+                          : noisy ? (p->nsteps == 1)
+                                  : (p->sampling == QGX_SAMPLING_AR1 || k.const_counter % p->nsteps == 0);
+    if (fusable && next_input && !p->z_external_dev && s + 1 < nsteps) {
+        if (int rc = generator_input_info(p->gen, m->B, m->N, &f.gf)) {
+            if (f.have_pre) first_half_unwind(m, f, st, JOIN_EVENT);
+            return rc;
+        }
+        if (noisy) {
+            f.gf.z = (float *)m->z; f.gf.b = 1.f;
+            f.gf.seed = p->seed; f.gf.member_offset = p->member_offset; f.gf.step = k.noise_step;
+        }
+        k.x_ready_gen = p->gen; k.x_ready_step = k.noise_step;
+    }
+    f.has_S = k.have_forcing; f.S = m->S; f.weight = p->weight;
+    return QGX_OK;
+}
+
+// Forcing source: the caller's field, de-meaned inside the step kernel if asked
+static void forcing_external(const qgx_param *p, StepForcing &f) {
+    f.has_S = true; f.S = p->forcing_dev; f.weight = p->weight; f.demean = p->demean;
+}
+
+// Forcing source: the backscatter closure of the current state (pyqg calls a q-parameterization behind _invert): weight 1,
+// and no de-mean — its spectrum has no (0, 0) element
+static int forcing_backscatter(qgx_model *m, hipStream_t st, StepForcing &f) {
+    f.has_S = true; f.S = m->S;
+    return backscatter_eval(m, m->qh[m->bk.cur_q], m->S, nullptr, st);
+}
+
+// the steps of one call on one stream, for the whole ensemble or for one half of it (qgx_step below, which has checked the
+// arguments: step_check): settle, a run-kernel stretch or one step's forcing, the diagnostics increment if due, the step
+static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_diag, hipStream_t st) {
+    const bool gen = p && p->gen, det = gen && p->sampling == QGX_SAMPLING_DETERMINISTIC;
+    if (gen && !det) m->bk.z_double = generator_noise_is_double(p->gen);      // (deterministic sampling leaves the sampler state alone)
     // (a model with molecular viscosity steps on the three-launch path at 256 x 256 as well: the run kernel holds a member's
     // state in all 256 registers of its waves, and its instance with the viscous term spilled — DESIGN.md section 3.12)
     // (so does a model with the backscatter closure: its forcing is recomputed from the state on every step)
     const bool plain = !(p && (p->gen || p->forcing_dev)) && !m->visc_on && !m->bs_on;
-    const bool fuse_ok = m->opts.genfuse != 0;
-    m->x_ready_gen = nullptr;                                            // an assembled input never outlives its call
+    m->bk.x_ready_gen = nullptr;                                            // an assembled input never outlives its call
     for (int s = 0; s < nsteps; ++s) {
-        { int trc = team_settle(m, st); if (trc) return trc; }              // at most one run is ever unsettled
-        if (plain && !m->small && large_team_available(m, st)) {
-            // a run of steps with no diagnostics increment due inside it and no (u, v, psi) refresh asked of it
-            const bool due = m->dg_every > 0 && m->tc >= 1 && m->tc >= m->dg_start && m->tc % m->dg_every == 0;
-            int K = 0;
-            const int last = refresh_diag ? nsteps - 1 : nsteps;          // the refreshing step takes the three-launch path
-            while (s + K < last) {
-                const int64_t t = m->tc + K;
-                if (K > 0 && m->dg_every > 0 && t >= 1 && t >= m->dg_start && t % m->dg_every == 0) break;
-                ++K;
-            }
-            const int kmin = m->opts.team_min;
-            if (K >= kmin) {
-                if (due) { int drc = diag_increment(m, nullptr, 1.0, st); if (drc) return drc; }
-                int rc = model_step_run(m, K, st);
-                if (rc) return rc;
-                s += K - 1;
-                continue;
-            }
+        QGX_SETTLE(m, st);              // at most one run is ever unsettled
+        const int K = plain && !m->small && large_team_available(m, st) ? run_stretch(m, s, nsteps, refresh_diag) : 0;
+        const int diag_now = (!K && refresh_diag && s == nsteps - 1) ? 1 : 0;
+        StepForcing f;
+        int rc = QGX_OK;
+        if (K) {}                                                        // (plain steps: no forcing)
+        else if (det) rc = forcing_mean(m, p, st, f);
+        else if (gen) rc = forcing_sampled(m, p, s, nsteps, diag_now, st, f);
+        else if (p && p->forcing_dev) forcing_external(p, f);
+        else if (m->bs_on) rc = forcing_backscatter(m, st, f);
+        if (rc) return rc;
+        // (before the time step; never while a first half is in flight: forcing_sampled launches none on such a step)
+        if (diag_due(m, m->bk.tc) && (rc = diag_increment(m, f.has_S ? f.S : nullptr, f.weight, st))) return rc;
+        if (K) {
+            if ((rc = model_step_run(m, K, st))) return rc;
+            s += K - 1;
+            continue;
         }
-        bool has_S = false;
-        const double *S = nullptr;
-        double weight = 1.0;
-        int demean_in_kernel = 0;
-        GenFuse gf;
-        bool use_gf = false;
-        const int diag_now = (refresh_diag && s == nsteps - 1) ? 1 : 0;
-        StepArgs pre;
-        bool have_pre = false;
-        int ablevel_before = m->ablevel;
-        if (det) {
-            // parameterization.py:27-28: the de-meaned mean of n_mean realisations for the current PV, recomputed on every step;
-            // never deferred into the step kernel, no next-input epilogue; z, have_noise and const_counter are not touched
-            weight = p->weight;
-            if (!m->small) { int qrc = large_ensure_q(m, st); if (qrc) return qrc; }
-            int rc = generator_forward_mean(p->gen, m->q, m->S, B, N, p->n_mean, m->opts.mean_chunk, p->demean, p->seed,
-                                            p->member_offset, m->noise_step, st);
-            if (rc) return rc;
-            m->noise_step += 1;
-            m->have_forcing = true;
-            has_S = true;
-            S = m->S;
-        } else if (p && p->gen) {
-            weight = p->weight;
-            bool compute = true;
-            double a = 0.0, b = 1.0;
-            bool draw = true;
-            const bool fusable = fuse_ok && m->small && small_layer_split(m->d, m->opts) && !m->z_double;
-            if (p->sampling == QGX_SAMPLING_AR1) {
-                if (m->have_noise) {
-                    if (p->nsteps > 0) {
-                        a = 1.0 - 1.0 / p->nsteps;
-                        b = sqrt(1.0 / p->nsteps * (2.0 - 1.0 / p->nsteps));
-                    } else { a = 1.0; b = 0.0; }
-                }
-            } else {
-                if (m->have_noise) {
-                    if (m->const_counter % p->nsteps == 0) m->const_counter = 1;
-                    else { m->const_counter += 1; compute = false; draw = false; }
-                } else m->const_counter = 1;
-            }
-            NoiseUpdate nu;
-            if (draw) {
-                nu.xi_ext = p->z_external_dev; nu.seed = p->seed; nu.member_offset = p->member_offset;
-                nu.step = m->noise_step; nu.a = a; nu.b = b;
-                m->noise_step += 1;
-                m->have_noise = true;
-            }
-            if (compute) {
-                if (!m->small) { int qrc = large_ensure_q(m, st); if (qrc) return qrc; }
-                // The half of the step kernel that needs nothing of the forcing (inversion, advection products, their
-                // transform, the tendency without its forcing term) on the side stream, under the generator's layers: on an
-                // ensemble that leaves CUs idle the step is a chain of dependent launches, and this takes two of the step
-                // kernel's four transforms out of it.  Not on steps that refresh (psi, u, v) or increment the diagnostics.
-                if (step_adv_applies(m) && !diag_now &&
-                    !(m->dg_every > 0 && m->tc >= 1 && m->tc >= m->dg_start && m->tc % m->dg_every == 0)) {
-                    const int sl = m->adv_slot;
-                    ablevel_before = m->ablevel;
-                    step_args_begin(m, 0, pre);
-                    hipError_t e = hipEventRecord(m->adv_event[sl][0], st);
-                    if (e == hipSuccess) e = hipStreamWaitEvent(m->adv_stream[sl], m->adv_event[sl][0], 0);
-                    if (e != hipSuccess) { m->ablevel = ablevel_before; QGX_HIP(e); }
-                    int arc = small_step(m->d, m->opts, pre, m->adv_stream[sl], 1);
-                    // (whatever was enqueued on the side stream is joined below on every path)
-                    e = hipEventRecord(m->adv_event[sl][1], m->adv_stream[sl]);
-                    if (arc || e != hipSuccess) {
-                        (void)hipStreamSynchronize(m->adv_stream[sl]);
-                        m->ablevel = ablevel_before;
-                        if (arc) return arc;
-                        QGX_HIP(e);
-                    }
-                    have_pre = true;
-                }
-                // Small grids in layer-split form, GAN / VAE / OLS: the generator's output kernel rides in the step kernel's
-                // prologue (unless this step's diagnostics need S first) and the next step's input kernel in its epilogue
-                // (below; GenFuse, common.hpp)
-                const bool diag_due = m->dg_every > 0 && m->tc >= 1 && m->tc >= m->dg_start && m->tc % m->dg_every == 0;
-                const bool input_ready = fusable && draw && m->x_ready_gen == (const void *)p->gen && m->x_ready_step == nu.step;
-                m->x_ready_gen = nullptr;
-                // a redraw always comes with a recompute; the sampler update rides in the input kernel (OLS: nothing to draw)
-                int rc = generator_forward(p->gen, m->q, noisy ? m->z : nullptr, m->S, B, N, p->demean, st,
-                                           draw && noisy ? &nu : nullptr, fusable && !diag_due ? &gf : nullptr, input_ready);
-                if (rc) {
-                    if (have_pre) {        // the first half wrote a dead tendency slot only: the state is that of step n - 1
-                        (void)hipStreamWaitEvent(st, m->adv_event[m->adv_slot][1], 0);
-                        m->ablevel = ablevel_before;
-                    }
-                    return rc;
-                }
-                m->have_forcing = true;
-            }
-            // the next step's input in this step kernel's epilogue, more steps to come in this call: GAN / VAE when it draws
-            // white-in-time Philox noise (a draw on every step); OLS whenever the next step recomputes the forcing (AR1: every
-            // step; constant: the step after the counter reached nsteps) — also behind a step that holds its forcing.  ANN: never,
-            // its kernel reads q itself (ann.hip)
-            const bool next_input = generator_reads_q(p->gen) ? false
-                                  : noisy ? (p->nsteps == 1)
-                                          : (p->sampling == QGX_SAMPLING_AR1 || m->const_counter % p->nsteps == 0);
-            if (fusable && next_input && !p->z_external_dev && s + 1 < nsteps) {
-                if (int rc = generator_input_info(p->gen, B, N, &gf)) return rc;
-                if (noisy) {
-                    gf.z = (float *)m->z; gf.b = 1.f;
-                    gf.seed = p->seed; gf.member_offset = p->member_offset; gf.step = m->noise_step;
-                }
-                m->x_ready_gen = p->gen; m->x_ready_step = m->noise_step;
-            }
-            use_gf = gf.y != nullptr || gf.X != nullptr;
-            has_S = m->have_forcing;
-            S = m->S;
-        } else if (p && p->forcing_dev) {
-            has_S = true;
-            S = p->forcing_dev;
-            weight = p->weight;
-            demean_in_kernel = p->demean;
-        } else if (m->bs_on) {
-            // the backscatter closure of the current state (pyqg calls a q-parameterization behind _invert): weight 1, and no
-            // de-mean — its spectrum has no (0, 0) element
-            int rc = backscatter_eval(m, m->qh[m->cur_q], m->S, nullptr, st);
-            if (rc) return rc;
-            has_S = true;
-            S = m->S;
-        }
-        // model.py::_calc_diagnostics: t >= dt, t >= tavestart, tc % taveints == 0 (before the time step)
-        if (m->dg_every > 0 && m->tc >= 1 && m->tc >= m->dg_start && m->tc % m->dg_every == 0) {
-            int drc = diag_increment(m, has_S ? S : nullptr, weight, st);
-            if (drc) return drc;
-        }
-        int rc = model_step_once(m, has_S, S, weight, demean_in_kernel, diag_now, st, use_gf ? &gf : nullptr, have_pre ? &pre : nullptr);
+        const bool use_gf = f.gf.y != nullptr || f.gf.X != nullptr;
+        rc = model_step_once(m, f.has_S, f.S, f.weight, f.demean, diag_now, st, use_gf ? &f.gf : nullptr, f.have_pre ? &f.pre : nullptr);
         if (rc) {
-            if (have_pre) { (void)hipStreamSynchronize(m->adv_stream[m->adv_slot]); m->ablevel = ablevel_before; }
+            if (f.have_pre) first_half_unwind(m, f, st, JOIN_SYNC);
             return rc;
         }
     }
@@ -805,19 +793,12 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
 // Two half-ensembles on two streams.  The online step is a chain of 7 dependent launches whose ramps, tails, kernel boundaries
 // and the step kernel's latency chain (one workgroup per member and layer) leave CUs idle; members are independent, so the two
 // halves of a shard can advance on two internal streams and fill each other's gaps.  A half is the SAME model over a slice:
-// every per-member array is member-major, so a child is a copy of the bookkeeping with B / 2 members and offset pointers; the
-// generator evaluates the halves in two workspaces.  Per-member results do not depend on it (Philox streams are keyed by the
-// global member id; the halves run the kernels the whole would whenever both sides of the few ensemble-size thresholds agree:
-// bit-identical at 64 x 64 / 128 and 96 x 96 / 32 members).
-// Measured with the bench's cadence (bench_tools/halves_cadence.py, one stream -> two): 96 x 96 with 16 / 24 / 32 / 48 / 64
-// members +6.5 / +4 / +4 / +11 / +1 % (before the 96 x 96 tile shapes were chosen by quantisation: +20 / . / +11.5 / +20 / +9 %); 64 x 64 with 16 / 32 / 48 / 64 / 128 members -1 / 0 / +19 / 0 / +0.4 %; 48 x 48 with 32 /
-// 64 members -25 / +27 %; 32 x 32 with 64 members -5 %: on the smaller grids the sign follows the tile-count quantisation of the
-// halves against the whole, not a rule, so the automatic choice is the 96 x 96 grid (16 ... 64 members) only and option
-// "streams" = 2 asks for it elsewhere.  Round 4 (bench_tools/halves_sizes.py): at 64 x 64 / 128 members the two-halves step
-// takes 635 ... 639 us on every box met, the one-stream step 637 us on a fast box and 662 ... 665 us on slow ones (the boxes
-// differ in the clock the f16 MFMA kernels sustain; interleaving the halves' memory-bound and MFMA-bound kernels evens that
-// out): +4 % where the box is slow, nothing where it is fast.  Not the default there: layer 2 of a half runs beside other
-// kernels, so the bench's live roofline of that kernel would describe the mix, not the kernel.
+// every per-member array is member-major (common.hpp::for_each_member_buffer), so a child is a copy of the model with B / 2
+// members, offset pointers and a StepBook of its own; the generator evaluates the halves in two workspaces.  Per-member
+// results do not depend on it (Philox streams are keyed by the global member id; the halves run the kernels the whole would
+// whenever both sides of the few ensemble-size thresholds agree: bit-identical at 64 x 64 / 128 and 96 x 96 / 32 members).
+// The automatic choice is the 96 x 96 grid with 16 ... 64 members, where it was measured to pay at every size; elsewhere the
+// sign follows tile-count quantisation, not a rule, and option "streams" = 2 asks for it (numbers: DESIGN.md sections 3.5, 3.1d).
 static bool step_in_halves(const qgx_model *m, const qgx_param *p) {
     if (m->opts.streams == 1 || !m->small || (m->B & 1) || !p || !p->gen || p->z_external_dev) return false;
     if (p->sampling == QGX_SAMPLING_DETERMINISTIC) return false;      // its pseudo-batches fill the device on one stream
@@ -829,41 +810,58 @@ extern "C" int qgx_step_streams(const qgx_model *m, const qgx_param *p) {
     return m && !m->plan_only && step_in_halves(m, p) ? 2 : 1;
 }
 
+// Everything qgx_step refuses about its arguments, with no HIP call and no write to the model: asked before anything is
+// settled, allocated, forked or launched, so a refusal leaves the handle as it was (also one that steps in halves).  First the
+// sizes (the halves of an ensemble stepped on two streams ask the kernels for B / 2 members), then the sampler rules.
+static int step_check(const qgx_model *m, int nsteps, const qgx_param *p) {
+    if (!p || !p->gen) return QGX_OK;
+    const bool det = p->sampling == QGX_SAMPLING_DETERMINISTIC;
+    if (nsteps > 0) {
+        if (det) {       // (the size rule is asked for the pseudo-batch actually launched)
+            QGX_REQUIRE(p->n_mean >= 1, "qgx_step: deterministic sampling needs n_mean >= 1 realisations (n_mean = %d)", p->n_mean);
+            QGX_REQUIRE(!p->z_external_dev, "qgx_step: deterministic sampling draws its own realisations (z_external_dev)");
+            if (int src = generator_mean_check(p->gen, m->B, m->N, p->n_mean, m->opts.mean_chunk, m->bk.noise_step)) return src;
+        } else {
+            if (int src = generator_size_ok(p->gen, m->B, m->N)) return src;
+            if (step_in_halves(m, p)) { if (int src = generator_size_ok(p->gen, m->B / 2, m->N)) return src; }
+        }
+    }
+    QGX_REQUIRE(p->sampling == QGX_SAMPLING_AR1 || p->sampling == QGX_SAMPLING_CONSTANT || det, "qgx_step: unknown sampling %d", p->sampling);
+    if (det) return QGX_OK;
+    QGX_REQUIRE(!(p->sampling == QGX_SAMPLING_CONSTANT && p->nsteps < 1), "qgx_step: constant sampler needs nsteps >= 1");
+    QGX_REQUIRE(p->nsteps != 0, "qgx_step: nsteps == 0 is not a valid decorrelation time");
+    QGX_REQUIRE(!(p->z_external_dev && nsteps != 1), "qgx_step: external noise needs nsteps_to_run == 1");
+    QGX_REQUIRE(!(p->z_external_dev && !generator_takes_noise(p->gen)),
+                "qgx_step: an OLS or ANN generator takes no latent noise (z_external_dev)");
+    return QGX_OK;
+}
+
 extern "C" int qgx_step(qgx_model *m, int nsteps, const qgx_param *p, int refresh_diag, void *stream) {
     QGX_NEEDS_STATE(m, "qgx_step");
     QGX_REQUIRE(m && nsteps >= 0, "qgx_step: bad argument");
     // pyqg has one q-parameterization slot: refused before anything is launched or changed
     QGX_REQUIRE(!(m->bs_on && p && (p->gen || p->forcing_dev)),
                 "qgx_step: the backscatter closure is on (qgx_set_backscatter): a generator or forcing_dev cannot be stepped with it");
+    if (int crc = step_check(m, nsteps, p)) return crc;
     hipStream_t st = (hipStream_t)stream;
-    // a grid the generator's kernels do not take is refused here: before any launch, and before step_core touches the
-    // sampler state (the halves of an ensemble stepped on two streams ask the kernels for B / 2 members)
-    if (p && p->gen && nsteps > 0) {
-        if (p->sampling == QGX_SAMPLING_DETERMINISTIC) {       // (the size rule is asked for the pseudo-batch actually launched)
-            if (int src = step_mean_check(m, p)) return src;
-        } else {
-            if (int src = generator_size_ok(p->gen, m->B, m->N)) return src;
-            if (step_in_halves(m, p)) { if (int src = generator_size_ok(p->gen, m->B / 2, m->N)) return src; }
-        }
-    }
-    { int trc = team_settle(m, st); if (trc) return trc; }
+    QGX_SETTLE(m, st);
     if (p && p->gen && nsteps > 0) { int arc = step_adv_ensure(m); if (arc) return arc; }
     if (p && (p->gen || p->forcing_dev) && nsteps > 0) { int src = step_sib_ensure(m); if (src) return src; }
     if (nsteps == 0 || !step_in_halves(m, p)) {
         if (p && p->gen) { int wrc = generator_select_workspace(p->gen, 0); if (wrc) return wrc; }
         return step_core(m, nsteps, p, refresh_diag, st);
     }
-    const int N = m->N, NK = m->NK, Bp = m->B / 2;
+    const int Bp = m->B / 2;
     for (int i = 0; i < 2; ++i) if (!m->sub_stream[i]) QGX_HIP(hipStreamCreateWithFlags(&m->sub_stream[i], hipStreamNonBlocking));
     for (int i = 0; i < 3; ++i) if (!m->sub_event[i]) QGX_HIP(hipEventCreateWithFlags(&m->sub_event[i], hipEventDisableTiming));
-    if (m->dg_every > 0) { int arc = diag_ensure_alloc(m); if (arc) return arc; }   // BEFORE the children copy the pointers
+    if (m->dg_every > 0) { int arc = diag_ensure_alloc(m); if (arc) return arc; }   // (the children are views of what exists at the fork)
     // fork.  From here on every exit runs the join below: the caller's stream is ordered behind whatever the sub-streams
     // were given, and a step that failed half-way leaves the handle marked invalid (the halves may stand at different
     // steps, the parent's bookkeeping at neither): later calls fail loudly instead of stepping from an inconsistent state.
     QGX_HIP(hipEventRecord(m->sub_event[2], st));
     qgx_model child[2] = {*m, *m};
     qgx_param pp[2] = {*p, *p};
-    const size_t sr = (size_t)2 * N * N, ss = (size_t)2 * N * NK, s2 = (size_t)N * NK;
+    // latent noise and its scratch: dense (B, 2, N, N) of the element type in use (qgx_get(QGX_F_Z) reads it that way)
     const size_t zbytes = generator_noise_is_double(p->gen) ? sizeof(double) : sizeof(float);
     int rc = QGX_OK;
     hipError_t herr = hipSuccess;
@@ -873,22 +871,13 @@ extern "C" int qgx_step(qgx_model *m, int nsteps, const qgx_param *p, int refres
         qgx_model &k = child[c];
         const size_t b0 = (size_t)c * Bp;
         k.B = Bp; k.d.B = Bp;
-        k.q += b0 * sr; k.u += b0 * sr; k.v += b0 * sr; k.S += b0 * sr;
-        k.qh[0] += b0 * ss; k.qh[1] += b0 * ss; k.ph += b0 * ss; k.dqh += b0 * ss;
-        for (int i = 0; i < 3; ++i) k.dq[i] += b0 * ss;
-        // latent noise and its scratch: dense (B, 2, N, N) of the element type in use (qgx_get(QGX_F_Z) reads it that way)
-        k.z = (char *)k.z + b0 * sr * zbytes;
-        k.xi = (char *)k.xi + b0 * sr * zbytes;
-        if (k.dg_R[0]) {
-            for (double *&r : k.dg_R) r += b0 * sr;
-            for (double *&r : k.dg_S) r += b0 * ss * 2;
-            for (int i = 0; i < qgx::N_DIAGS; ++i) k.dg_acc[i] += b0 * (i < 2 ? 2 * s2 : s2);
-        }
+        for_each_member_buffer(k, zbytes, [b0](auto *&ptr, size_t bytes) {
+            using P = std::remove_reference_t<decltype(ptr)>;
+            if (ptr) ptr = (P)((char *)ptr + b0 * bytes);
+        });
         k.sub_stream[0] = k.sub_stream[1] = nullptr;
         k.adv_slot = c;
         k.is_half = true;
-        if (k.visc_nu) k.visc_nu += b0;                 // (one nu per member)
-        if (k.sib_flag) k.sib_flag += b0 * 4;          // (a half owns the flag words and the placement words of its members: 4 per member)
         pp[c].member_offset = p->member_offset + b0;
     }
     // the halves take turns in chunks of steps (a chunk keeps the fused input / output kernels of consecutive steps fused and
@@ -930,19 +919,16 @@ extern "C" int qgx_step(qgx_model *m, int nsteps, const qgx_param *p, int refres
         if (advanced) {
             const std::string why = qgx_last_error();
             m->broken = "a step of two half-ensembles failed half-way (" + why + "); the halves are at steps " +
-                        std::to_string((long long)child[0].tc) + " and " + std::to_string((long long)child[1].tc) +
+                        std::to_string((long long)child[0].bk.tc) + " and " + std::to_string((long long)child[1].bk.tc) +
                         "; destroy the handle";
         }
         return rc;
     }
-    // the halves advanced in lockstep: the bookkeeping of either is the ensemble's
-    const qgx_model &k = child[0];
-    QGX_REQUIRE(k.tc == child[1].tc && k.cur_q == child[1].cur_q && k.i_new == child[1].i_new && k.noise_step == child[1].noise_step &&
-                k.dg_count == child[1].dg_count, "qgx_step: the two halves of the ensemble left the lockstep");
-    m->tc = k.tc; m->ablevel = k.ablevel; m->cur_q = k.cur_q; m->i_new = k.i_new; m->i_p = k.i_p; m->i_pp = k.i_pp; m->i_x = k.i_x;
-    m->z_double = k.z_double; m->have_noise = k.have_noise; m->const_counter = k.const_counter; m->have_forcing = k.have_forcing;
-    m->noise_step = k.noise_step; m->uv_stale = k.uv_stale; m->q_stale = k.q_stale; m->dg_count = k.dg_count;
-    m->sib_epoch = k.sib_epoch > child[1].sib_epoch ? k.sib_epoch : child[1].sib_epoch;
-    m->x_ready_gen = nullptr;
+    // the halves advanced in lockstep: the bookkeeping of either is the ensemble's.  (The whole records are compared, where
+    // five fields used to be: the halves execute the same sequence of bookkeeping updates, so they agree in every field.)
+    QGX_REQUIRE(child[0].bk == child[1].bk, "qgx_step: the two halves of the ensemble left the lockstep");
+    m->bk = child[0].bk;
+    m->bk.x_ready_gen = nullptr;
+    m->sib_epoch = child[0].sib_epoch > child[1].sib_epoch ? child[0].sib_epoch : child[1].sib_epoch;
     return QGX_OK;
 }

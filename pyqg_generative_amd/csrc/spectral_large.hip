@@ -19,8 +19,7 @@
 
 namespace qgx {
 
-constexpr int ZF = 3;   // complex N x N work fields per member in zbuf: layers 0,1 and one scratch (S / q pair)
-constexpr int DZF = 4;  // complex work fields per member of the fused diagnostics increment (dg_z)
+// (ZF = 3 complex work fields per member in zbuf, DZF = 4 in dg_z: common.hpp)
 
 extern __shared__ __attribute__((aligned(16))) char lg_smem[];
 
@@ -807,14 +806,14 @@ int large_invert(qgx_model *m, hipStream_t st) {
         if (!unfused && lpb >= 4 && lpb % 4 == 0 && (d.N / 2) % (lpb / 4) == 0 && d.N % lpb == 0) {
             const size_t lds = lines_lds(d.N, lpb);
             hipLaunchKernelGGL(k_l_rows_build_inv<0>, dim3(d.B * ((d.N / 2) / (lpb / 4))), dim3(256), lds, st, d,
-                               (const double2 *)m->qh[m->cur_q], m->zbuf, m->ph, lpb / 4, d.N);
+                               (const double2 *)m->qh[m->bk.cur_q], m->zbuf, m->ph, lpb / 4, d.N);
             hipLaunchKernelGGL(k_l_cols<3>, dim3(d.B * 2 * (d.N / lpb)), dim3(256), lds, st, d, m->zbuf, (double *)nullptr,
                                m->u, m->v, lpb);
             QGX_HIP(hipGetLastError());
             return QGX_OK;
         }
     }
-    hipLaunchKernelGGL(k_l_build_uv, pw_grid(d, d.N * d.NK), dim3(256), 0, st, d, m->qh[m->cur_q], m->zbuf, m->ph);
+    hipLaunchKernelGGL(k_l_build_uv, pw_grid(d, d.N * d.NK), dim3(256), 0, st, d, m->qh[m->bk.cur_q], m->zbuf, m->ph);
     int rc = fft2d_large<false>(d, m->zbuf, 0, 2, st);
     if (rc) return rc;
     // the product kernel doubles as the (u, v) unpacker; what it leaves in the scratch zbuf is unused
@@ -847,9 +846,9 @@ static int large_step_unfused(qgx_model *m, const StepArgs &a, hipStream_t st) {
 
 // m->q <- irfft2 of the current qh if the lazy unparameterized path left it behind
 int large_ensure_q(qgx_model *m, hipStream_t st) {
-    if (!m->q_stale) return QGX_OK;
-    int rc = large_qh_to_q(m, m->qh[m->cur_q], m->q, st);
-    if (!rc) m->q_stale = false;
+    if (!m->bk.q_stale) return QGX_OK;
+    int rc = large_qh_to_q(m, m->qh[m->bk.cur_q], m->q, st);
+    if (!rc) m->bk.q_stale = false;
     return rc;
 }
 
@@ -887,13 +886,13 @@ int large_step(qgx_model *m, const StepArgs &a, hipStream_t st) {
                                (const double2 *)m->zbuf, ppw4, zp);
         }
         QGX_HIP(hipGetLastError());
-        m->q_stale = true;
+        m->bk.q_stale = true;
         return QGX_OK;
     }
-    if (m->q_stale) {            // the eager path reads q^n from memory
+    if (m->bk.q_stale) {            // the eager path reads q^n from memory
         int rc = large_qh_to_q(m, a.qh_in, a.q, st);
         if (rc) return rc;
-        m->q_stale = false;
+        m->bk.q_stale = false;
     }
     if (a.has_S) {
         hipLaunchKernelGGL(k_l_rows_S, dim3(B * (N / lpb)), dim3(256), lds, st, d, a.S, m->zbuf, a.weight, lpb);
@@ -1401,7 +1400,7 @@ int large_team_steps(qgx_model *m, int K, int ablevel0, const double coef[3][3],
     QGX_HIP(hipGetLastError());
     m->team_pending = true;
     m->team_stream = st;
-    m->q_stale = true;
+    m->bk.q_stale = true;
     return QGX_OK;
 }
 

@@ -393,6 +393,89 @@ def test_a_failing_half_of_a_two_stream_step_joins_the_streams_and_marks_the_mod
     e.close()
 
 
+REFUSALS = [('constant', 0, 'constant sampler needs nsteps >= 1'), ('AR1', 0, 'not a valid decorrelation time'),
+            ('constant', -2, 'constant sampler needs nsteps >= 1')]
+
+
+def test_a_refused_argument_leaves_a_handle_that_steps_in_halves_usable():
+    """qgx_step checks its arguments (model.hip::step_check) before it settles, allocates, forks or launches anything: a
+    sampler rule refused on a handle that steps as two half-ensembles is the same harmless refusal as on one stream.  (It
+    used to be found by the first half after the fork, which marked the handle invalid for good.)"""
+    import pyqg_generative_amd._lib as L
+    N, B = 32, 2
+    gen = _gpu_generator('vae')
+    q0 = _eddy_like_q(np.random.RandomState(32), B, N)
+    fields = (L.F_QH, L.F_S, L.F_Z, L.F_DQHDT_PP)
+    kw = dict(generator=gen, sampling='AR1', nsteps_decor=3, seed=9)
+    ends = {}
+    for refuse in (True, False):
+        e = _engine(N, B, dt=14400.)
+        e.set_option('streams', 2)
+        assert e.step_streams(gen) == 2
+        e.set_q(q0)
+        e.step(3, **kw)
+        if refuse:
+            before = e.get(L.F_QH).clone()
+            for sampling, nd, msg in REFUSALS:
+                with pytest.raises(L.QgxError, match=msg):
+                    e.step(2, generator=gen, sampling=sampling, nsteps_decor=nd, seed=9)
+            assert e.tc == 3
+            assert torch.equal(e.get(L.F_QH), before)
+        e.step(3, **kw)
+        assert e.tc == 6
+        ends[refuse] = [e.get(f).clone() for f in fields]
+        e.close()
+    for a, b in zip(ends[True], ends[False]):
+        assert torch.equal(a, b)
+    assert bool(torch.isfinite(torch.view_as_real(ends[True][0])).all())
+    one = _engine(N, B, dt=14400.)                       # one stream: the same refusals, word for word
+    one.set_option('streams', 1)
+    assert one.step_streams(gen) == 1
+    one.set_q(q0)
+    one.step(3, **kw)
+    for sampling, nd, msg in REFUSALS:
+        with pytest.raises(L.QgxError, match=msg):
+            one.step(2, generator=gen, sampling=sampling, nsteps_decor=nd, seed=9)
+    one.step(3, **kw)
+    assert one.tc == 6
+    one.close()
+    gen.close()
+
+
+def test_halves_with_every_per_member_buffer_of_a_small_grid_live():
+    """The half-ensembles are slices of EVERY member-major buffer (common.hpp::for_each_member_buffer): per-member viscosity
+    (four different nu), the backscatter constants (set once, then switched off: the buffer exists when the halves are
+    sliced), the diagnostics work fields and accumulators, the sibling flags.  Against the one-stream step with the exact-f32
+    generator kernels, whose results do not depend on the number of members in a launch: bit for bit."""
+    import pyqg_generative_amd._lib as L
+    N, B = 32, 4
+    gen = _gpu_generator('gan')
+    gen.set_option('precision', 0)
+    q0 = _eddy_like_q(np.random.RandomState(324), B, N)
+    res = {}
+    for streams in (1, 2):
+        e = _engine(N, B, dt=14400.)
+        e.set_option('streams', streams)
+        assert e.step_streams(gen) == streams
+        e.set_q(q0)
+        e.set_viscosity([0., 10., 20., 50.])
+        e.set_backscatter([0.01, 0.02, 0.03, 0.04], [0.5, 0.6, 0.7, 0.8])
+        e.set_backscatter(None)
+        assert e.backscatter is None
+        e.diag_config(2, 2)
+        kw = dict(generator=gen, sampling='AR1', nsteps_decor=3, seed=21, member_offset=5)
+        e.step(9, **kw)
+        e.step(5, **kw)
+        res[streams] = [e.get(f).clone() for f in (L.F_QH, L.F_Q, L.F_S, L.F_Z, L.F_DQHDT_PP)] + \
+                       [e.diag(n).clone() for n in ('KEspec', 'paramspec', 'ENSparamspec', 'Dissspec')] + [e.tc, e.diag_count]
+        e.close()
+    assert res[1][-2:] == res[2][-2:] == [14, 6]
+    for a, b in zip(res[1][:-2], res[2][:-2]):
+        assert torch.equal(a, b)
+    assert bool(torch.isfinite(torch.view_as_real(res[2][0])).all())
+    gen.close()
+
+
 def _stepfault_child():
     import json
     import torch

@@ -22,10 +22,6 @@
 
 namespace qgx {
 
-// spectral_large.hip
-int large_q_to_qh(qgx_model *m, const double *q, double2 *qh, hipStream_t st);
-int large_qh_to_q(qgx_model *m, const double2 *qh, double *q, hipStream_t st);
-
 struct BsArgs {
     const double2 *qh;              // (B,2,N,NK) current state
     const double *smag, *back;      // (B) C_S, C_B

@@ -159,6 +159,21 @@ struct DiagAcc { double *KEspec, *Ensspec, *entspec, *APEflux, *KEflux, *APEgens
                         *paramspec_APEflux, *paramspec_KEflux,
                         *Dissspec, *ENSDissspec, *ENSflux, *ENSgenspec, *ENSfrictionspec, *ENSparamspec; };
 constexpr int N_DIAGS = 16;
+// The pointers of one increment (diag.hip::diag_increment fills it; passed to the kernels by value).  Spectra are (B,2,N,NK),
+// real fields (B,2,N,N).  DiagIn: what a caller brings — the state, the forcing and the tendencies — and all that
+// k_diag_small_reg takes (it has no scalar register to spare for kernel arguments it does not read); the rest is written by
+// the increment's own stages.
+struct DiagIn {
+    const double2 *qh; double2 *ph;                                      // state: qh in; ph out
+    const double *S; double weight;                                      // forcing (null: none) and its weight
+    const double *q;                                                     // state: q in
+    const double2 *dq_p, *dq_pp;                                         // T_{n-1}, T_{n-2}
+};
+struct DiagCall : DiagIn {
+    double *u, *v;                                                       // state, out where the path stores them
+    double *P, *XI;                                                      // work fields: p = irfft2(psi), xi = irfft2(-K^2 psi)
+    double2 *S3, *S4, *S5, *Sh, *S6, *S7;                                // spectra of the product pairs 0, 1, 2, 4, 5 and of the forcing (3)
+};
 
 // large grids (spectral_large.hip): complex work fields per member, of N rows at pitch N + large_zpad()
 constexpr int ZF = 3;   // zbuf: layers 0,1 and one scratch (S / q pair)
@@ -321,6 +336,25 @@ int small_step(const SpecDev &d, const ModelOpts &o, const StepArgs &a, hipStrea
 int small_q_to_qh(const SpecDev &d, const ModelOpts &o, const double *q, double2 *qh, hipStream_t st);
 int small_qh_to_q(const SpecDev &d, const ModelOpts &o, const double2 *qh, double *q, hipStream_t st);
 int small_invert(const SpecDev &d, const ModelOpts &o, const double2 *qh, double2 *ph, double *u, double *v, hipStream_t st);
+// one diagnostics increment: in one kernel (k_diag_small) / with its work fields in registers (k_diag_small_reg; _ok: the grid
+// has that kernel; halves: two workgroups per member) / its transforms as (member, transform) workgroups, k_diag_accumulate follows
+int small_diag_increment(const SpecDev &d, const DiagConst &c, const DiagCall &x, const DiagAcc &a, hipStream_t st);
+bool small_diag_increment_reg_ok(const SpecDev &d);
+int small_diag_increment_reg(const SpecDev &d, const DiagConst &c, const DiagCall &x, const DiagAcc &a, hipStream_t st, bool halves);
+int small_diag_transforms_wide(const SpecDev &d, const DiagConst &c, const DiagCall &x, hipStream_t st);
+// spectral_large.hip
+int large_prepare(const SpecDev &d);
+int large_q_to_qh(qgx_model *m, const double *q, double2 *qh, hipStream_t st);
+int large_qh_to_q(qgx_model *m, const double2 *qh, double *q, hipStream_t st);
+int large_invert(qgx_model *m, hipStream_t st);
+int large_step(qgx_model *m, const StepArgs &a, hipStream_t st);
+int large_ensure_q(qgx_model *m, hipStream_t st);
+bool large_diag_fused_ok(const qgx_model *m);
+int large_diag_fused(qgx_model *m, const DiagConst &c, const DiagCall &x, const DiagAcc &acc, hipStream_t st);
+int large_team_available(qgx_model *m, hipStream_t st);
+int large_team_check(qgx_model *m, hipStream_t st, unsigned *flag);
+int large_team_steps(qgx_model *m, int K, int ablevel0, const double coef[3][3], const double2 *qh_src, double2 *qh_dst,
+                     const double2 *p_src, const double2 *pp_src, double2 *p_dst, double2 *pp_dst, hipStream_t st);
 
 // backscatter.hip: kernel attributes / work fields of the closure; S (B,2,N,N) [and R (B)] of the state qh
 int backscatter_prepare(qgx_model *m);

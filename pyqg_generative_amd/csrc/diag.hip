@@ -13,25 +13,6 @@
 #include <cstdlib>
 
 namespace qgx {
-int large_q_to_qh(qgx_model *m, const double *q, double2 *qh, hipStream_t st);
-int large_qh_to_q(qgx_model *m, const double2 *qh, double *q, hipStream_t st);
-int large_invert(qgx_model *m, hipStream_t st);
-int large_ensure_q(qgx_model *m, hipStream_t st);
-bool large_diag_fused_ok(const qgx_model *m);
-int large_diag_fused(qgx_model *m, const DiagConst &c, const double2 *qh, const double2 *Sh, const double2 *dq_p, const double2 *dq_pp,
-                     const DiagAcc &acc, hipStream_t st);
-int small_diag_increment(const SpecDev &d, const DiagConst &c, const double2 *qh, double2 *ph, double *u, double *v, double *P,
-                         double *XI, double2 *S3, double2 *S4, double2 *S5, double2 *Sh, double2 *S6, double2 *S7, const double *S,
-                         double weight, const double *q, const double2 *dq_p, const double2 *dq_pp, const DiagAcc &a, hipStream_t st);
-
-
-bool small_diag_increment_reg_ok(const SpecDev &d);
-int small_diag_increment_reg(const SpecDev &d, const DiagConst &c, const double2 *qh, double2 *ph, const double *S, double weight, const double *q,
-                             const double2 *dq_p, const double2 *dq_pp, const DiagAcc &a, hipStream_t st, bool halves);
-
-int small_diag_transforms_wide(const SpecDev &d, const DiagConst &c, const double2 *qh, double2 *ph, double *u, double *v, double *P,
-                               double *XI, double2 *S3, double2 *S4, double2 *S5, double2 *Sh, double2 *S6, double2 *S7, const double *S,
-                               double weight, const double *q, hipStream_t st);
 
 // xih_k = -wv2 * ph_k
 __global__ void k_diag_xih(SpecDev d, const double2 *ph, double2 *xih) {
@@ -51,37 +32,24 @@ __global__ void k_diag_products(SpecDev d, DiagConst c, const double *u, const d
     const int rz = d.N * d.N, b = blockIdx.y;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < rz; idx += gridDim.x * blockDim.x) {
         const size_t o = (size_t)b * 2 * rz + idx;
-        const double u1 = u[o], u2 = u[o + rz], v1 = v[o], v2 = v[o + rz];
-        const double ptpc = p[o] - p[o + rz];
-        const double ub = c.del1 * u1 + c.del2 * u2, vb = c.del1 * v1 + c.del2 * v2;
-        R3[o] = ub * ptpc; R3[o + rz] = vb * ptpc;
-        const double x1 = xi[o], x2 = xi[o + rz];
-        R4[o] = u1 * x1; R4[o + rz] = v1 * x1;
-        R5[o] = u2 * x2; R5[o + rz] = v2 * x2;
-        const double q1 = q[o], q2 = q[o + rz];
-        R6[o] = u1 * q1; R6[o + rz] = v1 * q1;
-        R7[o] = u2 * q2; R7[o + rz] = v2 * q2;
+        const double2 uv1 = make_double2(u[o], v[o]), uv2 = make_double2(u[o + rz], v[o + rz]);
+        const double p1 = p[o], p2 = p[o + rz], x1 = xi[o], x2 = xi[o + rz], q1 = q[o], q2 = q[o + rz];
+        const double2 r3 = diag_product_pair(0, c, 0., uv1, uv2, p1, p2), r4 = diag_product_pair(1, c, 0., uv1, uv2, x1, x2),
+                      r5 = diag_product_pair(2, c, 0., uv1, uv2, x1, x2), r6 = diag_product_pair(4, c, 0., uv1, uv2, q1, q2),
+                      r7 = diag_product_pair(5, c, 0., uv1, uv2, q1, q2);
+        R3[o] = r3.x; R3[o + rz] = r3.y;
+        R4[o] = r4.x; R4[o + rz] = r4.y;
+        R5[o] = r5.x; R5[o + rz] = r5.y;
+        R6[o] = r6.x; R6[o + rz] = r6.y;
+        R7[o] = r7.x; R7[o + rz] = r7.y;
     }
 }
 
-__global__ void k_diag_accumulate(SpecDev d, DiagConst c, const double2 *qh, const double2 *ph, const double2 *S3,
-                                  const double2 *S4, const double2 *S5, const double2 *Sh, const double2 *S6, const double2 *S7,
-                                  const double2 *dq_p, const double2 *dq_pp, DiagAcc a) {
+__global__ void k_diag_accumulate(SpecDev d, DiagConst c, DiagCall x, DiagAcc a) {
     const int N = d.N, NK = d.NK, sz = N * NK, b = blockIdx.y;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < sz; idx += gridDim.x * blockDim.x) {
         const int j = idx / NK, i = idx - j * NK;
-        const size_t o = (size_t)b * 2 * sz + idx, o2 = (size_t)b * sz + idx;
-        const double2 zero = make_double2(0., 0.);
-        if (c.nu) {      // molecular viscosity: part of the parameterization's tendency (diag_add_visc)
-            double2 s1 = Sh ? Sh[o] : zero, s2 = Sh ? Sh[o + sz] : zero;
-            diag_add_visc(d, c, b, idx, qh[o], qh[o + sz], ph[o], ph[o + sz], s1, s2);
-            diag_accumulate_elem(d, c, a, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], S3[o], S3[o + sz], S4[o], S4[o + sz],
-                                 S5[o], S5[o + sz], true, s1, s2, S6[o], S6[o + sz], S7[o], S7[o + sz], dq_p[o], dq_p[o + sz], dq_pp[o],
-                                 dq_pp[o + sz]);
-        } else
-        diag_accumulate_elem(d, c, a, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], S3[o], S3[o + sz], S4[o], S4[o + sz],
-                             S5[o], S5[o + sz], Sh != nullptr, Sh ? Sh[o] : zero, Sh ? Sh[o + sz] : zero, S6[o], S6[o + sz], S7[o],
-                             S7[o + sz], dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
+        diag_accumulate(d, c, a, b, idx, i, j, sz, [&] { return diag_elem_load(x, (size_t)b * 2 * sz + idx, sz); });
     }
 }
 
@@ -115,15 +83,8 @@ int diag_ensure_alloc(qgx_model *m) {
     return QGX_OK;
 }
 
-int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st) {
+static DiagConst diag_const(const qgx_model *m) {
     const SpecDev &d = m->d;
-    const size_t nr = (size_t)d.B * 2 * d.N * d.N;
-    int rc;
-    if ((rc = diag_ensure_alloc(m))) return rc;
-    double2 *qh = m->qh[m->bk.cur_q];
-    double *p = m->dg_R[0], *xi = m->dg_R[1], *R3 = m->dg_R[2], *R4 = m->dg_R[3], *R5 = m->dg_R[4];
-    double2 *xih = (double2 *)m->dg_S[0], *S3 = (double2 *)m->dg_S[1], *S4 = (double2 *)m->dg_S[2],
-            *S5 = (double2 *)m->dg_S[3], *Sh = (double2 *)m->dg_S[4], *S6 = (double2 *)m->dg_S[5], *S7 = (double2 *)m->dg_S[6];
     DiagConst c;
     c.del1 = m->cfg.delta / (m->cfg.delta + 1.); c.del2 = 1. / (m->cfg.delta + 1.);
     c.rdm2 = pow(m->cfg.rd, -2.0); c.Udiff = m->cfg.U1 - m->cfg.U2; c.rek = m->cfg.rek;
@@ -136,81 +97,84 @@ int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st)
     }
     c.nu = m->visc_on ? m->visc_nu : nullptr;      // the viscous term is part of the parameterization's tendency
     c.nu_pv = m->visc_pv;
-    const double2 *dq_p = m->dq[m->bk.i_new], *dq_pp = m->dq[m->bk.i_p];       // T_{n-1}, T_{n-2}
+    return c;
+}
+static DiagAcc diag_acc(const qgx_model *m) {
     DiagAcc a;
     a.KEspec = m->dg_acc[0]; a.Ensspec = m->dg_acc[1]; a.entspec = m->dg_acc[2]; a.APEflux = m->dg_acc[3];
     a.KEflux = m->dg_acc[4]; a.APEgenspec = m->dg_acc[5]; a.KEfrictionspec = m->dg_acc[6]; a.paramspec = m->dg_acc[7];
     a.paramspec_APEflux = m->dg_acc[8]; a.paramspec_KEflux = m->dg_acc[9];
     a.Dissspec = m->dg_acc[10]; a.ENSDissspec = m->dg_acc[11]; a.ENSflux = m->dg_acc[12]; a.ENSgenspec = m->dg_acc[13];
     a.ENSfrictionspec = m->dg_acc[14]; a.ENSparamspec = m->dg_acc[15];
+    return a;
+}
+
+int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st) {
+    const SpecDev &d = m->d;
+    const size_t nr = (size_t)d.B * 2 * d.N * d.N;
+    int rc;
+    if ((rc = diag_ensure_alloc(m))) return rc;
+    double *R3 = m->dg_R[2], *R4 = m->dg_R[3], *R5 = m->dg_R[4], *R6 = m->dg_R[5], *R7 = m->dg_R[6];
+    double2 *xih = (double2 *)m->dg_S[0];
+    const DiagConst c = diag_const(m);
+    const DiagAcc a = diag_acc(m);
+    DiagCall x;
+    x.qh = m->qh[m->bk.cur_q]; x.ph = m->ph; x.u = m->u; x.v = m->v; x.q = m->q;
+    x.P = m->dg_R[0]; x.XI = m->dg_R[1];
+    x.S3 = (double2 *)m->dg_S[1]; x.S4 = (double2 *)m->dg_S[2]; x.S5 = (double2 *)m->dg_S[3]; x.Sh = (double2 *)m->dg_S[4];
+    x.S6 = (double2 *)m->dg_S[5]; x.S7 = (double2 *)m->dg_S[6];
+    x.S = S; x.weight = weight;
+    x.dq_p = m->dq[m->bk.i_new]; x.dq_pp = m->dq[m->bk.i_p];
+    const auto accumulate = [&] {
+        hipLaunchKernelGGL(k_diag_accumulate, dgrid(d, d.N * d.NK), dim3(256), 0, st, d, c, x, a);
+        return hipGetLastError();
+    };
+    // the forcing's spectrum where no kernel of the path forms it: Sh = rfft2(weight S) (R3 is free at that point)
+    const auto forcing_spectrum = [&](auto fwd) {
+        if (!S) return (int)QGX_OK;
+        hipLaunchKernelGGL(k_diag_scale_S, dim3(1024), dim3(256), 0, st, S, R3, nr, weight);
+        return fwd(R3, x.Sh);
+    };
+    bool uv_stale = m->bk.uv_stale;       // a path that stores u, v clears it; one that stores psi alone sets or leaves it
     if (m->small && m->opts.diag_fused && (m->opts.diag_wide > 0 || (m->opts.diag_wide < 0 && 6 * d.B <= 256))) {
         // few members: the ten transforms as (member, transform) workgroups — two launches — then the accumulation kernel;
         // a single member's increment is three short kernels instead of a chain of ten transforms on one CU
-        rc = small_diag_transforms_wide(d, c, qh, m->ph, m->u, m->v, p, xi, S3, S4, S5, Sh, S6, S7, S, weight, m->q, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_diag_accumulate, dgrid(d, d.N * d.NK), dim3(256), 0, st, d, c, (const double2 *)qh,
-                           (const double2 *)m->ph, (const double2 *)S3, (const double2 *)S4, (const double2 *)S5,
-                           S ? (const double2 *)Sh : (const double2 *)nullptr, (const double2 *)S6, (const double2 *)S7, dq_p, dq_pp, a);
-        QGX_HIP(hipGetLastError());
-        m->bk.uv_stale = false;
-        m->bk.dg_count += 1;
-        return QGX_OK;
-    }
-    if (m->small && m->opts.diag_fused && m->opts.diag_reg && small_diag_increment_reg_ok(d)) {
+        if ((rc = small_diag_transforms_wide(d, c, x, st))) return rc;
+        QGX_HIP(accumulate());
+        uv_stale = false;
+    } else if (m->small && m->opts.diag_fused && m->opts.diag_reg && small_diag_increment_reg_ok(d)) {
         // grids up to 64 x 64: the same in ONE kernel whose work fields stay in registers (k_diag_small_reg: a quarter of the
         // bytes); it stores ph but no u, v — they are marked stale and inverted on demand
         // ... as two workgroups per member (chains of 7 and 5 transforms instead of one of 10) while both fit the device at once
         const bool halves = m->opts.diag_reg == 3 || (m->opts.diag_reg == 1 && 2 * d.B <= 256);
-        rc = small_diag_increment_reg(d, c, qh, m->ph, S, weight, m->q, dq_p, dq_pp, a, st, halves);
-        if (rc) return rc;
-        m->bk.uv_stale = true;
-        m->bk.dg_count += 1;
-        return QGX_OK;
-    }
-    if (m->small && m->opts.diag_fused) {
+        if ((rc = small_diag_increment_reg(d, c, x, a, st, halves))) return rc;
+        uv_stale = true;
+    } else if (m->small && m->opts.diag_fused) {
         // small grids: the whole increment (inversion, ten packed transforms, products, accumulation) in ONE kernel, a
         // workgroup per member (spectral_small.hip::k_diag_small) instead of a dozen launches
-        rc = small_diag_increment(d, c, qh, m->ph, m->u, m->v, p, xi, S3, S4, S5, Sh, S6, S7, S, weight, m->q, dq_p, dq_pp, a, st);
-        if (rc) return rc;
-        m->bk.uv_stale = false;
-        m->bk.dg_count += 1;
-        return QGX_OK;
-    }
-    if (!m->small && large_diag_fused_ok(m)) {
+        if ((rc = small_diag_increment(d, c, x, a, st))) return rc;
+        uv_stale = false;
+    } else if (!m->small && large_diag_fused_ok(m)) {
         // large grids at the specialised sizes: the increment's four packed fields through three fused launches
         // (spectral_large.hip); ph is stored, u and v are not (uv_stale stays as it is: they are inverted on demand)
-        const double2 *Shp = nullptr;
-        if (S) {
-            hipLaunchKernelGGL(k_diag_scale_S, dim3(1024), dim3(256), 0, st, S, R3, nr, weight);
-            if ((rc = large_q_to_qh(m, R3, Sh, st))) return rc;
-            Shp = Sh;
-        }
-        if ((rc = large_diag_fused(m, c, qh, Shp, dq_p, dq_pp, a, st))) return rc;
-        m->bk.dg_count += 1;
-        return QGX_OK;
+        if ((rc = forcing_spectrum([&](const double *r, double2 *h) { return large_q_to_qh(m, r, h, st); }))) return rc;
+        if ((rc = large_diag_fused(m, c, x, a, st))) return rc;
+    } else {
+        // one launch per transform.  _invert: ph, u, v of the current state
+        rc = m->small ? small_invert(d, m->opts, x.qh, m->ph, m->u, m->v, st) : large_invert(m, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_diag_xih, dgrid(d, 2 * d.N * d.NK), dim3(256), 0, st, d, (const double2 *)m->ph, xih);
+        auto inv = [&](const double2 *h, double *r) { return m->small ? small_qh_to_q(d, m->opts, h, r, st) : large_qh_to_q(m, h, r, st); };
+        auto fwd = [&](const double *r, double2 *h) { return m->small ? small_q_to_qh(d, m->opts, r, h, st) : large_q_to_qh(m, r, h, st); };
+        if ((rc = inv(m->ph, x.P)) || (rc = inv(xih, x.XI))) return rc;
+        if (!m->small && (rc = large_ensure_q(m, st))) return rc;          // the lazy unparameterized path keeps no real-space q
+        hipLaunchKernelGGL(k_diag_products, dgrid(d, d.N * d.N), dim3(256), 0, st, d, c, (const double *)m->u,
+                           (const double *)m->v, (const double *)x.P, (const double *)x.XI, (const double *)m->q, R3, R4, R5, R6, R7);
+        if ((rc = fwd(R3, x.S3)) || (rc = fwd(R4, x.S4)) || (rc = fwd(R5, x.S5)) || (rc = fwd(R6, x.S6)) || (rc = fwd(R7, x.S7))) return rc;
+        if ((rc = forcing_spectrum(fwd))) return rc;
+        QGX_HIP(accumulate());
     }
-    // _invert: ph, u, v of the current state
-    rc = m->small ? small_invert(d, m->opts, qh, m->ph, m->u, m->v, st) : large_invert(m, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_diag_xih, dgrid(d, 2 * d.N * d.NK), dim3(256), 0, st, d, (const double2 *)m->ph, xih);
-    auto inv = [&](const double2 *h, double *r) { return m->small ? small_qh_to_q(d, m->opts, h, r, st) : large_qh_to_q(m, h, r, st); };
-    auto fwd = [&](const double *r, double2 *h) { return m->small ? small_q_to_qh(d, m->opts, r, h, st) : large_q_to_qh(m, r, h, st); };
-    if ((rc = inv(m->ph, p)) || (rc = inv(xih, xi))) return rc;
-    if (!m->small && (rc = large_ensure_q(m, st))) return rc;          // the lazy unparameterized path keeps no real-space q
-    double *R6 = m->dg_R[5], *R7 = m->dg_R[6];
-    hipLaunchKernelGGL(k_diag_products, dgrid(d, d.N * d.N), dim3(256), 0, st, d, c, (const double *)m->u,
-                       (const double *)m->v, (const double *)p, (const double *)xi, (const double *)m->q, R3, R4, R5, R6, R7);
-    if ((rc = fwd(R3, S3)) || (rc = fwd(R4, S4)) || (rc = fwd(R5, S5)) || (rc = fwd(R6, S6)) || (rc = fwd(R7, S7))) return rc;
-    const double2 *Shp = nullptr;
-    if (S) {
-        hipLaunchKernelGGL(k_diag_scale_S, dim3(1024), dim3(256), 0, st, S, R3, nr, weight);
-        if ((rc = fwd(R3, Sh))) return rc;
-        Shp = Sh;
-    }
-    hipLaunchKernelGGL(k_diag_accumulate, dgrid(d, d.N * d.NK), dim3(256), 0, st, d, c, (const double2 *)qh,
-                       (const double2 *)m->ph, (const double2 *)S3, (const double2 *)S4, (const double2 *)S5, Shp,
-                       (const double2 *)S6, (const double2 *)S7, dq_p, dq_pp, a);
-    QGX_HIP(hipGetLastError());
+    m->bk.uv_stale = uv_stale;
     m->bk.dg_count += 1;
     return QGX_OK;
 }

@@ -19,21 +19,32 @@ __device__ __forceinline__ double2 diag_jacobian(double kx, double ly, double2 A
 __device__ __forceinline__ double diag_dot(double2 a, double bx, double by) { return __builtin_fma(a.x, bx, a.y * by); }
 // Models with molecular viscosity (DiagConst::nu != null): the parameterization's spectral tendency dqh of member b at element
 // idx is weight * S^ (s1, s2 on entry; zero without a forcing) plus the viscous term the step kernels add to the tendency
-// (spectral_elem.hpp::visc_elem).  The callers keep their call of diag_accumulate_elem for models without viscosity exactly
-// as it was, in a branch of its own: its expressions compile to what they always were (paramspec and ENSparamspec moved
-// a last bit when (s1, s2) reached the one call through a select).
-__device__ __forceinline__ void diag_add_visc(const SpecDev &d, const DiagConst &c, int b, int idx, double2 q1, double2 q2, double2 p1,
+// (spectral_elem.hpp::visc_elem).  diag_accumulate() below keeps the call of diag_accumulate_elem for models without
+// viscosity in a branch of its own: its expressions compile to what they were before there was a viscous term (paramspec and
+// ENSparamspec moved a last bit when (s1, s2) reached one single call through a select).
+__device__ __forceinline__ void diag_add_visc(const SpecDev &d, const DiagConst &c, double nu, int idx, double2 q1, double2 q2, double2 p1,
                                               double2 p2, double2 &s1, double2 &s2) {
-    const double nu = c.nu[b], wv2 = d.wv2[idx];
+    const double wv2 = d.wv2[idx];
     const double2 v1 = visc_elem(nu, c.nu_pv, wv2, q1, p1), v2 = visc_elem(nu, c.nu_pv, wv2, q2, p2);
     s1.x += v1.x; s1.y += v1.y; s2.x += v2.x; s2.y += v2.y;
 }
+// One spectral element of the increment: what diag_accumulate_elem reads.  Value-initialised to zero, so a caller fills only
+// what its PARTS need.  (A, B)n: the half spectra of product pair n (diag_product_pair: 3 (ub ptpc, vb ptpc), 4, 5
+// (u_k xi_k, v_k xi_k), 6, 7 (u_k q_k, v_k q_k)); (s1, s2): the parameterization's spectral tendency, read where has_S;
+// hp, hpp: the two older tendencies T_{n-1}, T_{n-2}
+struct DiagElem {
+    double2 q1{}, q2{}, p1{}, p2{};
+    double2 A3{}, B3{}, A4{}, B4{}, A5{}, B5{}, A6{}, B6{}, A7{}, B7{};
+    bool has_S = false;
+    double2 s1{}, s2{};
+    double2 hp1{}, hp2{}, hpp1{}, hpp2{};
+};
 template <int PARTS = 7, bool JPRE = false>
 __device__ __forceinline__ void diag_accumulate_elem(const SpecDev &d, const DiagConst &c, const DiagAcc &a, int idx, int i, int j,
-                                                     size_t o, size_t o2, int sz, double2 q1, double2 q2, double2 p1, double2 p2,
-                                                     double2 A3, double2 B3, double2 A4, double2 B4, double2 A5, double2 B5,
-                                                     bool has_S, double2 s1, double2 s2, double2 A6, double2 B6, double2 A7,
-                                                     double2 B7, double2 hp1, double2 hp2, double2 hpp1, double2 hpp2) {
+                                                     size_t o, size_t o2, int sz, const DiagElem &e) {
+    const double2 q1 = e.q1, q2 = e.q2, p1 = e.p1, p2 = e.p2, A3 = e.A3, B3 = e.B3, A4 = e.A4, B4 = e.B4, A5 = e.A5, B5 = e.B5;
+    const double2 A6 = e.A6, B6 = e.B6, A7 = e.A7, B7 = e.B7, s1 = e.s1, s2 = e.s2, hp1 = e.hp1, hp2 = e.hp2, hpp1 = e.hpp1, hpp2 = e.hpp2;
+    const bool has_S = e.has_S;
     const double kx = d.kk[i], ly = d.ll[j], wv2 = d.wv2[idx];
     const double dpx = p1.x - p2.x, dpy = p1.y - p2.y;
     if (PARTS & 4) {
@@ -97,6 +108,60 @@ __device__ __forceinline__ void diag_accumulate_elem(const SpecDev &d, const Dia
     const double e2x = fm1 * (q2.x + c.dt1 * t2x + c.dt2 * hp2.x + c.dt3 * hpp2.x), e2y = fm1 * (q2.y + c.dt1 * t2y + c.dt2 * hp2.y + c.dt3 * hpp2.y);
     a.Dissspec[o2] += -(c.H0 * (p1.x * e1x + p1.y * e1y) + c.H1 * (p2.x * e2x + p2.y * e2y)) * c.invdt * c.invM2;
     a.ENSDissspec[o2] += (c.H0 * (q1.x * e1x + q1.y * e1y) + c.H1 * (q2.x * e2x + q2.y * e2y)) * c.invdt * c.invM2;
+}
+
+// The element of member b with the viscosity split, for every caller.  elem() -> the DiagElem, with the forcing's tendency in
+// (s1, s2) and has_S (zero, false without a forcing); it is asked for inside each branch, so that the element's loads stay
+// where they were when every caller wrote the two branches out (gathered in front of the branch they cost k_diag_accumulate
+// 288 bytes of scratch per lane).
+template <int PARTS = 7, bool JPRE = false, class E>
+__device__ __forceinline__ void diag_accumulate(const SpecDev &d, const DiagConst &c, const DiagAcc &a, int b, int idx, int i, int j, int sz,
+                                                E &&elem) {
+    const size_t o = (size_t)b * 2 * sz + idx, o2 = (size_t)b * sz + idx;
+    if (c.nu) {      // molecular viscosity: part of the parameterization's tendency (diag_add_visc)
+        const double nu = c.nu[b];
+        DiagElem e = elem();
+        diag_add_visc(d, c, nu, idx, e.q1, e.q2, e.p1, e.p2, e.s1, e.s2);
+        e.has_S = true;
+        diag_accumulate_elem<PARTS, JPRE>(d, c, a, idx, i, j, o, o2, sz, e);
+    } else
+        diag_accumulate_elem<PARTS, JPRE>(d, c, a, idx, i, j, o, o2, sz, elem());
+}
+
+// The element whose every field lies in global memory (k_diag_small, k_diag_accumulate): o = (b 2 + 0) sz + idx
+__device__ __forceinline__ DiagElem diag_elem_load(const DiagCall &x, size_t o, int sz) {
+    DiagElem e;
+    if (x.S) { e.has_S = true; e.s1 = x.Sh[o]; e.s2 = x.Sh[o + sz]; }
+    e.q1 = x.qh[o]; e.q2 = x.qh[o + sz]; e.p1 = x.ph[o]; e.p2 = x.ph[o + sz];
+    e.A3 = x.S3[o]; e.B3 = x.S3[o + sz]; e.A4 = x.S4[o]; e.B4 = x.S4[o + sz]; e.A5 = x.S5[o]; e.B5 = x.S5[o + sz];
+    e.A6 = x.S6[o]; e.B6 = x.S6[o + sz]; e.A7 = x.S7[o]; e.B7 = x.S7[o + sz];
+    e.hp1 = x.dq_p[o]; e.hp2 = x.dq_p[o + sz]; e.hpp1 = x.dq_pp[o]; e.hpp2 = x.dq_pp[o + sz];
+    return e;
+}
+
+// ---- the real-space product pairs of the increment, (a, b) of the packed field a + i b that is transformed
+// which: 0 (ub ptpc, vb ptpc), ub = del1 u_1 + del2 u_2, ptpc = p_1 - p_2 (APEflux);  1, 2 (u_k xi_k, v_k xi_k) (KEflux);
+//        3 the forcing, weight (S_1, S_2);  4, 5 (u_k q_k, v_k q_k) (the enstrophy flux and the tendency of Dissspec)
+// uv1, uv2 = (u_k, v_k); (f1, f2): both layers of the scalar field the pair multiplies — p, xi, S, q.  A caller passes what the
+// pair of `which` reads (diag_pair_layers), anything elsewhere.
+// (which == 0 leaves del1 u_1 + del2 u_2 to the compiler's choice of which product it fuses: one text does not pin the bits.
+//  The forms agree bit for bit because that choice comes out the same in the kernels this is inlined into today — measured,
+//  tests/test_gpu_parity.py — except in k_diag_small_reg at 32 x 32 (its own copy of this pair, or the unfused sums of
+//  APEflux in diag_accumulate_elem).  Explicit fmas would pin it, and move APEflux by a last bit once.)
+__device__ __forceinline__ int diag_pair_layers(int which) { return which == 0 ? 3 : which == 3 ? 0 : (which == 1 || which == 4) ? 1 : 2; }
+__device__ __forceinline__ double2 diag_product_pair(int which, const DiagConst &c, double weight, double2 uv1, double2 uv2, double f1, double f2) {
+    if (which == 0) {
+        const double u1 = uv1.x, u2 = uv2.x, v1 = uv1.y, v2 = uv2.y;
+        const double ptpc = f1 - f2;
+        const double ub = c.del1 * u1 + c.del2 * u2, vb = c.del1 * v1 + c.del2 * v2;
+        return make_double2(ub * ptpc, vb * ptpc);
+    }
+    if (which == 3) return make_double2(weight * f1, weight * f2);
+    return diag_pair_layers(which) == 1 ? make_double2(uv1.x * f1, uv1.y * f1) : make_double2(uv2.x * f2, uv2.y * f2);
+}
+// the spectrum array of product pair `which`
+__device__ __forceinline__ double2 *diag_spectrum(const DiagCall &x, int which) {
+    return which == 0 ? x.S3 : (which == 1 ? x.S4 : (which == 2 ? x.S5 : (which == 3 ? x.Sh : (which == 4 ? x.S6 : x.S7))));
 }
 
 }  // namespace qgx

@@ -21,10 +21,6 @@
 
 namespace qgx {
 
-// spectral_large.hip
-int large_q_to_qh(qgx_model *m, const double *q, double2 *qh, hipStream_t st);
-int large_qh_to_q(qgx_model *m, const double2 *qh, double *q, hipStream_t st);
-
 struct FlowArgs {
     const void *u, *v;              // (P, N, N) float or double, P = 2 S planes
     double *omega;                  // (P, N, N) or null

@@ -18,18 +18,6 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
-// spectral_large.hip
-int large_prepare(const SpecDev &d);
-int large_q_to_qh(qgx_model *m, const double *q, double2 *qh, hipStream_t st);
-int large_qh_to_q(qgx_model *m, const double2 *qh, double *q, hipStream_t st);
-int large_invert(qgx_model *m, hipStream_t st);
-int large_step(qgx_model *m, const StepArgs &a, hipStream_t st);
-int large_ensure_q(qgx_model *m, hipStream_t st);
-int large_team_available(qgx_model *m, hipStream_t st);
-int large_team_check(qgx_model *m, hipStream_t st, unsigned *flag);
-int large_team_steps(qgx_model *m, int K, int ablevel0, const double coef[3][3], const double2 *qh_src, double2 *qh_dst,
-                     const double2 *p_src, const double2 *pp_src, double2 *p_dst, double2 *pp_dst, hipStream_t st);
-
 // One _step_forward: AB3 coefficient schedule of kernel.pyx::_forward_timestep, history rotation.
 // the arguments of step n that do not depend on its forcing; advances the AB3 start-up level
 static void step_args_begin(qgx_model *m, int diag, StepArgs &a) {

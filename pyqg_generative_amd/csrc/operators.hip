@@ -8,8 +8,6 @@
 #include "common.hpp"
 
 namespace qgx {
-int large_q_to_qh(qgx_model *m, const double *q, double2 *qh, hipStream_t st);
-int large_qh_to_q(qgx_model *m, const double2 *qh, double *q, hipStream_t st);
 
 // dst (M,N,N/2+1) <- src (M,n,n/2+1): rows [0,h) and the last h rows, columns [0,h], h = min(n,N)/2
 __global__ void k_spec_regrid(const double2 *src, double2 *dst, int n, int N, double scale, int zero_src_2h,

@@ -571,20 +571,20 @@ __global__ __launch_bounds__(NT) void k_l_rows_diag_acc(SpecDev d, DiagConst c, 
 #pragma unroll
         for (int f = 0; f < NF; ++f) unpack_half(L[(r * NF + f) * LD + pos[i]], L[(rm * NF + f) * LD + pos[im]], A[f], Bv[f]);
         // (ub d, vb d) = del_1 (u_1 d) + del_2 (u_2 d);  (u_1 xi_1) = (u_1 q_1) + F_1 (u_1 d);  (u_2 xi_2) = (u_2 q_2) - F_2 (u_2 d)
-        const double2 A3 = make_double2(c.del1 * A[2].x + c.del2 * A[3].x, c.del1 * A[2].y + c.del2 * A[3].y);
-        const double2 B3 = make_double2(c.del1 * Bv[2].x + c.del2 * Bv[3].x, c.del1 * Bv[2].y + c.del2 * Bv[3].y);
-        const double2 A4 = make_double2(A[0].x + F1 * A[2].x, A[0].y + F1 * A[2].y), B4 = make_double2(Bv[0].x + F1 * Bv[2].x, Bv[0].y + F1 * Bv[2].y);
-        const double2 A5 = make_double2(A[1].x - F2 * A[3].x, A[1].y - F2 * A[3].y), B5 = make_double2(Bv[1].x - F2 * Bv[3].x, Bv[1].y - F2 * Bv[3].y);
-        const size_t o = (size_t)b * 2 * sz + idx, o2 = (size_t)b * sz + idx;
-        const double2 zero = make_double2(0., 0.);
-        if (c.nu) {      // molecular viscosity: part of the parameterization's tendency (diag_add_visc)
-            double2 s1 = Sh ? Sh[o] : zero, s2 = Sh ? Sh[o + sz] : zero;
-            diag_add_visc(d, c, b, idx, qh[o], qh[o + sz], ph[o], ph[o + sz], s1, s2);
-            diag_accumulate_elem(d, c, acc, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], A3, B3, A4, B4, A5, B5, true,
-                                 s1, s2, A[0], Bv[0], A[1], Bv[1], dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
-        } else
-        diag_accumulate_elem(d, c, acc, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], A3, B3, A4, B4, A5, B5, Sh != nullptr,
-                             Sh ? Sh[o] : zero, Sh ? Sh[o + sz] : zero, A[0], Bv[0], A[1], Bv[1], dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
+        DiagElem e;
+        e.A3 = make_double2(c.del1 * A[2].x + c.del2 * A[3].x, c.del1 * A[2].y + c.del2 * A[3].y);
+        e.B3 = make_double2(c.del1 * Bv[2].x + c.del2 * Bv[3].x, c.del1 * Bv[2].y + c.del2 * Bv[3].y);
+        e.A4 = make_double2(A[0].x + F1 * A[2].x, A[0].y + F1 * A[2].y); e.B4 = make_double2(Bv[0].x + F1 * Bv[2].x, Bv[0].y + F1 * Bv[2].y);
+        e.A5 = make_double2(A[1].x - F2 * A[3].x, A[1].y - F2 * A[3].y); e.B5 = make_double2(Bv[1].x - F2 * Bv[3].x, Bv[1].y - F2 * Bv[3].y);
+        e.A6 = A[0]; e.B6 = Bv[0]; e.A7 = A[1]; e.B7 = Bv[1];
+        diag_accumulate(d, c, acc, b, idx, i, j, sz, [&] {
+            const size_t o = (size_t)b * 2 * sz + idx;
+            DiagElem l = e;
+            l.q1 = qh[o]; l.q2 = qh[o + sz]; l.p1 = ph[o]; l.p2 = ph[o + sz];
+            if (Sh) { l.has_S = true; l.s1 = Sh[o]; l.s2 = Sh[o + sz]; }
+            l.hp1 = dq_p[o]; l.hp2 = dq_p[o + sz]; l.hpp1 = dq_pp[o]; l.hpp2 = dq_pp[o + sz];
+            return l;
+        });
     }
 }
 
@@ -653,7 +653,7 @@ enum LargeOp { L_HAS_STEP, L_HAS_DIAG, L_CAPS, L_STEP, L_DIAG };
 struct LargeCall {           // arguments of the launches: L_STEP reads a, L_DIAG the rest
     const StepArgs *a = nullptr;
     const DiagConst *c = nullptr;
-    const double2 *qh = nullptr, *Sh = nullptr, *dq_p = nullptr, *dq_pp = nullptr;
+    const DiagCall *x = nullptr;
     const DiagAcc *acc = nullptr;
 };
 
@@ -695,11 +695,13 @@ static int large_tiles_run(LargeOp op, qgx_model *m, const LargeCall &x, hipStre
         if (op == L_DIAG) {
             const SpecDev &d = m->d;
             const int B = d.B;
-            hipLaunchKernelGGL(k1, dim3(B * (NN / 2 / T::DP)), dim3(T::DT1), lines_lds(NN, 2 * DZF * T::DP), st, d, x.qh, m->dg_z,
+            const DiagCall &dc = *x.x;
+            hipLaunchKernelGGL(k1, dim3(B * (NN / 2 / T::DP)), dim3(T::DT1), lines_lds(NN, 2 * DZF * T::DP), st, d, dc.qh, m->dg_z,
                                m->ph, T::DP, zp);
             hipLaunchKernelGGL(k2, dim3(B * (NN / T::DC)), dim3(T::DT2), lines_lds(NN, DZF * T::DC), st, d, m->dg_z, zp);
             hipLaunchKernelGGL(k3, dim3(B * (NN / 2 / T::DP)), dim3(T::DT1), lines_lds(NN, 2 * DZF * T::DP), st, d, *x.c,
-                               (const double2 *)m->dg_z, x.qh, (const double2 *)m->ph, x.Sh, x.dq_p, x.dq_pp, *x.acc, zp);
+                               (const double2 *)m->dg_z, dc.qh, (const double2 *)m->ph,
+                               dc.S ? (const double2 *)dc.Sh : (const double2 *)nullptr, dc.dq_p, dc.dq_pp, *x.acc, zp);
         }
     }
     QGX_HIP(hipGetLastError());
@@ -917,12 +919,11 @@ int large_step(qgx_model *m, const StepArgs &a, hipStream_t st) {
 // the three launches of one diagnostics increment (kernels above); false: no specialisation for this grid size
 bool large_diag_fused_ok(const qgx_model *m) { return m->opts.large_fused && large_tiles(m->N, L_HAS_DIAG); }
 
-int large_diag_fused(qgx_model *m, const DiagConst &c, const double2 *qh, const double2 *Sh, const double2 *dq_p, const double2 *dq_pp,
-                     const DiagAcc &acc, hipStream_t st) {
+int large_diag_fused(qgx_model *m, const DiagConst &c, const DiagCall &dc, const DiagAcc &acc, hipStream_t st) {
     const SpecDev &d = m->d;
     if (!m->dg_z) QGX_HIP(hipMalloc((void **)&m->dg_z, (size_t)d.B * DZF * (d.N + large_zpad()) * d.N * sizeof(double2)));
     LargeCall x;
-    x.c = &c; x.qh = qh; x.Sh = Sh; x.dq_p = dq_p; x.dq_pp = dq_pp; x.acc = &acc;
+    x.c = &c; x.x = &dc; x.acc = &acc;
     return large_tiles(d.N, L_DIAG, m, x, st);
 }
 

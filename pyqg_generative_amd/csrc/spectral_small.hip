@@ -422,122 +422,166 @@ __global__ void k_invert_small(SpecDev d, const double2 *qh, double2 *ph, double
 }
 
 // ------------------------------------------------------------------ one increment of the time-averaged diagnostics
-// model.py::_calc_diagnostics on the small grids, a workgroup per member: _invert (psi, u, v of the current state),
-// p = irfft2(psi), xi = irfft2(-K^2 psi), the three pairs of real-space products, their transforms and the forcing's,
-// accumulation — what diag.hip runs as nine launches on the large grids.  Real-space fields pass through the model's own
-// arrays (u, v: kept, as _invert leaves them) and two scratch arrays; every global value is re-read by the thread that
-// wrote it or after a workgroup barrier.  The arithmetic is that of k_invert_small, k_qh_to_q_small, k_diag_xih,
-// k_diag_products, k_q_to_qh_small, k_diag_scale_S and k_diag_accumulate, expression by expression.
+// model.py::_calc_diagnostics on the small grids: _invert (psi, u, v of the current state), p = irfft2(psi),
+// xi = irfft2(-K^2 psi), the five pairs of real-space products, their transforms and the forcing's, accumulation — what
+// diag.hip runs as a dozen launches.  Ten STAGES of one packed transform each, written once (diag_stage_*) and run
+//   * all ten in sequence by one workgroup per member (k_diag_small),
+//   * one per workgroup, as (member, transform) workgroups (k_diag_inv_small, k_diag_fwd_small; k_diag_accumulate follows),
+// k_diag_small_reg further down keeps its own stages (work fields in registers instead of global memory) and shares the
+// element record and the viscosity split of diag_acc.hpp.  Real-space fields pass through the
+// model's own arrays (u, v: kept, as _invert leaves them) and the work fields of DiagCall; every global value is re-read by
+// the thread that wrote it or after a workgroup barrier.  The arithmetic is that of k_invert_small, k_qh_to_q_small, k_diag_xih,
+// k_diag_products, k_q_to_qh_small, k_diag_scale_S and k_diag_accumulate, expression by expression, and the product and
+// element formulas are the very functions of diag_acc.hpp: every form accumulates BIT-identical diagnostics (one exception,
+// measured: at 32 x 32 k_diag_small_reg's APEflux differs from the other forms in the last bit, 2e-16 relative).
+
+// What a stage works on: the workgroup's LDS field and grid, the sizes, member b's offsets into (B,2,N,NK) and (B,2,N,N)
+template <int NN> struct DiagWg {
+    double2 *Z;
+    Grid g;
+    int N, NK, LD, sz, rz;
+    size_t so, ro;
+};
 template <int NN>
-__global__ void k_diag_small(SpecDev d, DiagConst c, const double2 *qh, double2 *ph, double *u, double *v, double *P, double *XI,
-                             double2 *S3, double2 *S4, double2 *S5, double2 *Sh, double2 *S6, double2 *S7, const double *S, double weight,
-                             const double *q, const double2 *dq_p, const double2 *dq_pp, DiagAcc acc) {
-    double2 *Z = reinterpret_cast<double2 *>(qgx_smem);
+__device__ __forceinline__ DiagWg<NN> diag_wg(const SpecDev &d, int b) {
+    DiagWg<NN> w;
+    w.Z = reinterpret_cast<double2 *>(qgx_smem);
     int *pos_lds;
-    Grid g = make_grid(d, Z, pos_lds);
-    if (NN) { g.N = NN; g.NK = NN / 2 + 1; g.LD = NN + 1; }
-    const int N = NN ? NN : d.N, NK = NN ? NN / 2 + 1 : d.NK, LD = NN ? NN + 1 : d.LD, b = blockIdx.x;
-    const size_t so = (size_t)b * 2 * N * NK, ro = (size_t)b * 2 * N * N;
-    const int sz = N * NK, rz = N * N;
+    w.g = make_grid(d, w.Z, pos_lds);
+    if (NN) { w.g.N = NN; w.g.NK = NN / 2 + 1; w.g.LD = NN + 1; }
+    w.N = NN ? NN : d.N; w.NK = NN ? NN / 2 + 1 : d.NK; w.LD = NN ? NN + 1 : d.LD;
+    w.sz = w.N * w.NK; w.rz = w.N * w.N;
+    w.so = (size_t)b * 2 * w.sz; w.ro = (size_t)b * 2 * w.rz;
     __syncthreads();
-    // ---- _invert
-    for (int k = 0; k < 2; ++k) {
-        build_uv(Z, g, d, k, qh + so, qh + so + sz, ph + so + k * sz);
-        __syncthreads();
-        fft2d_inv_x<NN>(Z, N, LD, g.nrad, g.rad, g.tw);
-        for (int idx = threadIdx.x; idx < rz; idx += blockDim.x) {
-            const int y = idx / N, x = idx - y * N;
-            const double2 uv = Z[y * LD + x];
-            u[ro + k * rz + idx] = uv.x;
-            v[ro + k * rz + idx] = uv.y;
-        }
-        __syncthreads();
+    return w;
+}
+// the packed spectrum in the field -> real space, its two real fields to a[] and b[]
+template <int NN>
+__device__ __forceinline__ void diag_field_to_real(const DiagWg<NN> &w, double *a, double *b) {
+    fft2d_inv_x<NN>(w.Z, w.N, w.LD, w.g.nrad, w.g.rad, w.g.tw);
+    for (int idx = threadIdx.x; idx < w.rz; idx += blockDim.x) {
+        const int y = idx / w.N, x = idx - y * w.N;
+        const double2 t = w.Z[y * w.LD + x];
+        a[idx] = t.x;
+        b[idx] = t.y;
     }
-    // ---- p = irfft2(psi), both layers as one packed pair
-    build_pair(Z, g, ph + so, ph + so + sz, d.invN2);
+}
+// stage: _invert of layer k -> ph_k, u_k, v_k
+template <int NN>
+__device__ __forceinline__ void diag_stage_invert(const DiagWg<NN> &w, const SpecDev &d, const DiagCall &x, int k) {
+    build_uv(w.Z, w.g, d, k, x.qh + w.so, x.qh + w.so + w.sz, x.ph + w.so + k * w.sz);
     __syncthreads();
-    fft2d_inv_x<NN>(Z, N, LD, g.nrad, g.rad, g.tw);
-    for (int idx = threadIdx.x; idx < rz; idx += blockDim.x) {
-        const int y = idx / N, x = idx - y * N;
-        const double2 w = Z[y * LD + x];
-        P[ro + idx] = w.x;
-        P[ro + rz + idx] = w.y;
-    }
-    __syncthreads();
-    // ---- xi = irfft2(-K^2 psi): the spectrum goes through S3 (free until the first product transform)
-    for (int idx = threadIdx.x; idx < 2 * sz; idx += blockDim.x) {
-        const double w = -d.wv2[idx % sz];
-        const double2 p = ph[so + idx];
-        S3[so + idx] = make_double2(w * p.x, w * p.y);
-    }
-    __syncthreads();
-    build_pair(Z, g, S3 + so, S3 + so + sz, d.invN2);
-    __syncthreads();
-    fft2d_inv_x<NN>(Z, N, LD, g.nrad, g.rad, g.tw);
-    for (int idx = threadIdx.x; idx < rz; idx += blockDim.x) {
-        const int y = idx / N, x = idx - y * N;
-        const double2 w = Z[y * LD + x];
-        XI[ro + idx] = w.x;
-        XI[ro + rz + idx] = w.y;
-    }
-    __syncthreads();
-    // ---- the five pairs of products and the forcing, each: stage the pair, forward transform, unpack
-    for (int which = 0; which < 6; ++which) {
-        if (which == 3 && !S) continue;
-        for (int idx = threadIdx.x; idx < rz; idx += blockDim.x) {
-            const int y = idx / N, x = idx - y * N;
-            const size_t o = ro + idx;
-            double ra, rb;
-            if (which == 0) {
-                const double u1 = u[o], u2 = u[o + rz], v1 = v[o], v2 = v[o + rz];
-                const double ptpc = P[o] - P[o + rz];
-                const double ub = c.del1 * u1 + c.del2 * u2, vb = c.del1 * v1 + c.del2 * v2;
-                ra = ub * ptpc; rb = vb * ptpc;
-            } else if (which == 1) {
-                const double x1 = XI[o];
-                ra = u[o] * x1; rb = v[o] * x1;
-            } else if (which == 2) {
-                const double x2 = XI[o + rz];
-                ra = u[o + rz] * x2; rb = v[o + rz] * x2;
-            } else if (which == 3) {
-                ra = weight * S[o]; rb = weight * S[o + rz];
-            } else if (which == 4) {            // (u_1 q_1, v_1 q_1): the enstrophy flux and the tendency of Dissspec
-                const double q1 = q[o];
-                ra = u[o] * q1; rb = v[o] * q1;
-            } else {
-                const double q2 = q[o + rz];
-                ra = u[o + rz] * q2; rb = v[o + rz] * q2;
+    diag_field_to_real(w, x.u + w.ro + k * w.rz, x.v + w.ro + k * w.rz);
+}
+// stage: (f(psi_1) + i f(psi_2)) -> real space; f = 1: p (into P), XIH: f = -K^2: xi (into XI), its spectrum staged in S3 (free
+// until the first product transform).  RECOMPUTE: psi is formed from qh again and staged (S4 / S3) — the (member, transform)
+// workgroups do not wait for the invert stages; otherwise the ph that the invert stages stored is read
+template <int NN, bool RECOMPUTE>
+__device__ __forceinline__ void diag_stage_psi_real(const DiagWg<NN> &w, const SpecDev &d, const DiagCall &x, bool XIH) {
+    const double2 *src = x.ph + w.so;
+    if (RECOMPUTE || XIH) {
+        double2 *T = XIH ? x.S3 : x.S4;
+        for (int idx = threadIdx.x; idx < 2 * w.sz; idx += blockDim.x) {
+            const int k = idx / w.sz, r = idx - k * w.sz;
+            double2 p;
+            if constexpr (RECOMPUTE) p = invert_layer(d, k, r, x.qh[w.so + r], x.qh[w.so + w.sz + r]);
+            else p = x.ph[w.so + idx];
+            if (XIH) {
+                const double wk = -d.wv2[r];
+                p = make_double2(wk * p.x, wk * p.y);
             }
-            Z[y * LD + x] = make_double2(ra, rb);
+            T[w.so + idx] = p;
         }
         __syncthreads();
-        fft2d_fwd_x<NN>(Z, N, LD, g.nrad, g.rad, g.tw);
-        double2 *dst = which == 0 ? S3 : (which == 1 ? S4 : (which == 2 ? S5 : (which == 3 ? Sh : (which == 4 ? S6 : S7))));
-        for (int idx = threadIdx.x; idx < sz; idx += blockDim.x) {
-            const int j = idx / NK, i = idx - j * NK;
-            double2 s0, s1;
-            unpack_pair(Z, g, j, i, s0, s1);
-            dst[so + idx] = s0;
-            dst[so + sz + idx] = s1;
+        src = T + w.so;
+    }
+    build_pair(w.Z, w.g, src, src + w.sz, d.invN2);
+    __syncthreads();
+    double *dst = XIH ? x.XI : x.P;
+    diag_field_to_real(w, dst + w.ro, dst + w.ro + w.rz);
+}
+// stage: product pair `which` (diag_product_pair; 3: the forcing) -> its two half spectra (diag_spectrum)
+template <int NN>
+__device__ __forceinline__ void diag_stage_product(const DiagWg<NN> &w, const DiagConst &c, const DiagCall &x, int which) {
+    // pair(o) -> the pair of the pixel at offset o.  Three shapes of loads, chosen OUTSIDE the pixel loop so that a pixel's
+    // loads go out together (chosen per load inside it, each waited for the one before: the chained kernel lost 10 %)
+    const auto fill = [&](auto pair) {
+        for (int idx = threadIdx.x; idx < w.rz; idx += blockDim.x) {
+            const int y = idx / w.N, xx = idx - y * w.N;
+            w.Z[y * w.LD + xx] = pair(w.ro + idx);
         }
+    };
+    const size_t rz = w.rz;
+    if (which == 0) {            // both layers of u, v, p
+        fill([&](size_t o) { return diag_product_pair(0, c, 0., make_double2(x.u[o], x.v[o]), make_double2(x.u[o + rz], x.v[o + rz]), x.P[o], x.P[o + rz]); });
+    } else if (which == 3) {     // both layers of the forcing
+        fill([&](size_t o) { return diag_product_pair(3, c, x.weight, make_double2(0., 0.), make_double2(0., 0.), x.S[o], x.S[o + rz]); });
+    } else {                     // u, v and xi or q of the one layer the pair reads (passed for both: the pair picks its own)
+        const size_t k = diag_pair_layers(which) == 2 ? rz : 0;
+        const double *f = which <= 2 ? x.XI : x.q;
+        fill([&](size_t o) {
+            const double2 uv = make_double2(x.u[o + k], x.v[o + k]);
+            const double fk = f[o + k];
+            return diag_product_pair(which, c, 0., uv, uv, fk, fk);
+        });
+    }
+    __syncthreads();
+    fft2d_fwd_x<NN>(w.Z, w.N, w.LD, w.g.nrad, w.g.rad, w.g.tw);
+    double2 *dst = diag_spectrum(x, which);
+    for (int idx = threadIdx.x; idx < w.sz; idx += blockDim.x) {
+        const int j = idx / w.NK, i = idx - j * w.NK;
+        double2 s0, s1;
+        unpack_pair(w.Z, w.g, j, i, s0, s1);
+        dst[w.so + idx] = s0;
+        dst[w.so + w.sz + idx] = s1;
+    }
+}
+
+// the whole increment, a workgroup per member
+template <int NN>
+__global__ void k_diag_small(SpecDev d, DiagConst c, DiagCall x, DiagAcc acc) {
+    const int b = blockIdx.x;
+    const DiagWg<NN> w = diag_wg<NN>(d, b);
+    for (int k = 0; k < 2; ++k) {
+        diag_stage_invert(w, d, x, k);
+        __syncthreads();
+    }
+    diag_stage_psi_real<NN, false>(w, d, x, false);
+    __syncthreads();
+    diag_stage_psi_real<NN, false>(w, d, x, true);
+    __syncthreads();
+    for (int which = 0; which < 6; ++which) {
+        if (which == 3 && !x.S) continue;
+        diag_stage_product(w, c, x, which);
         __syncthreads();
     }
     // ---- accumulate (each thread re-reads the transforms it unpacked itself)
-    for (int idx = threadIdx.x; idx < sz; idx += blockDim.x) {
-        const int j = idx / NK, i = idx - j * NK;
-        const size_t o = so + idx, o2 = (size_t)b * sz + idx;
-        const double2 zero = make_double2(0., 0.);
-        if (c.nu) {      // molecular viscosity: part of the parameterization's tendency (diag_add_visc)
-            double2 s1 = S ? Sh[o] : zero, s2 = S ? Sh[o + sz] : zero;
-            diag_add_visc(d, c, b, idx, qh[o], qh[o + sz], ph[o], ph[o + sz], s1, s2);
-            diag_accumulate_elem(d, c, acc, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], S3[o], S3[o + sz], S4[o], S4[o + sz],
-                                 S5[o], S5[o + sz], true, s1, s2, S6[o], S6[o + sz], S7[o], S7[o + sz],
-                                 dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
-        } else
-        diag_accumulate_elem(d, c, acc, idx, i, j, o, o2, sz, qh[o], qh[o + sz], ph[o], ph[o + sz], S3[o], S3[o + sz], S4[o], S4[o + sz],
-                             S5[o], S5[o + sz], S != nullptr, S ? Sh[o] : zero, S ? Sh[o + sz] : zero, S6[o], S6[o + sz], S7[o], S7[o + sz],
-                             dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
+    for (int idx = threadIdx.x; idx < w.sz; idx += blockDim.x) {
+        const int j = idx / w.NK, i = idx - j * w.NK;
+        diag_accumulate(d, c, acc, b, idx, i, j, w.sz, [&] { return diag_elem_load(x, w.so + idx, w.sz); });
     }
+}
+
+// ------------------------------------------------------------------ the same increment spread over several workgroups per member
+// One workgroup per member is a chain of ten dependent 2-D transforms on ONE CU (about 110 us for a single member, and half
+// of the CUs idle at 128).  The four inverse transforms depend on qh alone and the six forward transforms on their results
+// alone, so they are run as two launches of (member, transform) workgroups followed by diag.hip's accumulation kernel:
+// three short launches instead of one long one.
+//   which 0, 1: _invert of layer k;  2: p = irfft2(psi);  3: xi = irfft2(-K^2 psi)
+template <int NN>
+__global__ void k_diag_inv_small(SpecDev d, DiagCall x) {
+    const int which = blockIdx.x & 3;
+    const DiagWg<NN> w = diag_wg<NN>(d, blockIdx.x >> 2);
+    if (which < 2) diag_stage_invert(w, d, x, which);
+    else diag_stage_psi_real<NN, true>(w, d, x, which == 3);
+}
+// which 0..5: the product pairs and the forcing
+template <int NN>
+__global__ void k_diag_fwd_small(SpecDev d, DiagConst c, DiagCall x, int nwhich) {
+    const int b = blockIdx.x / nwhich;
+    int which = blockIdx.x - b * nwhich;
+    if (!x.S && which >= 3) ++which;                 // no forcing: five pairs, the slot of the forcing is skipped
+    diag_stage_product(diag_wg<NN>(d, b), c, x, which);
 }
 
 // ------------------------------------------------------------------ the same increment with its work fields in registers
@@ -548,7 +592,9 @@ __global__ void k_diag_small(SpecDev d, DiagConst c, const double2 *qh, double2 
 // product pair straight into the LDS field it has just read, and accumulates as soon as a transform is in LDS: APEflux
 // after the (ub ptpc, vb ptpc) transform, KEflux after the two (u_k xi_k, v_k xi_k) ones (J_1 held in registers), the rest
 // after the last transform (the forcing's and the layer-1 enstrophy flux's spectra held in registers).  Same device
-// functions, same expressions, same element -> thread map: the accumulators are BIT-identical to k_diag_small's.  It stores
+// functions, same expressions, same element -> thread map: the accumulators are BIT-identical to k_diag_small's at 48 x 48
+// and 64 x 64; at 32 x 32 APEflux alone differs in the last bit (2e-16 relative: which products of a sum the
+// compiler fuses is its own choice per instance, diag_acc.hpp).  It stores
 // ph but no u, v (the caller marks them stale: qgx_get inverts on demand).  Grids up to 64 x 64 (at 96 x 96 nine pixels per
 // thread do not fit the 128 registers of a 1024-thread workgroup).
 // LDS of k_diag_small_reg: the field + tables of small_lds_bytes(), then the forcing's two half spectra
@@ -561,8 +607,9 @@ __host__ __device__ constexpr size_t diag_reg_lds_bytes(int N) { return diag_reg
 // two enstrophy-flux ones, with every other accumulator (5) — instead of ten in one chain on half of the CUs (128 members).
 // Both halves invert and both store the same psi; the accumulators they add to are disjoint.  0: one workgroup per member.
 template <int NN, int HALF = 0>
-__global__ __launch_bounds__(1024) void k_diag_small_reg(SpecDev d, DiagConst c, const double2 *qh, double2 *ph, const double *S, double weight,
-                                                         const double *q, const double2 *dq_p, const double2 *dq_pp, DiagAcc acc) {
+__global__ __launch_bounds__(1024) void k_diag_small_reg(SpecDev d, DiagConst c, DiagIn x, DiagAcc acc) {
+    const double2 *qh = x.qh; double2 *ph = x.ph; const double *S = x.S; const double weight = x.weight; const double *q = x.q;
+    const double2 *dq_p = x.dq_p, *dq_pp = x.dq_pp;
     double2 *Z = reinterpret_cast<double2 *>(qgx_smem);
     int *pos_lds;
     Grid g = make_grid(d, Z, pos_lds);
@@ -637,9 +684,9 @@ __global__ __launch_bounds__(1024) void k_diag_small_reg(SpecDev d, DiagConst c,
             const int j = idx / NK, i = idx - j * NK;
             double2 A3, B3;
             unpack_pair(Z, g, j, i, A3, B3);
-            const double2 p1 = ph0[idx], p2 = ph1[idx];
-            diag_accumulate_elem<1>(d, c, acc, idx, i, j, so + idx, (size_t)b * sz + idx, sz, zero, zero, p1, p2, A3, B3, zero, zero, zero, zero,
-                                    false, zero, zero, zero, zero, zero, zero, zero, zero, zero, zero);
+            DiagElem e;
+            e.p1 = ph0[idx]; e.p2 = ph1[idx]; e.A3 = A3; e.B3 = B3;
+            diag_accumulate_elem<1>(d, c, acc, idx, i, j, so + idx, (size_t)b * sz + idx, sz, e);
         }
     }
     __syncthreads();
@@ -686,9 +733,9 @@ __global__ __launch_bounds__(1024) void k_diag_small_reg(SpecDev d, DiagConst c,
             const int j = idx / NK, i = idx - j * NK;
             double2 A5, B5;
             unpack_pair(Z, g, j, i, A5, B5);
-            const double2 p1 = ph0[idx], p2 = ph1[idx];
-            diag_accumulate_elem<2, true>(d, c, acc, idx, i, j, so + idx, (size_t)b * sz + idx, sz, zero, zero, p1, p2, zero, zero, J1[r], zero, A5, B5,
-                                    false, zero, zero, zero, zero, zero, zero, zero, zero, zero, zero);
+            DiagElem e;
+            e.p1 = ph0[idx]; e.p2 = ph1[idx]; e.A4 = J1[r]; e.A5 = A5; e.B5 = B5;
+            diag_accumulate_elem<2, true>(d, c, acc, idx, i, j, so + idx, (size_t)b * sz + idx, sz, e);
         }
     }
     __syncthreads();
@@ -752,126 +799,17 @@ __global__ __launch_bounds__(1024) void k_diag_small_reg(SpecDev d, DiagConst c,
             unpack_pair(Z, g, j, i, A7, B7);
             const double2 q1 = qh0[idx], q2 = qh1[idx];
             const double2 p1 = ph0[idx], p2 = ph1[idx];
-            const size_t o = so + idx;
-            if (c.nu) {      // molecular viscosity: part of the parameterization's tendency (diag_add_visc)
-                double2 s1 = S ? SH[idx] : zero, s2 = S ? SH[sz + idx] : zero;
-                diag_add_visc(d, c, b, idx, q1, q2, p1, p2, s1, s2);
-                diag_accumulate_elem<4, true>(d, c, acc, idx, i, j, o, (size_t)b * sz + idx, sz, q1, q2, p1, p2, zero, zero, zero, zero, zero, zero,
-                                              true, s1, s2, G1[r], zero, A7, B7, dq_p[o], dq_p[o + sz], dq_pp[o], dq_pp[o + sz]);
-            } else
-            diag_accumulate_elem<4, true>(d, c, acc, idx, i, j, o, (size_t)b * sz + idx, sz, q1, q2, p1, p2, zero, zero, zero, zero, zero, zero,
-                                          S != nullptr, S ? SH[idx] : zero, S ? SH[sz + idx] : zero, G1[r], zero, A7, B7, dq_p[o], dq_p[o + sz],
-                                          dq_pp[o], dq_pp[o + sz]);
+            diag_accumulate<4, true>(d, c, acc, b, idx, i, j, sz, [&] {
+                const size_t o = so + idx;
+                DiagElem e;
+                e.has_S = S != nullptr;
+                e.s1 = S ? SH[idx] : zero; e.s2 = S ? SH[sz + idx] : zero;
+                e.q1 = q1; e.q2 = q2; e.p1 = p1; e.p2 = p2;
+                e.A6 = G1[r]; e.A7 = A7; e.B7 = B7;
+                e.hp1 = dq_p[o]; e.hp2 = dq_p[o + sz]; e.hpp1 = dq_pp[o]; e.hpp2 = dq_pp[o + sz];
+                return e;
+            });
         }
-    }
-}
-
-// ------------------------------------------------------------------ the same increment spread over several workgroups per member
-// One workgroup per member is a chain of ten dependent 2-D transforms on ONE CU (about 110 us for a single member, and half
-// of the CUs idle at 128).  The four inverse transforms depend on qh alone and the six forward transforms on their results
-// alone, so they are run as two launches of (member, transform) workgroups followed by diag.hip's accumulation kernel:
-// three short launches instead of one long one.  Same device functions, same expressions: bit-identical to k_diag_small.
-//   which 0, 1: _invert of layer k -> ph_k, u_k, v_k;  2: p = irfft2(psi) (both layers packed);  3: xi = irfft2(-K^2 psi)
-template <int NN>
-__global__ void k_diag_inv_small(SpecDev d, const double2 *qh, double2 *ph, double *u, double *v, double *P, double *XI,
-                                 double2 *T3, double2 *T4) {
-    double2 *Z = reinterpret_cast<double2 *>(qgx_smem);
-    int *pos_lds;
-    Grid g = make_grid(d, Z, pos_lds);
-    if (NN) { g.N = NN; g.NK = NN / 2 + 1; g.LD = NN + 1; }
-    const int N = NN ? NN : d.N, NK = NN ? NN / 2 + 1 : d.NK, LD = NN ? NN + 1 : d.LD;
-    const int b = blockIdx.x >> 2, which = blockIdx.x & 3;
-    const size_t so = (size_t)b * 2 * N * NK, ro = (size_t)b * 2 * N * N;
-    const int sz = N * NK, rz = N * N;
-    __syncthreads();
-    if (which < 2) {
-        const int k = which;
-        build_uv(Z, g, d, k, qh + so, qh + so + sz, ph + so + k * sz);
-        __syncthreads();
-        fft2d_inv_x<NN>(Z, N, LD, g.nrad, g.rad, g.tw);
-        for (int idx = threadIdx.x; idx < rz; idx += blockDim.x) {
-            const int y = idx / N, x = idx - y * N;
-            const double2 uv = Z[y * LD + x];
-            u[ro + k * rz + idx] = uv.x;
-            v[ro + k * rz + idx] = uv.y;
-        }
-        return;
-    }
-    // psi (which == 2) or -K^2 psi (which == 3) of both layers into this workgroup's own scratch, then one packed pair
-    double2 *T = which == 2 ? T4 : T3;
-    for (int idx = threadIdx.x; idx < 2 * sz; idx += blockDim.x) {
-        const int k = idx / sz, r = idx - k * sz;
-        const double2 p = invert_layer(d, k, r, qh[so + r], qh[so + sz + r]);
-        if (which == 2) T[so + idx] = p;
-        else {
-            const double w = -d.wv2[r];
-            T[so + idx] = make_double2(w * p.x, w * p.y);
-        }
-    }
-    __syncthreads();
-    build_pair(Z, g, T + so, T + so + sz, d.invN2);
-    __syncthreads();
-    fft2d_inv_x<NN>(Z, N, LD, g.nrad, g.rad, g.tw);
-    double *dst = which == 2 ? P : XI;
-    for (int idx = threadIdx.x; idx < rz; idx += blockDim.x) {
-        const int y = idx / N, x = idx - y * N;
-        const double2 w = Z[y * LD + x];
-        dst[ro + idx] = w.x;
-        dst[ro + rz + idx] = w.y;
-    }
-}
-
-// which 0..5: the product pair (or the forcing, which == 3) of k_diag_small, transformed and unpacked into its spectrum array
-template <int NN>
-__global__ void k_diag_fwd_small(SpecDev d, DiagConst c, const double *u, const double *v, const double *P, const double *XI,
-                                 const double *q, const double *S, double weight, double2 *S3, double2 *S4, double2 *S5, double2 *Sh,
-                                 double2 *S6, double2 *S7, int nwhich) {
-    double2 *Z = reinterpret_cast<double2 *>(qgx_smem);
-    int *pos_lds;
-    Grid g = make_grid(d, Z, pos_lds);
-    if (NN) { g.N = NN; g.NK = NN / 2 + 1; g.LD = NN + 1; }
-    const int N = NN ? NN : d.N, NK = NN ? NN / 2 + 1 : d.NK, LD = NN ? NN + 1 : d.LD;
-    const int b = blockIdx.x / nwhich;
-    int which = blockIdx.x - b * nwhich;
-    if (!S && which >= 3) ++which;                 // no forcing: five pairs, the slot of the forcing is skipped
-    const size_t so = (size_t)b * 2 * N * NK, ro = (size_t)b * 2 * N * N;
-    const int sz = N * NK, rz = N * N;
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < rz; idx += blockDim.x) {
-        const int y = idx / N, x = idx - y * N;
-        const size_t o = ro + idx;
-        double ra, rb;
-        if (which == 0) {
-            const double u1 = u[o], u2 = u[o + rz], v1 = v[o], v2 = v[o + rz];
-            const double ptpc = P[o] - P[o + rz];
-            const double ub = c.del1 * u1 + c.del2 * u2, vb = c.del1 * v1 + c.del2 * v2;
-            ra = ub * ptpc; rb = vb * ptpc;
-        } else if (which == 1) {
-            const double x1 = XI[o];
-            ra = u[o] * x1; rb = v[o] * x1;
-        } else if (which == 2) {
-            const double x2 = XI[o + rz];
-            ra = u[o + rz] * x2; rb = v[o + rz] * x2;
-        } else if (which == 3) {
-            ra = weight * S[o]; rb = weight * S[o + rz];
-        } else if (which == 4) {
-            const double q1 = q[o];
-            ra = u[o] * q1; rb = v[o] * q1;
-        } else {
-            const double q2 = q[o + rz];
-            ra = u[o + rz] * q2; rb = v[o + rz] * q2;
-        }
-        Z[y * LD + x] = make_double2(ra, rb);
-    }
-    __syncthreads();
-    fft2d_fwd_x<NN>(Z, N, LD, g.nrad, g.rad, g.tw);
-    double2 *dst = which == 0 ? S3 : (which == 1 ? S4 : (which == 2 ? S5 : (which == 3 ? Sh : (which == 4 ? S6 : S7))));
-    for (int idx = threadIdx.x; idx < sz; idx += blockDim.x) {
-        const int j = idx / NK, i = idx - j * NK;
-        double2 s0, s1;
-        unpack_pair(Z, g, j, i, s0, s1);
-        dst[so + idx] = s0;
-        dst[so + sz + idx] = s1;
     }
 }
 
@@ -967,47 +905,31 @@ int small_invert(const SpecDev &d, const ModelOpts &o, const double2 *qh, double
     QGX_HIP(hipGetLastError());
     return QGX_OK;
 }
-// the one-workgroup-per-member increment with its work fields in registers (k_diag_small_reg): grids up to 64 x 64; stores no
-// ph, u, v.  -> false: no such kernel for this grid
+// the one-workgroup-per-member increment with its work fields in registers (k_diag_small_reg): grids up to 64 x 64; stores
+// ph, no u, v.  -> false: no such kernel for this grid.  halves: two workgroups per member (k_diag_small_reg HALF)
 bool small_diag_increment_reg_ok(const SpecDev &d) { return d.N == 32 || d.N == 48 || d.N == 64; }
-int small_diag_increment_reg(const SpecDev &d, const DiagConst &c, const double2 *qh, double2 *ph, const double *S, double weight, const double *q,
-                             const double2 *dq_p, const double2 *dq_pp, const DiagAcc &a, hipStream_t st, bool halves) {
-    if (halves) {      // two workgroups per member (k_diag_small_reg HALF)
-        switch (d.N) {
-            case 32: hipLaunchKernelGGL((k_diag_small_reg<32, 1>), dim3(2 * d.B), dim3(1024), diag_reg_lds_bytes(32), st, d, c, qh, ph, S, weight, q, dq_p, dq_pp, a); break;
-            case 48: hipLaunchKernelGGL((k_diag_small_reg<48, 1>), dim3(2 * d.B), dim3(1024), diag_reg_lds_bytes(48), st, d, c, qh, ph, S, weight, q, dq_p, dq_pp, a); break;
-            case 64: hipLaunchKernelGGL((k_diag_small_reg<64, 1>), dim3(2 * d.B), dim3(1024), diag_reg_lds_bytes(64), st, d, c, qh, ph, S, weight, q, dq_p, dq_pp, a); break;
-            default: QGX_REQUIRE(false, "small_diag_increment_reg: no kernel for N = %d", d.N);
+int small_diag_increment_reg(const SpecDev &d, const DiagConst &c, const DiagCall &x, const DiagAcc &a, hipStream_t st, bool halves) {
+    QGX_REQUIRE(small_diag_increment_reg_ok(d), "small_diag_increment_reg: no kernel for N = %d", d.N);
+    QGX_DISPATCH_N(d.N, {
+        if constexpr (NN == 32 || NN == 48 || NN == 64) {
+            const auto k = halves ? (k_diag_small_reg<NN, 1>) : (k_diag_small_reg<NN, 0>);
+            hipLaunchKernelGGL(k, dim3((halves ? 2 : 1) * d.B), dim3(1024), diag_reg_lds_bytes(NN), st, d, c, (DiagIn)x, a);
         }
-        QGX_HIP(hipGetLastError());
-        return QGX_OK;
-    }
-    switch (d.N) {
-        case 32: hipLaunchKernelGGL(k_diag_small_reg<32>, dim3(d.B), dim3(1024), diag_reg_lds_bytes(32), st, d, c, qh, ph, S, weight, q, dq_p, dq_pp, a); break;
-        case 48: hipLaunchKernelGGL(k_diag_small_reg<48>, dim3(d.B), dim3(1024), diag_reg_lds_bytes(48), st, d, c, qh, ph, S, weight, q, dq_p, dq_pp, a); break;
-        case 64: hipLaunchKernelGGL(k_diag_small_reg<64>, dim3(d.B), dim3(1024), diag_reg_lds_bytes(64), st, d, c, qh, ph, S, weight, q, dq_p, dq_pp, a); break;
-        default: QGX_REQUIRE(false, "small_diag_increment_reg: no kernel for N = %d", d.N);
-    }
+    })
     QGX_HIP(hipGetLastError());
     return QGX_OK;
 }
-int small_diag_increment(const SpecDev &d, const DiagConst &c, const double2 *qh, double2 *ph, double *u, double *v, double *P,
-                         double *XI, double2 *S3, double2 *S4, double2 *S5, double2 *Sh, double2 *S6, double2 *S7, const double *S,
-                         double weight, const double *q, const double2 *dq_p, const double2 *dq_pp, const DiagAcc &a, hipStream_t st) {
-    QGX_DISPATCH_N(d.N, hipLaunchKernelGGL(k_diag_small<NN>, dim3(d.B), dim3(1024), small_lds_bytes(d), st, d, c, qh, ph, u, v, P, XI,
-                                           S3, S4, S5, Sh, S6, S7, S, weight, q, dq_p, dq_pp, a))
+int small_diag_increment(const SpecDev &d, const DiagConst &c, const DiagCall &x, const DiagAcc &a, hipStream_t st) {
+    QGX_DISPATCH_N(d.N, hipLaunchKernelGGL(k_diag_small<NN>, dim3(d.B), dim3(1024), small_lds_bytes(d), st, d, c, x, a))
     QGX_HIP(hipGetLastError());
     return QGX_OK;
 }
 // the transforms of one increment as (member, transform) workgroups: inverse set, then forward set (k_diag_accumulate follows)
-int small_diag_transforms_wide(const SpecDev &d, const DiagConst &c, const double2 *qh, double2 *ph, double *u, double *v, double *P,
-                               double *XI, double2 *S3, double2 *S4, double2 *S5, double2 *Sh, double2 *S6, double2 *S7, const double *S,
-                               double weight, const double *q, hipStream_t st) {
-    const int nwhich = S ? 6 : 5;
+int small_diag_transforms_wide(const SpecDev &d, const DiagConst &c, const DiagCall &x, hipStream_t st) {
+    const int nwhich = x.S ? 6 : 5;
     QGX_DISPATCH_N(d.N, {
-        hipLaunchKernelGGL(k_diag_inv_small<NN>, dim3(4 * d.B), dim3(1024), small_lds_bytes(d), st, d, qh, ph, u, v, P, XI, S3, S4);
-        hipLaunchKernelGGL(k_diag_fwd_small<NN>, dim3(nwhich * d.B), dim3(1024), small_lds_bytes(d), st, d, c, (const double *)u,
-                           (const double *)v, (const double *)P, (const double *)XI, q, S, weight, S3, S4, S5, Sh, S6, S7, nwhich);
+        hipLaunchKernelGGL(k_diag_inv_small<NN>, dim3(4 * d.B), dim3(1024), small_lds_bytes(d), st, d, x);
+        hipLaunchKernelGGL(k_diag_fwd_small<NN>, dim3(nwhich * d.B), dim3(1024), small_lds_bytes(d), st, d, c, x, nwhich);
     })
     QGX_HIP(hipGetLastError());
     return QGX_OK;

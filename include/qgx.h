@@ -529,6 +529,11 @@ int qgx_histogram(const void *x_dev, int is_double, int64_t R, int64_t T, int64_
  * in qgx_train.h, which this header includes. */
 #include "qgx_train.h"
 
+/* Training of the convolutional nets (AndrewCNN: OLSModel.net and every net built from it): the circular convolution, its
+ * data gradient and its weight gradient as stateless layer operations; autograd, BatchNorm and Adam stay with the caller
+ * (tools/train_CNN.py).  Declared and documented in qgx_conv_train.h, which this header includes. */
+#include "qgx_conv_train.h"
+
 /* ---- latent noise ------------------------------------------------------------
  * z <- a z + b xi with xi ~ N(0,1) from Philox4x32-10 (stochastic_pyqg.py:43-49).  z: (B, n_per_member) float or double,
  * n_per_member a positive multiple of 4; a == 0 overwrites z (its previous contents are not read).  Counter of the four

@@ -185,6 +185,16 @@ TRAIN_SYMBOLS = [
     ('qgx_ann_trainer_write', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
 ]
 
+# what include/qgx_conv_train.h declares: the circular convolution and its two gradients (tools/train_CNN.py)
+_CONV = [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]                                       # B, N, cin, cout, k
+_CONV_WORK = [C.c_void_p, C.c_size_t, C.c_void_p]                                             # work, work_bytes, stream
+CONV_TRAIN_SYMBOLS = [
+    ('qgx_conv2d_workspace', C.c_int, _CONV + [C.POINTER(C.c_size_t)]),
+    ('qgx_conv2d_forward', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + _CONV + _CONV_WORK),
+    ('qgx_conv2d_backward_data', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + _CONV + _CONV_WORK),
+    ('qgx_conv2d_backward_weight', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + _CONV + _CONV_WORK),
+]
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -197,7 +207,7 @@ def _load():
     # Load torch's first — torch finds no GPU when it is handed the other runtime.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS + TRAIN_SYMBOLS:
+    for name, res, args in SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS + TRAIN_SYMBOLS + CONV_TRAIN_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -38,7 +38,8 @@ struct ConvGArgs {
 constexpr int G_CC = 32;              // input channels per staged chunk
 constexpr int G_STRIDE = G_CC + 4;    // floats per patch pixel: 16-byte reads of consecutive pixels fall on different banks
 
-template <int NT, int MT>
+// LINEAR (training, conv_train.hip): NHWC out with the bias alone — no ReLU, no BatchNorm affine, scale / shift not read
+template <int NT, int MT, bool LINEAR = false>
 __global__ __launch_bounds__(256) void k_convg(ConvGArgs a) {
     constexpr int G_MT = MT;          // M-tiles per wave
     float *patch = reinterpret_cast<float *>(conv_smem);
@@ -169,7 +170,14 @@ __global__ __launch_bounds__(256) void k_convg(ConvGArgs a) {
             const int co = (nt0 + nt) * 32 + li;
             if (co >= cstore) continue;            // padded output channels: nothing past the channels the buffer holds
             const float bias = a.bias[co];
-            if (a.final) {
+            if constexpr (LINEAR) {
+                float *o = a.out + ((size_t)b * N * N + (size_t)y0 * N) * cstore + co;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int p = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    o[(size_t)p * cstore] = acc[mt][nt][r] + bias;
+                }
+            } else if (a.final) {
                 float *o = a.out + ((size_t)b * cstore + co) * N * N + (size_t)y0 * N;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -340,6 +348,30 @@ static int launch_convg(qgx_generator *g, int layer, const LayerHost &L, bool fi
     dim3 grid(B * (N / R), ny), block(256);
     auto kern = R * N / 32 > 8 ? (nt == 2 ? k_convg<2, 3> : k_convg<1, 3>) : (nt == 2 ? k_convg<2, 2> : k_convg<1, 2>);
     return launch_conv_kernel(kern, grid, block, lds, st, a);
+}
+
+// One convolution outside any generator handle (conv_train.hip): NHWC (B, N, N, cinp) in, NHWC (B, N, N, cstore) out,
+// out = conv + bias; `w` packed as cnn_pack_net_arch packs a hidden layer ([group][coutp][8], one zero group at the end),
+// `bias` [coutp].  The tile shapes are launch_convg's, so the summation order is that of the generator's layers.
+bool convg_linear_ok(int64_t B, int N, int coutp, int ks) {
+    const int R0 = choose_rows(N);
+    if (B < 1 || N < 16 || N > 128 || R0 <= 0 || N % R0 || B * N * N > (int64_t)1 << 29) return false;
+    const int ntf = coutp / 32, ny = ntf / tiles_per_wg(ntf);
+    const int R = rows_generic((int)B, N, ny);
+    return R > 0 && lds_generic(R, ks, N) <= 160 * 1024;
+}
+int launch_convg_linear(const float *in, float *out, const float *w, const float *bias, int B, int N, int cinp, int coutp,
+                        int cstore, int ks, hipStream_t st) {
+    QGX_REQUIRE(convg_linear_ok(B, N, coutp, ks), "conv2d (generic engine): N = %d is not supported (B = %d; 16, 32, 48, 64, 96 or 128)", N, B);
+    const int ntf = coutp / 32, nt = tiles_per_wg(ntf), ny = ntf / nt;
+    const int R = rows_generic(B, N, ny);
+    ConvGArgs a = {};
+    a.in = in; a.out = out; a.w = w; a.bias = bias; a.scale = nullptr; a.shift = nullptr;
+    a.N = N; a.R = R; a.ks = ks; a.cin = cinp; a.cinp = cinp; a.coutp = coutp; a.cstore = cstore;
+    a.planar_in = 0; a.final = 0;
+    dim3 grid(B * (N / R), ny), block(256);
+    auto kern = R * N / 32 > 8 ? (nt == 2 ? k_convg<2, 3, true> : k_convg<1, 3, true>) : (nt == 2 ? k_convg<2, 2, true> : k_convg<1, 2, true>);
+    return launch_conv_kernel(kern, grid, block, lds_generic(R, ks, N), st, a);
 }
 
 // the n_layers convolutions: x planar (B, n_in, N, N) -> y planar (B, n_out, N, N); activations alternate actA, actB

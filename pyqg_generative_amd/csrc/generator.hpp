@@ -170,6 +170,10 @@ void cnn_arch_to_weights(const qgx_cnn_arch *a, qgx_cnn_weights *w);     // ... 
 int cnn_pack_net_arch(NetHost &net, const qgx_cnn_arch *a);
 int cnng_convs(qgx_generator *g, const NetHost &net, const float *x, float *y, int B, int N, hipStream_t st);
 bool cnng_size_ok(const NetHost &net, int B, int N);
+// ... one convolution with the bias alone, NHWC in and out, outside any handle: the layer operation of conv_train.hip
+bool convg_linear_ok(int64_t B, int N, int coutp, int ks);       // no HIP call
+int launch_convg_linear(const float *in, float *out, const float *w, const float *bias, int B, int N, int cinp, int coutp,
+                        int cstore, int ks, hipStream_t st);
 // conv.hip helpers the generic launchers share
 int ensure_dynamic_lds(const void *kern, int bytes);
 int choose_rows(int N);

@@ -261,6 +261,7 @@ struct qgx_model {
     int dg_every = 0;
     double *dg_R[7] = {};
     double *dg_S[7] = {};
+    double *dg_Sdm = nullptr;              // an external forcing less its layer means, where the step de-means it (diag_increment)
     double *dg_acc[qgx::N_DIAGS] = {};
     double2 *dg_z = nullptr;               // large grids: the four work fields of the three-launch increment (spectral_large.hip)
     // the two internal streams of a step in halves (model.hip::qgx_step) and their fork / join events
@@ -278,7 +279,7 @@ struct qgx_model {
 namespace qgx {
 // THE list of the model's device buffers with a leading member axis: f(pointer, bytes per member) for each, null ones
 // included.  qgx_step slices its half-ensembles with it and qgx_destroy frees what it yields: a new per-member buffer is
-// added here and nowhere else.  The sizes are those of qgx_create, diag_ensure_alloc, large_diag_fused, backscatter_prepare,
+// added here and nowhere else.  The sizes are those of qgx_create, diag_ensure_alloc, diag_increment, large_diag_fused, backscatter_prepare,
 // qgx_set_viscosity / _backscatter and step_sib_ensure.  z_elem: bytes of a latent-noise element in use (allocated: double).
 template <class F>
 void for_each_member_buffer(qgx_model &m, size_t z_elem, F &&f) {
@@ -291,6 +292,7 @@ void for_each_member_buffer(qgx_model &m, size_t z_elem, F &&f) {
     f(m.z, 2 * N * N * z_elem); f(m.xi, 2 * N * N * z_elem);
     f(m.zbuf, ZF * zfield); f(m.dg_z, DZF * zfield);
     for (double *&p : m.dg_R) f(p, real);
+    f(m.dg_Sdm, real);
     for (double *&p : m.dg_S) f(p, spec);                                           // (complex fields kept as doubles)
     for (int i = 0; i < N_DIAGS; ++i) f(m.dg_acc[i], (i < 2 ? 2 : 1) * N * NK * sizeof(double));
     f(m.visc_nu, sizeof(double));
@@ -363,7 +365,7 @@ int backscatter_eval(qgx_model *m, const double2 *qh, double *S, double *ratio, 
 bool generator_noise_is_double(const qgx_generator *g);
 bool generator_takes_noise(const qgx_generator *g);     // false for OLS and ANN: no latent noise at all
 bool generator_reads_q(const qgx_generator *g);         // true for ANN: its kernel reads q itself, there is no input to assemble
-int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st);
+int diag_increment(qgx_model *m, const double *S, double weight, int demean, hipStream_t st);
 int diag_ensure_alloc(qgx_model *m);      // the increment's work fields and accumulators (allocated at first use)
 // the generator's activation workspace for the calls that follow (1: the second half of an ensemble stepped in halves)
 int generator_select_workspace(qgx_generator *g, int idx);

@@ -62,6 +62,23 @@ __global__ void k_diag_scale_S(const double *src, double *dst, size_t n, double 
         dst[i] = w * src[i];
 }
 
+// dst = src - mean_{y,x} src for each (member, layer) plane of n values, one workgroup per plane
+__global__ void k_diag_demean(const double *src, double *dst, int n) {
+    __shared__ double red[256];
+    const double *s = src + (size_t)blockIdx.x * n;
+    double *o = dst + (size_t)blockIdx.x * n;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += s[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    const double mean = red[0] / n;
+    for (int i = threadIdx.x; i < n; i += 256) o[i] = s[i] - mean;
+}
+
 static dim3 dgrid(const SpecDev &d, int n) { return dim3((unsigned)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256), d.B); }
 
 static int dalloc0(double *&p, size_t n) {
@@ -109,11 +126,19 @@ static DiagAcc diag_acc(const qgx_model *m) {
     return a;
 }
 
-int diag_increment(qgx_model *m, const double *S, double weight, hipStream_t st) {
+int diag_increment(qgx_model *m, const double *S, double weight, int demean, hipStream_t st) {
     const SpecDev &d = m->d;
     const size_t nr = (size_t)d.B * 2 * d.N * d.N;
     int rc;
     if ((rc = diag_ensure_alloc(m))) return rc;
+    if (S && demean) {
+        // an external forcing that the step kernels de-mean (qgx_param::demean: they drop the (0, 0) element of its spectrum)
+        // is the parameterization's tendency WITHOUT its layer means here too: pyqg's dqh is the transform of the de-meaned
+        // field, and ENSparamspec's (0, 0) element is conj(qh) dqh there, not zero once q has a mean
+        if (!m->dg_Sdm && (rc = dalloc0(m->dg_Sdm, nr))) return rc;
+        hipLaunchKernelGGL(k_diag_demean, dim3(2 * d.B), dim3(256), 0, st, S, m->dg_Sdm, d.N * d.N);
+        S = m->dg_Sdm;
+    }
     double *R3 = m->dg_R[2], *R4 = m->dg_R[3], *R5 = m->dg_R[4], *R6 = m->dg_R[5], *R7 = m->dg_R[6];
     double2 *xih = (double2 *)m->dg_S[0];
     const DiagConst c = diag_const(m);

@@ -762,7 +762,7 @@ static int step_core(qgx_model *m, int nsteps, const qgx_param *p, int refresh_d
         else if (m->bs_on) rc = forcing_backscatter(m, st, f);
         if (rc) return rc;
         // (before the time step; never while a first half is in flight: forcing_sampled launches none on such a step)
-        if (diag_due(m, m->bk.tc) && (rc = diag_increment(m, f.has_S ? f.S : nullptr, f.weight, st))) return rc;
+        if (diag_due(m, m->bk.tc) && (rc = diag_increment(m, f.has_S ? f.S : nullptr, f.weight, f.demean, st))) return rc;
         if (K) {
             if ((rc = model_step_run(m, K, st))) return rc;
             s += K - 1;

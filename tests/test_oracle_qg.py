@@ -265,3 +265,143 @@ def test_oracle_long_run_matches_the_references_published_dataset_checksums():
         se = per_run.std(ddof=1) / np.sqrt(len(per_run))
         print(f'oracle {total:.6e} published {published:.6e} ({100 * (total / published - 1):+.3f} %), standard error {100 * se / published:.2f} %')
         assert abs(total - published) <= 4 * se + 0.003 * published
+
+
+# ---- every physical constant off pyqg's default (tests/physics_sets.py): the oracle anchored on the analytic checks above,
+# independently of the kernels that are compared with it at these constants (tests/test_gpu_physics_constants.py)
+import pytest
+import physics_sets
+
+
+@pytest.mark.parametrize('name', ['A', 'B'])
+def test_linear_growth_rates_with_every_constant_off_default(name):
+    """the body of test_linear_growth_rates_oblique_modes_and_jet_parameters with U2 != 0, L != 1e6, other rd, delta, beta,
+    rek, H1: U2 = 0 would move the eigenvalue by 0.4 ... 1.0 of itself, L = 1e6 by 0.26 ... 0.86; the bounds are that
+    test's (measured: growth rate 8.2e-5, phase 1.7e-7, other modes 2e-16)"""
+    params = dict(physics_sets.SETS[name], filterfac=0.)
+    for N, modes in ((32, [(3, 0), (2, 1), (4, -2)]), (48, [(5, 2)])):
+        for kx, ly in modes:
+            m = qg_ref.QGModelRef(nx=N, dt=1800., **params)
+            assert m.Ubg[1] != 0 and m.kk[1] != 2 * np.pi / 1e6
+            w, vec = _unstable_mode(m, kx, ly)
+            qh = np.zeros((2, N, N // 2 + 1), complex)
+            qh[:, ly, kx] = 1e-12 * N * N * vec
+            m.set_qh(qh)
+            nsteps = 300
+            a0 = m.qh[:, ly, kx].copy()
+            for _ in range(nsteps):
+                m._step_forward()
+            ratio = m.qh[:, ly, kx] / a0
+            T = nsteps * m.dt
+            np.testing.assert_allclose(np.log(np.abs(ratio)) / T, w.real, rtol=3e-4, err_msg=str((name, N, kx, ly)))
+            np.testing.assert_allclose(ratio / np.abs(ratio), np.exp(1j * w.imag * T) * np.ones(2), atol=2e-3)
+            rest = np.abs(m.qh).copy()
+            rest[:, ly, kx] = 0
+            assert rest.max() < 1e-9 * np.abs(m.qh[:, ly, kx]).max()
+
+
+@pytest.mark.parametrize('name', ['A', 'B'])
+def test_energy_budget_closes_with_every_constant_off_default(name):
+    """the body of test_energy_budget_of_the_diagnostics_closes, both of its band limits, dt = 7200"""
+    N = 64
+    rs = np.random.RandomState(5)
+    S = rs.randn(2, N, N) * np.array([7e-12, 2e-13])[:, None, None]
+    for band in (1. / 4., 2. / 3.):
+        m = qg_ref.QGModelRef(nx=N, dt=7200., parameterization=lambda mm: S, **physics_sets.SETS[name])
+        q = rs.randn(2, N, N) * np.array([8e-6, 1e-6])[:, None, None]
+        m.set_qh(np.fft.rfftn(q, axes=(-2, -1)) * (m.wv < band * m.kk[-1]))
+        m._invert()
+        m._do_advection()
+        m._do_friction()
+        m._do_q_subgrid_parameterization()
+        d = m._diag_functions()
+        dEdt = -_hermitian_sum(((m.Hi / m.H)[:, None, None] * np.real(np.conj(m.ph) * m.dqhdt)).sum(0)) / m.M ** 2
+        parts = {k: _hermitian_sum(d[k]) for k in ('KEflux', 'APEflux', 'APEgenspec', 'KEfrictionspec', 'paramspec')}
+        scale = sum(abs(_hermitian_sum(np.abs(d[k]))) for k in parts)
+        assert abs(sum(parts.values()) - dEdt) < 1e-12 * scale, (band, parts, dEdt)
+        assert abs(parts['KEflux']) < 1e-12 * _hermitian_sum(np.abs(d['KEflux']))
+        if band <= 0.25:
+            assert abs(parts['APEflux']) < 1e-12 * _hermitian_sum(np.abs(d['APEflux']))
+        assert parts['KEfrictionspec'] < 0
+        np.testing.assert_allclose(d['paramspec_APEflux'] + d['paramspec_KEflux'], d['paramspec'],
+                                   atol=1e-12 * np.abs(d['paramspec']).max())
+        ke_grid = 0.5 * ((m.u ** 2 + m.v ** 2).mean(axis=(1, 2)))
+        np.testing.assert_allclose([0.5 * _hermitian_sum(d['KEspec'][z]) for z in (0, 1)], ke_grid, rtol=1e-10)
+        np.testing.assert_allclose([_hermitian_sum(d['Ensspec'][z]) for z in (0, 1)], (m.q ** 2).mean(axis=(1, 2)), rtol=1e-10)
+
+
+@pytest.mark.parametrize('name', ['A', 'B'])
+def test_enstrophy_budget_closes_with_every_constant_off_default(name):
+    """the body of test_enstrophy_budget_and_filter_dissipation_of_the_diagnostics_close, both of its band limits, dt = 7200:
+    Dissspec / ENSDissspec carry kx U2 q2 and the filter of this set's filterfac"""
+    N = 64
+    rs = np.random.RandomState(6)
+    S = rs.randn(2, N, N) * np.array([7e-12, 2e-13])[:, None, None]
+    for band in (1. / 4., 0.95):
+        m = qg_ref.QGModelRef(nx=N, dt=7200., parameterization=lambda mm: S, **physics_sets.SETS[name])
+        q = rs.randn(2, N, N) * np.array([8e-6, 1e-6])[:, None, None]
+        m.set_qh(np.fft.rfftn(q, axes=(-2, -1)) * (m.wv < band * m.kk[-1]))
+        if band <= 0.25:
+            m._invert()
+            m._do_advection()
+            f0 = m._diag_functions()['ENSflux']
+            assert abs(_hermitian_sum(f0)) < 1e-12 * _hermitian_sum(np.abs(f0))
+        for _ in range(3):
+            m._step_forward()
+        m._invert()
+        m._do_advection()
+        m._do_friction()
+        m._do_q_subgrid_parameterization()
+        d = m._diag_functions()
+        hr = (m.Hi / m.H)[:, None, None]
+        dZdt = (hr * np.real(np.conj(m.qh) * m.dqhdt)).sum(0) / m.M ** 2
+        total = d['ENSflux'] + d['ENSgenspec'] + d['ENSfrictionspec'] + d['ENSparamspec']
+        scale = sum(np.abs(d[k]).max() for k in ('ENSflux', 'ENSgenspec', 'ENSfrictionspec', 'ENSparamspec'))
+        np.testing.assert_allclose(total, dZdt, rtol=0, atol=1e-12 * scale)
+        dt1, dt2, dt3 = 23. / 12. * m.dt, -16. / 12. * m.dt, 5. / 12. * m.dt
+        unf = m.qh + dt1 * m.dqhdt + dt2 * m.dqhdt_p + dt3 * m.dqhdt_pp
+        diss = (m.filtr - 1.0) * unf
+        np.testing.assert_allclose(diss, m._dissipation_spectrum(), rtol=0, atol=0)
+        assert (m.filtr <= 1.0).all()
+        if band > 0.9:
+            assert np.abs(diss).max() > 0
+        qh_n, ph_n = m.qh.copy(), m.ph.copy()
+        np.testing.assert_allclose(d['ENSDissspec'] * m.dt, (hr * np.real(np.conj(qh_n) * diss)).sum(0) / m.M ** 2,
+                                   rtol=0, atol=1e-13 * max(np.abs(d['ENSDissspec']).max() * m.dt, 1e-300))
+        np.testing.assert_allclose(d['Dissspec'] * m.dt, -(hr * np.real(np.conj(ph_n) * diss)).sum(0) / m.M ** 2,
+                                   rtol=0, atol=1e-13 * max(np.abs(d['Dissspec']).max() * m.dt, 1e-300))
+        m._forward_timestep()
+        np.testing.assert_allclose(m.qh, m.filtr * unf, rtol=0, atol=1e-15 * np.abs(unf).max())
+        Zf = 0.5 * (hr * np.abs(m.filtr * unf) ** 2).sum(0)
+        Zu = 0.5 * (hr * np.abs(unf) ** 2).sum(0)
+        ident = (hr * (np.real(np.conj(unf) * diss) + 0.5 * np.abs(diss) ** 2)).sum(0)
+        np.testing.assert_allclose(Zf - Zu, ident, rtol=0, atol=1e-12 * np.abs(Zu).max())
+        assert (Zf <= Zu).all()
+
+
+def test_h1_alone_changes_nothing_and_every_other_constant_does():
+    """only H_k / H enters: H1 cannot be pinned by any comparison (exactly 0), every other constant set back to pyqg's
+    default moves qh after 8 steps by more than 1e-3 of its maximum — nine orders above the 1e-12 per step the kernels are
+    held to at these sets"""
+    import inspect
+    defaults = {k: p.default for k, p in inspect.signature(qg_ref.QGModelRef.__init__).parameters.items()}
+    N = 32
+
+    def run(params):
+        m = qg_ref.QGModelRef(nx=N, dt=physics_sets.dt_half(N), **params)
+        m.set_q(physics_sets.eddy_like_q(np.random.RandomState(3), 1, N, physics_sets.A['L'])[0])
+        for _ in range(8):
+            m._step_forward()
+        assert m._calc_cfl() < 0.2
+        return m
+    for name, params in physics_sets.SETS.items():
+        base = run(params)
+        for key in params:
+            assert params[key] != defaults[key], (name, key)
+            other = run(dict(params, **{key: defaults[key]}))
+            moved = np.abs(other.qh - base.qh).max() / np.abs(base.qh).max()
+            if key == 'H1':
+                # qh exactly; KE through the quotient H_k / H, rounded once for each H1
+                assert moved == 0 and abs(other._calc_ke() - base._calc_ke()) <= 4e-16 * base._calc_ke(), (name, moved)
+            else:
+                assert moved > 1e-3, (name, key, moved)

@@ -534,6 +534,11 @@ int qgx_histogram(const void *x_dev, int is_double, int64_t R, int64_t T, int64_
  * (tools/train_CNN.py).  Declared and documented in qgx_conv_train.h, which this header includes. */
 #include "qgx_conv_train.h"
 
+/* The two ends of such a net's training step: the gather of a batch from a planar data set into the engine layout, and the
+ * loss head (MSE, or softplus then MSE: MeanVarModel's variance net) with its gradient and its planar outputs.  Declared and
+ * documented in qgx_head_train.h, which this header includes. */
+#include "qgx_head_train.h"
+
 /* ---- latent noise ------------------------------------------------------------
  * z <- a z + b xi with xi ~ N(0,1) from Philox4x32-10 (stochastic_pyqg.py:43-49).  z: (B, n_per_member) float or double,
  * n_per_member a positive multiple of 4; a == 0 overwrites z (its previous contents are not read).  Counter of the four

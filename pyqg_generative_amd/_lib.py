@@ -195,6 +195,18 @@ CONV_TRAIN_SYMBOLS = [
     ('qgx_conv2d_backward_weight', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + _CONV + _CONV_WORK),
 ]
 
+# what include/qgx_head_train.h declares: the batch gather and the loss head of a net's training step (tools/train_CNN.py)
+HEAD_MSE, HEAD_SOFTPLUS_MSE = 0, 1
+_HEAD = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]                                         # y, t, idx, mode
+_HEAD_SHAPE = [C.c_int64, C.c_int, C.c_int, C.c_int64]                                        # B, N, C, n
+HEAD_TRAIN_SYMBOLS = [
+    ('qgx_batch_gather', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    ('qgx_head_workspace', C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
+    ('qgx_head_loss', C.c_int, _HEAD + [C.c_void_p] + _HEAD_SHAPE + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ('qgx_head_grad', C.c_int, _HEAD + [C.c_void_p, C.c_void_p] + _HEAD_SHAPE + [C.c_void_p]),
+    ('qgx_head_apply', C.c_int, _HEAD + [C.c_void_p] + _HEAD_SHAPE + [C.c_void_p]),
+]
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -207,7 +219,7 @@ def _load():
     # Load torch's first — torch finds no GPU when it is handed the other runtime.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS + TRAIN_SYMBOLS + CONV_TRAIN_SYMBOLS:
+    for name, res, args in SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS + TRAIN_SYMBOLS + CONV_TRAIN_SYMBOLS + HEAD_TRAIN_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -1,4 +1,4 @@
-"""One training step of OLSModel's net (tools/train_CNN.py over csrc/conv_train.hip) next to plain torch on the same GPU.
+"""One training step of OLSModel's net (tools/train_CNN.py and tools/train_ops.py over csrc/conv_train.hip) next to plain torch on the same GPU.
 
 The shipped widths [128, 64, 32, 32, 32, 32, 32] at 64 x 64, batch 64, BatchNorm and bias on.  Three tables:
   * per layer: forward, data gradient and weight gradient of the device kernels (packing and reduction kernels included), HIP
@@ -52,7 +52,7 @@ def main():
     ap.add_argument('--inner', type=int, default=10)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'cnn_train_time.txt'))
     args = ap.parse_args()
-    from pyqg_generative_amd.tools import train_CNN as T
+    from pyqg_generative_amd.tools import train_CNN as T, train_ops as O
     assert torch.cuda.is_available(), 'cnn_train_time.py needs cuda:0'
     dev = torch.device('cuda', 0)
     B, N = args.batch, args.n
@@ -76,17 +76,17 @@ def main():
         cout, cin, k = int(m.weight.shape[0]), int(m.weight.shape[1]), int(m.weight.shape[2])
         p = k // 2
         flop = 2.0 * B * N * N * cin * cout * k * k
-        xa = T.to_engine_layout(torch.randn((B, cin, N, N), generator=g, device=dev))
-        dya = T.to_engine_layout(torch.randn((B, cout, N, N), generator=g, device=dev))
+        xa = O.to_engine_layout(torch.randn((B, cin, N, N), generator=g, device=dev))
+        dya = O.to_engine_layout(torch.randn((B, cout, N, N), generator=g, device=dev))
         w, b = m.weight.detach(), m.bias.detach()
         xp = torch.randn((B, cin, N, N), generator=g, device=dev).contiguous(memory_format=torch.channels_last)
         dyp = torch.randn((B, cout, N, N), generator=g, device=dev).contiguous(memory_format=torch.channels_last)
         xpad = F.pad(xp, (p, p, p, p), mode='circular')
         bw = lambda mask: torch.ops.aten.convolution_backward(dyp, xpad, w, [cout], [1, 1], [0, 0], [1, 1], False, [0, 0], 1, mask)
         ops = {
-            'd_fwd': lambda: T.conv2d_forward(xa, w, b),
-            'd_dgrad': (lambda: T.conv2d_backward_data(dya, w)) if l > 0 else None,
-            'd_wgrad': lambda: T.conv2d_backward_weight(xa, dya, cin, cout, k),
+            'd_fwd': lambda: O.conv2d_forward(xa, w, b),
+            'd_dgrad': (lambda: O.conv2d_backward_data(dya, w)) if l > 0 else None,
+            'd_wgrad': lambda: O.conv2d_backward_weight(xa, dya, cin, cout, k),
             't_fwd': lambda: F.conv2d(F.pad(xp, (p, p, p, p), mode='circular'), w, b),
             't_dgrad': (lambda: bw([True, False, False])) if l > 0 else None,
             't_wgrad': lambda: bw([False, True, True]),
@@ -160,15 +160,15 @@ def main():
             pairs.append((e0, e1))
             return out
         return wrapped
-    saved = (T.conv2d_forward, T.conv2d_backward_data, T.conv2d_backward_weight)
-    T.conv2d_forward, T.conv2d_backward_data, T.conv2d_backward_weight = (bracket(f) for f in saved)
+    saved = (O.conv2d_forward, O.conv2d_backward_data, O.conv2d_backward_weight)
+    O.conv2d_forward, O.conv2d_backward_data, O.conv2d_backward_weight = (bracket(f) for f in saved)
     shares = []
     for _ in range(args.reps):
         pairs.clear()
         ms = event_ms(step_device)
         conv_ms = sum(a.elapsed_time(b) for a, b in pairs)
         shares.append((ms, conv_ms, len(pairs)))
-    T.conv2d_forward, T.conv2d_backward_data, T.conv2d_backward_weight = saved
+    O.conv2d_forward, O.conv2d_backward_data, O.conv2d_backward_weight = saved
     ms, conv_ms, calls = sorted(shares)[len(shares) // 2]
     lines += [f'device step with an event pair around each of its {calls} convolution calls: {ms:.3f} ms, of which the calls {conv_ms:.3f} ms',
               f'share of the BatchNorm / ReLU / MSE / Adam ops and launch gaps: {100 * (1 - conv_ms / ms):.1f} % of that step '

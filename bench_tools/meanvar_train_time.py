@@ -67,7 +67,7 @@ def main():
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'meanvar_train_time.txt'))
     args = ap.parse_args()
-    from pyqg_generative_amd.tools import train_CNN as T
+    from pyqg_generative_amd.tools import train_CNN as T, train_ops as O
     assert torch.cuda.is_available(), 'meanvar_train_time.py needs cuda:0'
     dev = torch.device('cuda', 0)
     B, N, S = args.batch, args.n, args.samples
@@ -109,13 +109,13 @@ def main():
 
     def ends_fused():
         y.grad = None
-        a = T.gather_batch(X, idx)
-        T.head_loss(y, Tg, idx, 'softplus_mse').backward()
+        a = O.gather_batch(X, idx)
+        O.head_loss(y, Tg, idx, 'softplus_mse').backward()
         return a
 
     def ends_plain():
         y.grad = None
-        a = T.to_engine_layout(X[idx])
+        a = O.to_engine_layout(X[idx])
         F.mse_loss(F.softplus(y[..., :2].permute(0, 3, 1, 2)), Tg[idx]).backward()
         return a
     lines += rows('the two ends alone', *alternate(ends_fused, ends_plain, args.reps, 10))

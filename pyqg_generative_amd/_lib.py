@@ -185,7 +185,7 @@ TRAIN_SYMBOLS = [
     ('qgx_ann_trainer_write', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
 ]
 
-# what include/qgx_conv_train.h declares: the circular convolution and its two gradients (tools/train_CNN.py)
+# what include/qgx_conv_train.h declares: the circular convolution and its two gradients (tools/train_ops.py)
 _CONV = [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]                                       # B, N, cin, cout, k
 _CONV_WORK = [C.c_void_p, C.c_size_t, C.c_void_p]                                             # work, work_bytes, stream
 CONV_TRAIN_SYMBOLS = [
@@ -195,7 +195,7 @@ CONV_TRAIN_SYMBOLS = [
     ('qgx_conv2d_backward_weight', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + _CONV + _CONV_WORK),
 ]
 
-# what include/qgx_head_train.h declares: the batch gather and the loss head of a net's training step (tools/train_CNN.py)
+# what include/qgx_head_train.h declares: the batch gather and the loss head of a net's training step (tools/train_ops.py)
 HEAD_MSE, HEAD_SOFTPLUS_MSE = 0, 1
 _HEAD = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]                                         # y, t, idx, mode
 _HEAD_SHAPE = [C.c_int64, C.c_int, C.c_int, C.c_int64]                                        # B, N, C, n

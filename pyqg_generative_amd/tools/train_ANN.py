@@ -4,6 +4,8 @@ prepare_data_ANN, :645-700 train, driver tools/train_ANN.py).
 ``fit_ann`` builds the stencil rows of the datasets on the device (csrc/ann_train.hip, qgx_ann_rows), trains the net with
 the fused loss / gradient and Adam kernels of the trainer handle (include/qgx_train.h) and writes the reference's model
 folder: net.pt, scale.json, model_args.json, stats.nc.  It returns ``ANNModel(folder=...)`` read back from those files.
+This module holds the row builder, the trainer handle, the folder writer and the fit; what it shares with the CNN fits
+(argument checks, schedule, dataset extraction, stats.nc, the epoch log, the command line) is in tools/train_common.py.
 
 Command line:
     python -m pyqg_generative_amd.tools.train_ANN --train 'GLOB' --validate 'GLOB' [--test 'GLOB'] \\
@@ -13,7 +15,6 @@ reference trains on 48 x 48 and 96 x 96 together).  With --test, `offline-<k>.nc
 """
 import ctypes as C
 import json
-import math
 import os
 from time import time
 
@@ -23,12 +24,10 @@ import torch
 from .. import _lib, weights as _weights
 from .._lib import lib, check
 from ..engine import Generator
+from .train_common import (check_fit_args, command_line, cuda_device, learning_rates, log_epoch, print_start, save_state_dict,
+                           stacked, write_log)
 
 STEP = 3          # prepare_data_ANN keeps every third point in y and x (cnn_tools.py:384-386)
-
-
-def _stream():
-    return _lib.current_stream_ptr()
 
 
 def ann_rows(img, stencil_size, step=1):
@@ -44,7 +43,7 @@ def ann_rows(img, stencil_size, step=1):
     nc = -(-N // step)
     with torch.cuda.device(img.device):
         rows = torch.empty((nc * nc * n_img, s * s), dtype=torch.float32, device=img.device)
-        check(lib.qgx_ann_rows(img.data_ptr(), n_img, N, s, step, rows.data_ptr(), _stream()))
+        check(lib.qgx_ann_rows(img.data_ptr(), n_img, N, s, step, rows.data_ptr(), _lib.current_stream_ptr()))
     return rows
 
 
@@ -90,23 +89,23 @@ class AnnTrainer:
         n, ip = self._batch(x, y, idx)
         with torch.cuda.device(self.device):
             check(lib.qgx_ann_trainer_grad(self._h, x.data_ptr(), y.data_ptr(), ip, n, x_scale, y_scale,
-                                           None if loss_acc is None else loss_acc.data_ptr(), _stream()))
+                                           None if loss_acc is None else loss_acc.data_ptr(), _lib.current_stream_ptr()))
 
     def adam(self, lr):
         with torch.cuda.device(self.device):
-            check(lib.qgx_ann_trainer_adam(self._h, lr, _stream()))
+            check(lib.qgx_ann_trainer_adam(self._h, lr, _lib.current_stream_ptr()))
 
     def step(self, x, y, idx, x_scale, y_scale, lr, loss_acc=None):
         n, ip = self._batch(x, y, idx)
         with torch.cuda.device(self.device):
             check(lib.qgx_ann_trainer_step(self._h, x.data_ptr(), y.data_ptr(), ip, n, x_scale, y_scale, lr,
-                                           None if loss_acc is None else loss_acc.data_ptr(), _stream()))
+                                           None if loss_acc is None else loss_acc.data_ptr(), _lib.current_stream_ptr()))
 
     def loss(self, x, y, idx, x_scale, y_scale, loss_acc):
         n, ip = self._batch(x, y, idx)
         with torch.cuda.device(self.device):
             check(lib.qgx_ann_trainer_loss(self._h, x.data_ptr(), y.data_ptr(), ip, n, x_scale, y_scale,
-                                           loss_acc.data_ptr(), _stream()))
+                                           loss_acc.data_ptr(), _lib.current_stream_ptr()))
 
     def read(self, what=_lib.TRAIN_PARAMS):
         out = np.empty(self.size, np.float32)
@@ -132,32 +131,9 @@ class AnnTrainer:
         return {k: torch.from_numpy(v) for k, v in self.unpack(self.read(_lib.TRAIN_PARAMS)).items()}
 
 
-def learning_rates(num_epochs, learning_rate):
-    """the learning rate of every epoch under train()'s schedule (cnn_tools.py:670-672, :692): MultiStepLR with milestones
-    int(E / 2), int(3 E / 4), int(7 E / 8), gamma 0.1, stepped after each epoch — torch's class on a dummy optimizer, so that
-    repeated and zero milestones of a small E behave as torch's do"""
-    E = int(num_epochs)
-    opt = torch.optim.SGD([torch.zeros(1, requires_grad=True)], lr=float(learning_rate))
-    sched = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=[int(E / 2), int(E * 3 / 4), int(E * 7 / 8)], gamma=0.1)
-    out = []
-    for _ in range(E):
-        out.append(float(opt.param_groups[0]['lr']))
-        opt.step()
-        sched.step()
-    return out
-
-
 def _images(ds, name):
     """stack_images (cnn_tools.py:360-371) of ds[name] with dims (run, time, lev, y, x): (n_img, N, N) float32 on the host"""
-    if name not in ds:
-        raise ValueError(f'fit_ann needs {name!r} in every dataset')
-    a = ds[name]
-    dims = tuple(a.dims)
-    if dims != ('run', 'time', 'lev', 'y', 'x'):
-        if set(dims) != {'run', 'time', 'lev', 'y', 'x'}:
-            raise ValueError(f'{name}: dims {dims}, expected (run, time, lev, y, x)')
-        a = a.transpose('run', 'time', 'lev', 'y', 'x')
-    v = np.asarray(a.values)
+    v = stacked(ds, name, 'fit_ann')
     if v.shape[-1] != v.shape[-2]:
         raise ValueError(f'{name}: a {v.shape[-2]} x {v.shape[-1]} grid is not square')
     return np.ascontiguousarray(v.reshape((-1,) + v.shape[-2:]), dtype=np.float32)
@@ -191,23 +167,14 @@ def device_scales(X, Y, stencil_size):
 
 def write_model_folder(folder, state_dict, x_scale, y_scale, stencil_size, hidden_channels, scale_invariant, log):
     """save_model (ann_model.py:54-66): net.pt (CPU float32 state dict), scale.json, model_args.json, stats.nc"""
-    from .simulate import dataset_backend
     os.makedirs(folder, exist_ok=True)
-    sd = {k: torch.as_tensor(np.asarray(v, dtype=np.float32)).clone() for k, v in state_dict.items()}
-    torch.save(sd, os.path.join(folder, 'net.pt'))
+    save_state_dict(os.path.join(folder, 'net.pt'), state_dict)
     with open(os.path.join(folder, 'scale.json'), 'w') as f:
         json.dump({'x_scale': float(x_scale), 'y_scale': float(y_scale)}, f)
     with open(os.path.join(folder, 'model_args.json'), 'w') as f:
         json.dump(dict(model='ANNModel', stencil_size=int(stencil_size), hidden_channels=[int(h) for h in hidden_channels],
                        scale_invariant=bool(scale_invariant)), f)
-    xr = dataset_backend()
-    E = len(next(iter(log.values())))
-    stats = xr.Dataset({k: (['epoch'], np.asarray(v, dtype=np.float64)) for k, v in log.items()},
-                       coords={'epoch': np.arange(1, E + 1)})
-    path = os.path.join(folder, 'stats.nc')
-    if os.path.exists(path):
-        os.remove(path)
-    stats.to_netcdf(path)
+    write_log(os.path.join(folder, 'stats.nc'), log)
 
 
 def fit_ann(ds_train, ds_test, *, stencil_size=3, hidden_channels=[24, 24], scale_invariant=False, folder='model',
@@ -219,17 +186,12 @@ def fit_ann(ds_train, ds_test, *, stencil_size=3, hidden_channels=[24, 24], scal
     tensor holding a permutation of 0 ... n_rows - 1) in place of torch.randperm seeded from `seed`."""
     from ..models.ann_model import ANNModel
     num_epochs, batch_size = int(num_epochs), int(batch_size)
-    if batch_size < 1:
-        raise ValueError(f'fit_ann: batch_size = {batch_size}')
-    if num_epochs < 1:
-        raise ValueError(f'fit_ann: num_epochs = {num_epochs}')
-    if not (math.isfinite(learning_rate) and learning_rate >= 0):
-        raise ValueError(f'fit_ann: learning_rate = {learning_rate}')
+    check_fit_args('fit_ann', num_epochs, batch_size, learning_rate)
     s, hidden = int(stencil_size), [int(h) for h in hidden_channels]
     train_img, test_img = _check_datasets(ds_train), _check_datasets(ds_test)
     net = _weights.synthetic_ann(s, hidden, bool(scale_invariant), seed)
 
-    dev = torch.device('cuda', int(device))
+    dev = cuda_device(device)
     with torch.cuda.device(dev):
         X, Y = device_rows(train_img, s, dev)
         Xt, Yt = device_rows(test_img, s, dev)
@@ -240,10 +202,9 @@ def fit_ann(ds_train, ds_test, *, stencil_size=3, hidden_channels=[24, 24], scal
         gen.manual_seed(int(seed))
         lrs = learning_rates(num_epochs, learning_rate)
         acc = torch.zeros((num_epochs, 2, 2), dtype=torch.float64, device=dev)     # per epoch: train / test, (sum, rows)
-        log = {'loss': [], 'loss_test': []}
+        log = {}
         t_s = time()
-        if verbose:
-            print(f'Training starts on device {torch.cuda.get_device_name(dev)}, number of samples {R}')
+        print_start(dev, R, verbose)
         for epoch in range(num_epochs):
             t_e = time()
             if permutations is None:
@@ -255,14 +216,7 @@ def fit_ann(ds_train, ds_test, *, stencil_size=3, hidden_channels=[24, 24], scal
             for b0 in range(0, R, batch_size):
                 trainer.step(X, Y, order[b0:b0 + batch_size], x_scale, y_scale, lrs[epoch], acc[epoch, 0])
             trainer.loss(Xt, Yt, None, x_scale, y_scale, acc[epoch, 1])
-            a = acc[epoch].cpu().numpy()                      # the epoch's one host read
-            log['loss'].append(float(a[0, 0] / a[0, 1]))
-            log['loss_test'].append(float(a[1, 0] / a[1, 1]))
-            if verbose:
-                t = time()
-                print('[%d/%d] [%.2f/%.2f] Loss: [%.3f, %.3f]' % (epoch + 1, num_epochs, t - t_e,
-                                                                  (t - t_s) * (num_epochs / (epoch + 1) - 1),
-                                                                  log['loss'][-1], log['loss_test'][-1]))
+            log_epoch(log, acc[epoch].cpu().numpy(), epoch, num_epochs, t_e, t_s, verbose)      # the epoch's one host read
         if verbose:
             print(f'training took {time() - t_s:.2f} seconds')
         sd = trainer.state_dict()
@@ -271,32 +225,9 @@ def fit_ann(ds_train, ds_test, *, stencil_size=3, hidden_channels=[24, 24], scal
     return ANNModel(scale_invariant=bool(scale_invariant), stencil_size=s, hidden_channels=hidden, folder=folder, device=device)
 
 
-def _open(pattern):
-    from .simulate import dataset_backend
-    xr = dataset_backend()
-    return [xr.open_mfdataset(p.strip(), combine='nested', concat_dim='run') for p in pattern.split(',') if p.strip()]
-
-
 def main(argv=None):
-    import argparse
-    import ast
-    parser = argparse.ArgumentParser(description='train ANNModel on the device and write its model folder')
-    parser.add_argument('--train', type=str, required=True, help="glob of training files; several, comma-separated: several datasets")
-    parser.add_argument('--validate', type=str, required=True)
-    parser.add_argument('--test', type=str, default=None, help='glob(s) of files for test_offline')
-    parser.add_argument('--model_args', type=str, default=str({}))
-    parser.add_argument('--fit_args', type=str, default=str({}))
-    args = parser.parse_args(argv)
-    print(args)
-    model_args, fit_args = ast.literal_eval(args.model_args), ast.literal_eval(args.fit_args)
-    if not isinstance(model_args, dict) or not isinstance(fit_args, dict):
-        raise ValueError('--model_args and --fit_args are dict literals')
-    model_args.pop('read', None)
-    model = fit_ann(_open(args.train), _open(args.validate), **model_args, **fit_args)
-    if args.test:
-        for k, ds in enumerate(_open(args.test)):
-            model.test_offline(ds).to_netcdf(os.path.join(model.folder, f'offline-{k}.nc'))
-    return model
+    return command_line('train ANNModel on the device and write its model folder', {'ANNModel': fit_ann}, argv,
+                        several=True, ignore=('read',))
 
 
 if __name__ == '__main__':

@@ -1,0 +1,267 @@
+"""The device operations of a CNN training step: ctypes wrappers over include/qgx_conv_train.h and include/qgx_head_train.h
+and the two torch.autograd.Functions that put them behind autograd.
+
+The convolutions — more than 95 % of a step's FLOPs — are the kernels of csrc/conv_train.hip behind ``circular_conv2d``.  The
+two ends of a step — the gather of a batch from the resident set into the engine layout, and the loss head (MSE, or softplus
+then MSE) with its gradient — are the kernels of csrc/train_head.hip behind ``gather_batch``, ``head_loss`` and ``head_apply``.
+Every tensor is checked here, once per layout (``_engine``, ``_planar``, ``_rows``), before a pointer reaches the library.
+The nets and loops that use these operations are in tools/train_CNN.py.
+"""
+import ctypes as C
+
+import torch
+
+from .. import _lib
+from .._lib import lib, check
+
+GRIDS = (16, 32, 48, 64, 96, 128)          # what include/qgx_conv_train.h admits
+
+
+def c8(c):
+    """channels per pixel of the engine's layout: rounded up to 8"""
+    return (int(c) + 7) // 8 * 8
+
+
+_WORK = {}
+
+
+def workspace(kind, size_call, shape, device):
+    """the workspace of one kind ('conv': one size for the three calls; 'head': the loss partials) and shape, of
+    size_call(*shape, &bytes) bytes, cached per device, stream and shape: calls on one stream run in order, so they may share
+    it; calls on different streams may not"""
+    key = (kind, device.index, torch.cuda.current_stream(device).cuda_stream) + shape
+    ws = _WORK.get(key)
+    if ws is None:
+        n = C.c_size_t()
+        check(size_call(*shape, C.byref(n)))
+        ws = _WORK[key] = torch.empty(n.value, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _aligned(t):
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _engine(t, name, channels=None):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == t.shape[2] and t.shape[3] % 8 == 0):
+        raise ValueError(f'{name}: a float32 device tensor (B, N, N, C8) in the engine layout, not {tuple(t.shape)} {t.dtype} on {t.device}')
+    if channels is not None and t.shape[3] != c8(channels):
+        raise ValueError(f'{name}: {t.shape[3]} channels per pixel, {channels} channels take {c8(channels)}')
+    return t.contiguous()
+
+
+def _planar(t, name):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[2] == t.shape[3]
+            and 1 <= t.shape[1] <= 8 and t.shape[0] >= 1):
+        raise ValueError(f'{name}: a float32 device tensor (n, C, N, N) with 1 ... 8 channels, not '
+                         f'{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}'
+                         f'{(" %s on %s" % (t.dtype, t.device)) if torch.is_tensor(t) else ""}')
+    return _aligned(t.contiguous())
+
+
+def _rows(idx, like):
+    """idx -> None or a contiguous, aligned int64 vector on `like`'s device (the indices' range is the caller's duty: train()
+    checks an epoch's order on the host before it uploads it)"""
+    if idx is None:
+        return None
+    if not (torch.is_tensor(idx) and idx.dtype == torch.int64 and idx.dim() == 1 and idx.device == like.device and len(idx) >= 1):
+        raise ValueError(f'idx: an int64 vector on {like.device}, or None')
+    return _aligned(idx.contiguous())
+
+
+def _weight(w):
+    if not (w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and w.shape[2] == w.shape[3]):
+        raise ValueError(f'weight: a float32 device tensor (cout, cin, k, k), not {tuple(w.shape)} {w.dtype} on {w.device}')
+    return w.contiguous(), int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def conv2d_forward(x, w, b=None):
+    """y (B, N, N, c8(cout)) = conv_circular(x (B, N, N, c8(cin)), w (cout, cin, k, k)) + b"""
+    w, cout, cin, k = _weight(w)
+    x = _engine(x, 'x', cin)
+    B, N = int(x.shape[0]), int(x.shape[1])
+    with torch.cuda.device(x.device):
+        ws = workspace('conv', lib.qgx_conv2d_workspace, (B, N, cin, cout, k), x.device)
+        y = torch.empty((B, N, N, c8(cout)), dtype=torch.float32, device=x.device)
+        check(lib.qgx_conv2d_forward(x.data_ptr(), w.data_ptr(), _ptr(None if b is None else b.contiguous()), y.data_ptr(),
+                                     B, N, cin, cout, k, ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()))
+    return y
+
+
+def conv2d_backward_data(dy, w):
+    """dx (B, N, N, c8(cin)) of dy (B, N, N, c8(cout))"""
+    w, cout, cin, k = _weight(w)
+    dy = _engine(dy, 'dy', cout)
+    B, N = int(dy.shape[0]), int(dy.shape[1])
+    with torch.cuda.device(dy.device):
+        ws = workspace('conv', lib.qgx_conv2d_workspace, (B, N, cin, cout, k), dy.device)
+        dx = torch.empty((B, N, N, c8(cin)), dtype=torch.float32, device=dy.device)
+        check(lib.qgx_conv2d_backward_data(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), B, N, cin, cout, k, ws.data_ptr(),
+                                           ws.numel(), _lib.current_stream_ptr()))
+    return dx
+
+
+def conv2d_backward_weight(x, dy, cin, cout, k, bias=True):
+    """dw (cout, cin, k, k) and db (cout) (None without `bias`)"""
+    x, dy = _engine(x, 'x', cin), _engine(dy, 'dy', cout)
+    B, N = int(x.shape[0]), int(x.shape[1])
+    if dy.shape[:3] != x.shape[:3]:
+        raise ValueError(f'x {tuple(x.shape)} and dy {tuple(dy.shape)} differ in batch or grid')
+    with torch.cuda.device(x.device):
+        ws = workspace('conv', lib.qgx_conv2d_workspace, (B, N, cin, cout, k), x.device)
+        dw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=x.device)
+        db = torch.empty((cout,), dtype=torch.float32, device=x.device) if bias else None
+        check(lib.qgx_conv2d_backward_weight(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), _ptr(db), B, N, cin, cout, k,
+                                             ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()))
+    return dw, db
+
+
+LAUNCHES = {'forward': 0, 'backward_data': 0, 'backward_weight': 0}      # counted per call of the Function (tests, timing)
+
+
+class _CircularConv2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = b is not None
+        LAUNCHES['forward'] += 1
+        return conv2d_forward(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            LAUNCHES['backward_data'] += 1
+            dx = conv2d_backward_data(dy, w)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            LAUNCHES['backward_weight'] += 1
+            dw, db = conv2d_backward_weight(x, dy, int(w.shape[1]), int(w.shape[0]), int(w.shape[2]), bias=ctx.has_bias)
+        return dx, dw, db
+
+
+def circular_conv2d(x, w, b=None):
+    """Conv2d(padding='same', padding_mode='circular') on the engine layout, differentiable: x (B, N, N, c8(cin)) float32 on
+    the device with zero pad channels, w (cout, cin, k, k), b (cout) or None -> (B, N, N, c8(cout)).  The data gradient is
+    computed only if x requires it (a net's first layer does not)."""
+    return _CircularConv2d.apply(x, w, b)
+
+
+def to_engine_layout(x):
+    """planar (B, C, N, N) -> (B, N, N, c8(C)) with zero pad channels"""
+    B, Cn, N = int(x.shape[0]), int(x.shape[1]), int(x.shape[-1])
+    out = torch.zeros((B, N, N, c8(Cn)), dtype=torch.float32, device=x.device)
+    out[..., :Cn] = x.permute(0, 2, 3, 1)
+    return out
+
+
+HEADS = {'mse': _lib.HEAD_MSE, 'softplus_mse': _lib.HEAD_SOFTPLUS_MSE}     # the modes of include/qgx_head_train.h
+HEAD_LAUNCHES = {'gather': 0, 'loss': 0, 'grad': 0, 'apply': 0}           # counted per call of a wrapper (tests, timing)
+
+
+def head_mode(head):
+    if head not in HEADS:
+        raise ValueError(f'head={head!r}: one of {sorted(HEADS)}')
+    return HEADS[head]
+
+
+def _head_args(head, y, T, idx):
+    """(mode, y, T, idx, B, N, C, n) of a head call: y (B, N, N, 8) in the engine layout against rows idx of the planar set T"""
+    mode, T = head_mode(head), _planar(T, 'T')
+    y = _aligned(_engine(y, 'y', int(T.shape[1])))
+    idx = _rows(idx, y)
+    B, N = int(y.shape[0]), int(y.shape[1])
+    if T.device != y.device or int(T.shape[-1]) != N or (len(T) < B if idx is None else len(idx) != B):
+        raise ValueError(f'y {tuple(y.shape)}, T {tuple(T.shape)}, idx {None if idx is None else tuple(idx.shape)} do not fit')
+    return mode, y, T, idx, B, N, int(T.shape[1]), len(T)
+
+
+def gather_batch(X, idx=None):
+    """X[idx] (all of X without idx) of the planar device set X (n, C, N, N), in the engine layout (B, N, N, 8) with zero pad
+    channels: one launch for the index gather, the zero fill and the permuted copy of to_engine_layout"""
+    X = _planar(X, 'X')
+    idx = _rows(idx, X)
+    n, Cn, N = int(X.shape[0]), int(X.shape[1]), int(X.shape[-1])
+    B = n if idx is None else len(idx)
+    with torch.cuda.device(X.device):
+        out = torch.empty((B, N, N, 8), dtype=torch.float32, device=X.device)
+        check(lib.qgx_batch_gather(X.data_ptr(), _ptr(idx), out.data_ptr(), n, B, N, Cn, _lib.current_stream_ptr()))
+    HEAD_LAUNCHES['gather'] += 1
+    return out
+
+
+def head_loss_value(y, T, idx, head):
+    """mean over b, c, y, x of (h(y[b]) - T[idx[b]])^2 as a 0-dim float64 device tensor (no autograd: see head_loss)"""
+    mode, y, T, idx, B, N, Cn, n = _head_args(head, y, T, idx)
+    with torch.cuda.device(y.device):
+        ws = workspace('head', lib.qgx_head_workspace, (B, N), y.device)
+        loss = torch.empty((), dtype=torch.float64, device=y.device)
+        check(lib.qgx_head_loss(y.data_ptr(), T.data_ptr(), _ptr(idx), mode, loss.data_ptr(), B, N, Cn, n, ws.data_ptr(),
+                                ws.numel(), _lib.current_stream_ptr()))
+    HEAD_LAUNCHES['loss'] += 1
+    return loss
+
+
+def head_loss_grad(y, T, idx, head, gout):
+    """dy (B, N, N, 8) of head_loss_value times the 0-dim float64 device tensor gout, which is read on the device"""
+    mode, y, T, idx, B, N, Cn, n = _head_args(head, y, T, idx)
+    if not (torch.is_tensor(gout) and gout.numel() == 1 and gout.device == y.device):
+        raise ValueError('gout: one number on the device of y')
+    gout = _aligned(gout.detach().to(torch.float64).contiguous())
+    with torch.cuda.device(y.device):
+        dy = torch.empty_like(y)
+        check(lib.qgx_head_grad(y.data_ptr(), T.data_ptr(), _ptr(idx), mode, gout.data_ptr(), dy.data_ptr(), B, N, Cn, n,
+                                _lib.current_stream_ptr()))
+    HEAD_LAUNCHES['grad'] += 1
+    return dy
+
+
+class _HeadLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, T, idx, head):
+        ctx.save_for_backward(y, T, idx)
+        ctx.head = head
+        return head_loss_value(y, T, idx, head)
+
+    @staticmethod
+    def backward(ctx, gout):
+        y, T, idx = ctx.saved_tensors
+        return head_loss_grad(y, T, idx, ctx.head, gout), None, None, None
+
+
+def head_loss(y_engine, T, idx, mode):
+    """The loss of a net's last activation y_engine (B, N, N, 8) against rows idx (None: 0 ... B - 1) of the planar device set
+    T (n, C, N, N): mse_loss(h(y), T[idx]) with h the identity (mode 'mse') or softplus ('softplus_mse'), a 0-dim float64
+    device tensor, differentiable in y_engine.  Forward and backward are one HIP call each; the backward recomputes from
+    y_engine and T, nothing but those two is kept."""
+    return _HeadLoss.apply(y_engine, T, idx, mode)
+
+
+def head_apply(y_engine, channels, mode, T=None, idx=None, out=None):
+    """planar (B, channels, N, N): h(y_engine) without T, else the squared residuals (T[idx] - h(y_engine))^2; written into
+    `out` if given (a contiguous float32 device tensor of that shape).  Not differentiable."""
+    Cn, n = int(channels), 0
+    if not 1 <= Cn <= 8:
+        raise ValueError(f'channels = {channels}: 1 ... 8')
+    if T is None:
+        m, y = head_mode(mode), _aligned(_engine(y_engine.detach(), 'y', Cn))
+        B, N = int(y.shape[0]), int(y.shape[1])
+    else:
+        m, y, T, idx, B, N, Ct, n = _head_args(mode, y_engine.detach(), T, idx)
+        if Ct != Cn:
+            raise ValueError(f'T has {Ct} channels, not {channels}')
+    with torch.cuda.device(y.device):
+        if out is None:
+            out = torch.empty((B, Cn, N, N), dtype=torch.float32, device=y.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, Cn, N, N) and out.is_contiguous()
+                  and out.data_ptr() % 16 == 0):
+            raise ValueError(f'out: a contiguous float32 device tensor {(B, Cn, N, N)}')
+        check(lib.qgx_head_apply(y.data_ptr(), _ptr(T), None if T is None else _ptr(idx), m, out.data_ptr(), B, N, Cn, n,
+                                 _lib.current_stream_ptr()))
+    HEAD_LAUNCHES['apply'] += 1
+    return out

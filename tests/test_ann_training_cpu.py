@@ -106,7 +106,7 @@ def test_refusals_before_any_device_call():
 @pytest.mark.parametrize('E', [1, 2, 3, 4, 5, 6, 7, 8, 9, 50])
 def test_learning_rates_are_multisteplr(E):
     import ann_training_restatement as ar
-    from pyqg_generative_amd.tools.train_ANN import learning_rates
+    from pyqg_generative_amd.tools.train_common import learning_rates
     p = torch.zeros(1, requires_grad=True)
     opt = torch.optim.Adam([p], lr=1e-3)
     sched = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=[int(E / 2), int(E * 3 / 4), int(E * 7 / 8)], gamma=0.1)

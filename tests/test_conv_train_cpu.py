@@ -207,7 +207,7 @@ def test_ols_model_still_needs_a_trained_folder(tmp_path):
 # ---- schedule --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('E', [1, 2, 3, 4, 5, 6, 7, 8, 9, 50])
 def test_learning_rates_are_the_references_multisteplr(E):
-    from pyqg_generative_amd.tools import train_CNN
+    from pyqg_generative_amd.tools import train_CNN, train_common
     p = torch.zeros(1, requires_grad=True)
     opt = torch.optim.Adam([p], lr=1e-3)
     sched = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=[int(E / 2), int(E * 3 / 4), int(E * 7 / 8)], gamma=0.1)
@@ -216,7 +216,7 @@ def test_learning_rates_are_the_references_multisteplr(E):
         want.append(opt.param_groups[0]['lr'])
         opt.step()
         sched.step()
-    assert train_CNN.learning_rates(E, 1e-3) == want
+    assert train_common.learning_rates(E, 1e-3) == want
     assert cr.lr_sequence(E, 1e-3) == pytest.approx(want, rel=1e-12)
     if E == 50:
         assert [want[0], want[24], want[25], want[37], want[43]] == pytest.approx([1e-3, 1e-3, 1e-4, 1e-5, 1e-6], rel=1e-12)

@@ -160,7 +160,7 @@ def test_same_bits_again_and_on_another_stream(shape):
 def test_wrappers_and_autograd():
     """tools/train_CNN.py's surface: gather_batch, head_apply, and head_loss through torch.autograd (the incoming gradient is
     read on the device), the cached workspace, the refusals of the facade"""
-    from pyqg_generative_amd.tools import train_CNN as T
+    from pyqg_generative_amd.tools import train_ops as T
     case = _case((3, 16, 2), True, True)
     dev = _dev()
     y, src, t = (torch.tensor(case[k]).to(dev) for k in ('y', 'src', 't'))

@@ -68,7 +68,8 @@ def _compare(got, r64, r32, what):
 def test_one_step_of_a_softplus_net_and_the_indexed_loss():
     """compute_loss (torch expressions at both ends) and indexed_loss (the kernels at both ends) of one state dict: the loss,
     every parameter's gradient and the running statistics against float64, and against each other"""
-    from pyqg_generative_amd.tools.train_CNN import FusedHeadCNN, HEAD_LAUNCHES
+    from pyqg_generative_amd.tools.train_CNN import FusedHeadCNN
+    from pyqg_generative_amd.tools.train_ops import HEAD_LAUNCHES
     sd = {k: v.clone() for k, v in FusedHeadCNN(2, 2, HIDDEN, head='softplus_mse', seed=21).state_dict().items()}
     X, T = _batch(31, 7)
     idx = np.array([5, 0, 6, 2])
@@ -108,7 +109,8 @@ def test_one_step_of_a_softplus_net_and_the_indexed_loss():
 def test_trajectory_of_ten_adam_steps_through_train():
     """train()'s loop with a net that offers the indexed loss: 8 samples in batches of 4 over 5 epochs, the batch order fixed;
     every training and test batch goes through the kernels"""
-    from pyqg_generative_amd.tools.train_CNN import FusedHeadCNN, train, HEAD_LAUNCHES
+    from pyqg_generative_amd.tools.train_CNN import FusedHeadCNN, train
+    from pyqg_generative_amd.tools.train_ops import HEAD_LAUNCHES
     net = FusedHeadCNN(2, 2, HIDDEN, head='softplus_mse', seed=22)
     sd = {k: v.clone() for k, v in net.state_dict().items()}
     x, y = _batch(32, 8)

@@ -27,11 +27,12 @@ def stencil_rows(img, s, step=1):
     return np.concatenate(out, axis=0)
 
 
-def prepare_data(images, s):
+def prepare_data(images, s, step=STEP):
     """images: [(q (n, N, N), forcing (n, N, N)), ...] -> X (R, s * s), Y (R, 1), x_scale, y_scale: the population std of
-    the centre feature and of the targets, in float64, cast to float32, as Python floats"""
-    X = np.concatenate([stencil_rows(q, s, STEP) for q, _ in images], axis=0)
-    Y = np.concatenate([stencil_rows(f, 1, STEP) for _, f in images], axis=0)
+    the centre feature and of the targets, in float64, cast to float32, as Python floats.  (step: the reference's 3; the
+    kernel tests also take every point, step 1, for batches of many tiles.)"""
+    X = np.concatenate([stencil_rows(q, s, step) for q, _ in images], axis=0)
+    Y = np.concatenate([stencil_rows(f, 1, step) for _, f in images], axis=0)
     x_scale = float(X[:, s * s // 2].astype('float64').std().astype('float32'))
     y_scale = float(Y.astype('float64').std().astype('float32'))
     return X, Y, x_scale, y_scale

@@ -52,7 +52,7 @@ def backward_data(dy, w):
     for ky in range(k):
         for kx in range(k):
             # dx[y, x] += dy[y - ky + P, x - kx + P] w[ky, kx]: roll dy by (ky - P, kx - P)
-            dx += np.einsum('oc,boyx->bcyx', w[:, :, ky, kx], np.roll(g, (ky - p, kx - p), axis=(2, 3)))
+            dx += np.einsum('oc,boyx->bcyx', w[:, :, ky, kx], np.roll(g, (ky - p, kx - p), axis=(2, 3)), optimize=True)
     return to_layout(dx)
 
 

@@ -14,6 +14,7 @@ torch = pytest.importorskip('torch')
 from conftest import ROOT
 
 import conv_train_restatement as cr
+import train_plan_restatement as tp
 
 SHAPES = [(2, 5, 5), (5, 2, 3), (8, 32, 3), (33, 7, 3)]
 
@@ -56,6 +57,65 @@ def test_integer_cases_are_exact_in_float32():
     """every product and partial sum of the GPU test's integer cases stays below 2^24 in magnitude"""
     for (cin, cout, k), (B, N) in [((256, 1, 3), (3, 16)), ((70, 40, 5), (2, 48)), ((1, 256, 3), (34, 16)), ((40, 70, 5), (3, 16))]:
         assert 9 * cin * k * k + 3 < 2 ** 24 and 9 * cout * k * k < 2 ** 24 and 9 * B * N * N < 2 ** 24
+    for cin, cout, k, B, N in _gpu_cases():
+        assert 9 * cin * k * k + 3 < 2 ** 24 and 9 * cout * k * k < 2 ** 24 and 9 * B * N * N < 2 ** 24
+
+
+# ---- the weight gradient's plan --------------------------------------------------------------------------------------
+def _gpu_cases():
+    """every case of tests/test_gpu_conv_train.py, old and new (the module asks for no device when it is imported)"""
+    import test_gpu_conv_train as g
+    return list(g.CASES)
+
+
+def _library_bytes(cin, cout, k, B, N):
+    from pyqg_generative_amd._lib import lib
+    n = C.c_size_t(0)
+    assert lib.qgx_conv2d_workspace(B, N, cin, cout, k, C.byref(n)) == 0
+    return n.value
+
+
+def test_restated_plan_gives_the_librarys_workspace_size_for_every_gpu_case():
+    """the workspace holds S x pairs x k^2 x 1024 floats of partial sums and nb x cout8 of bias block sums: its size, which the
+    library computes without a device, pins the restated plan's S and nb (tests/train_plan_restatement.py)"""
+    cases = _gpu_cases()
+    assert len(cases) >= 27 and set(tp.CONV_REGIMES) <= set(cases)
+    for case in cases:
+        cin, cout, k, B, N = case
+        assert _library_bytes(*case) == tp.conv_workspace_bytes(B, N, cin, cout, k), case
+
+
+def test_restated_plan_gives_the_librarys_workspace_size_on_a_sweep():
+    n = 0
+    for N in tp.GRIDS:
+        for k in (3, 5):
+            for B in (1, 2, 3, 9, 23, 64, 130):
+                for cin in (1, 8, 33, 70, 256):
+                    for cout in (1, 8, 33, 70, 256):
+                        assert _library_bytes(cin, cout, k, B, N) == tp.conv_workspace_bytes(B, N, cin, cout, k), (cin, cout, k, B, N)
+                        n += 1
+    assert n == 6 * 2 * 7 * 25
+
+
+def test_declared_regimes_hold_in_the_restated_plan():
+    """each GPU case that is there for a regime is in it; and the plan's own invariants over the sweep: every unit in exactly
+    one share, every pixel in exactly one block, the patches within the LDS a workgroup may ask for"""
+    for case, regime in tp.CONV_REGIMES.items():
+        cin, cout, k, B, N = case
+        plan = tp.wgrad_plan(B, N, cin, cout, k)
+        assert {key: plan[key] for key in regime} == regime, case
+    for N in tp.GRIDS:
+        for k in (3, 5):
+            for B in (1, 2, 3, 9, 23, 64, 130):
+                for c in (1, 33, 256):
+                    p = tp.wgrad_plan(B, N, c, c, k)
+                    assert N % p['R'] == 0 and p['U'] * p['R'] == B * N and p['lds'] <= 160 * 1024
+                    assert (p['S'] - 1) * p['ups'] < p['U'] <= p['S'] * p['ups'] and 1 <= p['last_units'] <= p['ups']
+                    assert (p['nb'] - 1) * p['ppb'] < B * N * N <= p['nb'] * p['ppb'] and p['nb'] <= 256 and p['ppb'] >= 64
+                    assert 1 <= p['G'] and p['G'] * cr.c8(c) <= 256
+    # the shipped shape at batch 64 on 64 x 64 runs deep in the regime the new cases enter
+    p = tp.wgrad_plan(64, 64, 128, 64, 3)
+    assert (p['R'], p['ups'], p['ppb']) == (2, 32, 1024)
 
 
 # ---- declarations and bindings ---------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """GPU: training of ANNModel on the device (csrc/ann_train.hip, include/qgx_train.h, tools/train_ANN.py) against the
 restatement of tests/ann_training_restatement.py: stencil rows, scales, loss and gradient against float64 autograd, Adam
-against torch.optim.Adam, a training trajectory through fit_ann, and the model folder it writes.
+against torch.optim.Adam, a training trajectory through fit_ann, and the model folder it writes.  Loss and gradient run at
+two batch sizes: up to 4096 rows, where every workgroup takes one tile, and above 256 x 128 rows, where workgroups add two
+to four tiles into their partial sums (section 3b; tests/train_plan_restatement.py::ann_plan restates the partition).
 
 All data follow the recipe of the restatement: band-limited images of unit variance, targets from a seeded teacher net plus
 0.1 white noise, student weights from weights.synthetic_ann."""
@@ -11,6 +13,7 @@ import pytest
 import torch
 
 import ann_training_restatement as ar
+import train_plan_restatement as tp
 from redzone import guarded
 
 pytestmark = pytest.mark.gpu
@@ -136,6 +139,109 @@ def test_loss_and_gradient_match_float64_autograd(recipe, s, hidden, si):
     t.close()
 
 
+# ---- 3b. more than one tile per workgroup ----------------------------------------------------------------------------
+# A gradient launch has at most 256 workgroups, and workgroup w walks the tiles w, w + 256, ... of RT <= 128 rows.  Up to
+# 256 RT rows (every batch above) each workgroup runs ONE tile: the accumulation across tiles (part[o] + s[kk]), the barrier
+# between tiles, and a short last tile written over the columns an earlier full tile left never run.  fit_ann's test-set
+# loss and every batch of the reference's size on a small net are in that regime.
+MANY_TILES_BOUND = 2e-6
+
+
+@pytest.fixture(scope='module')
+def dense():
+    """per stencil size: the rows of 64 images at 24 x 24 at EVERY point (step 1): 36 864 rows, their scales"""
+    out = {}
+    for s, si in sorted({(s, si) for s, _, si in SHAPES}):
+        q, f = ar.teacher_student_images(64, 24, 10 + s, s=s, scale_invariant=si)
+        X, Y, xs, ys = ar.prepare_data([(q, f)], s, step=1)
+        assert X.shape == (36864, s * s)
+        out[s, si] = dict(X=X, Y=Y, xs=xs, ys=ys, Xd=torch.as_tensor(X).cuda().contiguous(), Yd=torch.as_tensor(Y).cuda().contiguous())
+    return out
+
+
+def _errors(loss, grads, loss64, g64):
+    """relative error of the loss; per tensor the largest gradient error over the largest |gradient|"""
+    return abs(loss - loss64) / loss64, [float(np.abs(np.asarray(g, np.float64) - w).max() / np.abs(w).max()) for g, w in zip(grads, g64)]
+
+
+@pytest.mark.parametrize('s,hidden,si', SHAPES)
+def test_many_tiles_per_workgroup_match_float64_autograd(dense, s, hidden, si):
+    from pyqg_generative_amd import _lib
+    from pyqg_generative_amd.tools.train_ANN import AnnTrainer
+    r = dense[s, si]
+    net = _student(s, hidden, si)
+    x64, y64 = ar.normalised(r['X'], r['Y'], r['xs'], r['ys'], torch.float64)
+    keep = np.nonzero(ar.min_abs_preactivation(net, x64.numpy()) >= 1e-4)[0]
+    dropped = 1.0 - keep.size / x64.shape[0]
+    assert dropped <= 0.03
+    while keep.size % 4 == 0:
+        keep = keep[:-1]
+    n = keep.size
+    # RT <= 128 for every net, so this alone means more than one tile in some workgroup; the restated plan says how many
+    assert n > 256 * 128
+    plan = tp.ann_plan(s, hidden, n)
+    assert plan['nparts'] == 256 and plan['tiles_per_workgroup'] >= 2 and plan['last_rows'] % 4 != 0
+    print(f'\n{s} {hidden} si={si}: {dropped:.2%} of {x64.shape[0]} rows dropped, {n} rows, {plan}')
+    loss64, g64 = _autograd64(net, x64[keep], y64[keep])
+    # the float32 torch CPU evaluation of the same rows: the yardstick the bound was chosen against (DESIGN 3.17)
+    m32 = ar.TorchANN(net, torch.float32)
+    l32 = m32.loss(x64[keep].float(), y64[keep].float())
+    l32.backward()
+    cpu_loss, cpu_grad = _errors(float(l32.detach()), [p.grad.numpy() for p in m32.parameters()], loss64, g64)
+    t = AnnTrainer(net, device=0)
+    idx_d = torch.as_tensor(keep.astype(np.int64)).cuda()
+    acc = guarded((2,), torch.float64, _dev(), fill=0x00)
+    t.grad(r['Xd'], r['Yd'], idx_d, r['xs'], r['ys'], acc.t)
+    g1 = t.read(_lib.TRAIN_GRAD)
+    acc.check(what='loss_acc_dev')
+    a = acc.t.cpu().numpy()
+    assert a[1] == n
+    dev_loss, dev_grad = _errors(a[0] / a[1], t.unpack(g1).values(), loss64, g64)
+    print(f'  loss: device {dev_loss:.2e}, float32 torch CPU {cpu_loss:.2e}')
+    for (key, _), d, c in zip(t.shapes, dev_grad, cpu_grad):
+        print(f'    {key}: device {d:.2e}, float32 torch CPU {c:.2e} of max |g|')
+    assert dev_loss <= MANY_TILES_BOUND
+    for (key, _), d in zip(t.shapes, dev_grad):
+        assert d <= MANY_TILES_BOUND, (key, d)
+    # a second identical call: the same bits, and the accumulator adds up
+    t.grad(r['Xd'], r['Yd'], idx_d, r['xs'], r['ys'], acc.t)
+    assert np.array_equal(g1.view(np.int32), t.read(_lib.TRAIN_GRAD).view(np.int32))
+    acc.check(what='loss_acc_dev')
+    assert np.array_equal(acc.t.cpu().numpy(), 2 * a)
+    # on another stream: the same bits
+    st = torch.cuda.Stream()
+    st.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(st):
+        t.grad(r['Xd'], r['Yd'], idx_d, r['xs'], r['ys'], None)
+    st.synchronize()
+    assert np.array_equal(g1.view(np.int32), t.read(_lib.TRAIN_GRAD).view(np.int32))
+    # forward only: the same loss
+    acc2 = guarded((2,), torch.float64, _dev(), fill=0x00)
+    t.loss(r['Xd'], r['Yd'], idx_d, r['xs'], r['ys'], acc2.t)
+    torch.cuda.synchronize()
+    acc2.check(what='loss_acc_dev')
+    assert np.array_equal(acc2.t.cpu().numpy(), a)
+    # fit_ann's test-set path: idx = NULL over all 36 864 rows is idx = arange bit for bit, and the float64 loss of those rows
+    R = r['Xd'].shape[0]
+    assert tp.ann_plan(s, hidden, R)['tiles_per_workgroup'] >= 2
+    acc3 = guarded((2,), torch.float64, _dev(), fill=0x00)
+    acc4 = guarded((2,), torch.float64, _dev(), fill=0x00)
+    t.loss(r['Xd'], r['Yd'], None, r['xs'], r['ys'], acc3.t)
+    t.loss(r['Xd'], r['Yd'], torch.arange(R, device=_dev()), r['xs'], r['ys'], acc4.t)
+    torch.cuda.synchronize()
+    acc3.check(what='loss_acc_dev')
+    acc4.check(what='loss_acc_dev')
+    a3 = acc3.t.cpu().numpy()
+    assert np.array_equal(a3.view(np.int64), acc4.t.cpu().numpy().view(np.int64)) and a3[1] == R
+    with torch.no_grad():
+        all64 = float(ar.TorchANN(net, torch.float64).loss(x64, y64))
+        all32 = float(ar.TorchANN(net, torch.float32).loss(x64.float(), y64.float()))
+    err = abs(a3[0] / a3[1] - all64) / all64
+    print(f'  all {R} rows, idx = NULL: loss error device {err:.2e}, float32 torch CPU {abs(all32 - all64) / all64:.2e}')
+    assert err <= MANY_TILES_BOUND
+    t.close()
+
+
 def test_zero_stencil_gives_nan_under_scale_invariance(recipe):
     from pyqg_generative_amd import _lib
     from pyqg_generative_amd.tools.train_ANN import AnnTrainer
@@ -192,7 +298,7 @@ def test_adam_matches_torch_optim_adam():
     t.close()
 
 
-def test_step_is_grad_then_adam_bitwise(recipe):
+def test_step_is_grad_then_adam_bitwise(recipe, dense):
     from pyqg_generative_amd import _lib
     from pyqg_generative_amd.tools.train_ANN import AnnTrainer
     for s, hidden, si in (SHAPES[0], SHAPES[2]):
@@ -211,6 +317,17 @@ def test_step_is_grad_then_adam_bitwise(recipe):
             for what in range(4):
                 assert np.array_equal(a.read(what).view(np.int32), b.read(what).view(np.int32)), (s, k, what)
             assert torch.equal(acc_a, acc_b)
+        # one batch of more than 256 tiles: every workgroup's slice of the partial sums, some written over two or more tiles
+        d = dense[s, si]
+        n = 33001
+        assert n > 32768 and tp.ann_plan(s, hidden, n)['tiles_per_workgroup'] >= 2
+        idx = torch.as_tensor(rs.permutation(d['X'].shape[0])[:n].astype(np.int64)).cuda()
+        a.step(d['Xd'], d['Yd'], idx, d['xs'], d['ys'], 1e-4, acc_a)
+        b.grad(d['Xd'], d['Yd'], idx, d['xs'], d['ys'], acc_b)
+        b.adam(1e-4)
+        for what in range(4):
+            assert np.array_equal(a.read(what).view(np.int32), b.read(what).view(np.int32)), (s, n, what)
+        assert torch.equal(acc_a, acc_b)
         assert not np.array_equal(a.read(_lib.TRAIN_PARAMS), np.concatenate([np.r_[w.ravel(), bb] for w, bb in zip(net['w'], net['b'])]))
         a.close()
         b.close()

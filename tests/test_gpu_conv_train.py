@@ -3,11 +3,13 @@ restatement of tests/conv_train_restatement.py: exact on integer data, within th
 zero pad channels, the same bits on a second call and on another stream, and every output and the workspace between guard
 bands (tests/redzone.py).
 
-The ragged case.  The weight gradient cuts the U = B N / R units of R image rows (R = 4 where the two LDS patches of four
-rows fit 80 KiB: every tested shape but the 5 x 5 one at 48 x 48, which has R = 2) into S shares of
-ups = ceil(U / min(U, ceil(512 / pairs))) units, pairs = ceil(cout / 32) ceil(cin / 32).  (cin, cout, k) = (1, 256, 3) at
-B = 34, N = 16 has pairs = 8, U = 136, ups = 3, S = 46: the last share holds ONE unit where the others hold three.  (Every
-other tested shape has ups = 1.)"""
+More than one unit per share.  The weight gradient cuts the U = B N / R units of R image rows into S shares of `ups` consecutive
+units, and the bias gradient the B N^2 pixels into blocks of ppb pixels; a workgroup that takes more than one unit (or a thread
+more than one pixel per group) runs the accumulate-across-units code, the restaging barrier, the short last share.  Which case
+does so is decided by the host-side plan, restated in tests/train_plan_restatement.py and pinned to the library on the CPU
+(tests/test_conv_train_cpu.py).  The cases that are here for such a regime declare it as data (CONV_REGIMES there) and _run
+asserts it against the restated plan before it launches; test_regime_table prints R, U, ups, S, the last share's units, the LDS
+bytes and ppb of EVERY case from that plan — the table is computed, not written down here."""
 import ctypes as C
 import functools
 
@@ -16,6 +18,7 @@ import pytest
 import torch
 
 import conv_train_restatement as cr
+import train_plan_restatement as tp
 from redzone import guarded
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +27,8 @@ SHAPES = [(2, 5, 5), (5, 2, 3), (8, 32, 3), (33, 7, 3), (40, 70, 5), (70, 40, 5)
 CASES = [s + (3, 16) for s in SHAPES] + \
         [s + bn for s in ((33, 7, 3), (40, 70, 5)) for bn in ((2, 48), (1, 16), (1, 48))] + \
         [(1, 256, 3, 34, 16)] + \
-        [(8, 8, 5, 1, 32), (8, 8, 3, 2, 64), (8, 8, 3, 1, 96), (8, 8, 5, 1, 128)]       # ragged (module docstring); the other grids
+        [(8, 8, 5, 1, 32), (8, 8, 3, 2, 64), (8, 8, 3, 1, 96), (8, 8, 5, 1, 128)]       # a ragged last share; the other grids
+CASES += [c for c in tp.CONV_REGIMES if c not in CASES]                                 # more than one unit per share
 IDS = ['cin%d-cout%d-k%d-B%d-N%d' % c for c in CASES]
 
 
@@ -53,9 +57,30 @@ def _truth(case, integer, absolute=False):
     return out
 
 
+def _assert_regime(case):
+    """a case that is here for a regime still is in it, by the restated plan"""
+    cin, cout, k, B, N = case
+    plan = tp.wgrad_plan(B, N, cin, cout, k)
+    for key, want in tp.CONV_REGIMES.get(case, {}).items():
+        assert plan[key] == want, f'{case} is no longer in its regime: {key} = {plan[key]}, declared {want}'
+
+
+def test_regime_table():
+    print('\n' + tp.regime_table(CASES))
+    assert all(c in CASES for c in tp.CONV_REGIMES)
+    plans = [tp.wgrad_plan(c[3], c[4], c[0], c[1], c[2]) for c in CASES]
+    # what the cases cover between them: every unit size with several units per share, both LDS caps, every grid with either k
+    assert {(p['R'], min(p['ups'], 3)) for p in plans} >= {(R, u) for R in (1, 2, 4) for u in (1, 2, 3)} - {(2, 3)}
+    assert {p['under_80k'] for p in plans} == {True, False} and any(p['crosses_image'] for p in plans)
+    assert any(p['ups'] > 1 and p['cot_n'] > 1 and p['cit_n'] > 1 for p in plans)
+    assert any(p['dbias_passes'] > 2 and not p['dbias_even'] for p in plans)
+    assert {(c[4], c[2]) for c in CASES} >= {(128, 3), (96, 5), (64, 5)}
+
+
 def _run(case, integer, bias=True, guard=True):
     """the three calls through the C ABI on guarded buffers -> (y, dx, dw, db) as numpy, after the guard checks"""
     from pyqg_generative_amd._lib import lib, check, current_stream_ptr
+    _assert_regime(case)
     cin, cout, k, B, N = case
     x, w, b, dy = (torch.as_tensor(a).to(_dev()) for a in _data(case, integer))
     n = C.c_size_t()
@@ -136,7 +161,10 @@ def test_same_bits_again_and_on_another_stream(case):
         assert np.array_equal(a.view(np.int32), c.view(np.int32)), f'{name}: another stream gave other bits'
 
 
-@pytest.mark.parametrize('case', [CASES[0], CASES[3], CASES[-1]], ids=[IDS[0], IDS[3], IDS[-1]])
+NO_BIAS = [CASES[0], CASES[3], (8, 8, 5, 1, 128), (40, 70, 5, 23, 16)]      # the last: several units per share
+
+
+@pytest.mark.parametrize('case', NO_BIAS, ids=[IDS[CASES.index(c)] for c in NO_BIAS])
 def test_without_bias_nothing_is_added_and_db_is_not_touched(case):
     cin, cout, k, B, N = case
     y, dx, dw, _ = _run(case, True, bias=False)
@@ -147,21 +175,23 @@ def test_without_bias_nothing_is_added_and_db_is_not_touched(case):
 
 
 def test_a_stale_workspace_changes_nothing():
-    """the workspace's previous contents (NaN patterns, another shape's partial sums) do not enter a result"""
+    """the workspace's previous contents (NaN patterns, another shape's partial sums) do not enter a result; the case with
+    ups = 2 covers the slices a workgroup writes after its later units"""
     from pyqg_generative_amd._lib import lib, check, current_stream_ptr
-    case = (40, 70, 5, 3, 16)
-    cin, cout, k, B, N = case
-    want = _run(case, False, guard=False)
-    x, w, b, dy = (torch.as_tensor(a).to(_dev()) for a in _data(case, False))
-    n = C.c_size_t()
-    check(lib.qgx_conv2d_workspace(B, N, cin, cout, k, C.byref(n)))
-    for fill in (0x00, 0x7F):
-        ws = guarded((n.value,), torch.uint8, _dev(), fill=fill)
-        dw = torch.empty((cout, cin, k, k), device=_dev())
-        db = torch.empty((cout,), device=_dev())
-        check(lib.qgx_conv2d_backward_weight(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), db.data_ptr(), B, N, cin, cout, k,
-                                             ws.t.data_ptr(), n.value, current_stream_ptr()))
-        torch.cuda.synchronize()
-        ws.check(what='workspace')
-        assert np.array_equal(dw.cpu().numpy().view(np.int32), want[2].view(np.int32))
-        assert np.array_equal(db.cpu().numpy().view(np.int32), want[3].view(np.int32))
+    for case in ((40, 70, 5, 3, 16), (40, 70, 5, 23, 16)):
+        assert tp.wgrad_plan(case[3], case[4], *case[:3])['ups'] == (1 if case[3] == 3 else 2)
+        cin, cout, k, B, N = case
+        want = _run(case, False, guard=False)
+        x, w, b, dy = (torch.as_tensor(a).to(_dev()) for a in _data(case, False))
+        n = C.c_size_t()
+        check(lib.qgx_conv2d_workspace(B, N, cin, cout, k, C.byref(n)))
+        for fill in (0x00, 0x7F):
+            ws = guarded((n.value,), torch.uint8, _dev(), fill=fill)
+            dw = torch.empty((cout, cin, k, k), device=_dev())
+            db = torch.empty((cout,), device=_dev())
+            check(lib.qgx_conv2d_backward_weight(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), db.data_ptr(), B, N, cin, cout, k,
+                                                 ws.t.data_ptr(), n.value, current_stream_ptr()))
+            torch.cuda.synchronize()
+            ws.check(what='workspace')
+            assert np.array_equal(dw.cpu().numpy().view(np.int32), want[2].view(np.int32)), (case, fill)
+            assert np.array_equal(db.cpu().numpy().view(np.int32), want[3].view(np.int32)), (case, fill)

@@ -6,7 +6,14 @@ output and the workspace between guard bands (tests/redzone.py).
 Shapes (B, N): the smallest (1, 16): one workgroup, one partial; (3, 16) and (5, 16): odd partial counts; (2, 48): a grid that
 is no power of two, 18 partials; (1, 128): the largest pixel offset within an image.  C = 2 throughout, C = 1 and C = 8 (the
 second 16-byte half of a record) at (3, 16).  Every shape runs without idx (n = B + 2 rows, the first B used) and with a
-permuted idx into n = B + 2 rows that repeats a row."""
+permuted idx into n = B + 2 rows that repeats a row.
+
+More than one share per thread.  The loss is cut into nb <= 1024 partials of ppb pixels (tests/train_plan_restatement.py restates
+the plan; tests/test_head_train_cpu.py pins it to the library).  Up to 65 536 pixels every thread of k_head_finish adds one
+partial at the most, and up to 262 144 every thread of k_head_loss one pixel.  (257, 16): 257 partials, thread 0 of
+k_head_finish adds two; (5, 128): 320 partials at the largest offsets within an image; (1025, 16) with C = 2 and C = 8:
+ppb = 512 — the second pass of k_head_loss — with 513 partials, the last of 256 pixels only.  These shapes declare their regime
+as data (HEAD_REGIMES there) and _run asserts it against the restated plan before it launches."""
 import ctypes as C
 
 import numpy as np
@@ -15,11 +22,13 @@ import torch
 
 import conv_train_restatement as cr
 import head_restatement as hr
+import train_plan_restatement as tp
 from redzone import guarded
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 16, 2), (3, 16, 2), (5, 16, 2), (2, 48, 2), (1, 128, 2), (3, 16, 1), (3, 16, 8)]
+SHAPES += list(tp.HEAD_REGIMES)          # (257, 16, 2), (5, 128, 2), (1025, 16, 2), (1025, 16, 8)
 IDS = [f'B{b}-N{n}-C{c}' for b, n, c in SHAPES]
 SOFTPLUS_MARGIN = 4.0
 
@@ -57,6 +66,9 @@ def _run(case, mode, gout=1.0, stream=None):
     """the five calls through the C ABI on guarded buffers -> {name: numpy} after the guard checks"""
     from pyqg_generative_amd._lib import lib, check, current_stream_ptr
     B, N, Cn, n = case['B'], case['N'], case['C'], case['n']
+    plan = tp.head_plan(B, N)
+    for key, want in tp.HEAD_REGIMES.get((B, N, Cn), {}).items():
+        assert plan[key] == want, f'{(B, N, Cn)} is no longer in its regime: {key} = {plan[key]}, declared {want}'
     m = hr.MODES[mode]
     dev = _dev()
     y, src, t = (torch.tensor(case[k]).to(dev) for k in ('y', 'src', 't'))
@@ -142,7 +154,7 @@ def test_softplus_mode_within_four_times_float32_torch(shape, with_idx):
         assert dev <= SOFTPLUS_MARGIN * ref, (name, dev, ref)
 
 
-@pytest.mark.parametrize('shape', [SHAPES[2], SHAPES[3], SHAPES[6]], ids=[IDS[2], IDS[3], IDS[6]])
+@pytest.mark.parametrize('shape', [SHAPES[2], SHAPES[3], SHAPES[6], (1025, 16, 2)], ids=[IDS[2], IDS[3], IDS[6], 'B1025-N16-C2'])
 def test_same_bits_again_and_on_another_stream(shape):
     case = _case(shape, False, True)
     a, b = _run(case, 'softplus_mse', 0.375), _run(case, 'softplus_mse', 0.375)

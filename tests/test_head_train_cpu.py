@@ -15,6 +15,7 @@ from conftest import ROOT
 
 import conv_train_restatement as cr
 import head_restatement as hr
+import train_plan_restatement as tp
 
 EDGE = np.array([20.0, np.nextafter(np.float32(20), np.float32(21)), 30.0, -30.0, -100.0, 1e4, -1e4, 0.0, 19.999998], np.float32)
 
@@ -74,8 +75,44 @@ def test_gather_restatement_is_the_index_and_the_layout():
 def test_integer_cases_are_exact():
     """every difference of the GPU test's integer cases is below 2^24 (float32) and every sum of squares below 2^53"""
     assert 16 < 2 ** 24 and 16 * 16 * 8 * 128 * 128 * 5 < 2 ** 53
+    assert all(16 * 16 * Cn * N * N * B < 2 ** 53 for B, N, Cn in _gpu_shapes())
     # a float32 scale times an integer difference of 5 bits is exact in float64
     assert 24 + 5 <= 53
+
+
+# ---- the loss's plan ---------------------------------------------------------------------------------------------------------
+def _gpu_shapes():
+    """every shape of tests/test_gpu_head_train.py, old and new (the module asks for no device when it is imported)"""
+    import test_gpu_head_train as g
+    return list(g.SHAPES)
+
+
+def test_restated_plan_gives_the_librarys_workspace_size():
+    """The workspace is one float64 per partial, rounded up to 256 bytes, so its size resolves the number of partials nb ONLY
+    TO 32: it tells 257 partials from 256, and 513 from 512, but not 320 from 300.  Within that resolution the restated plan
+    (tests/train_plan_restatement.py) is pinned to the library, for every GPU shape and on a sweep; the sweep's B are chosen
+    with B N^2 / 256 on both sides of multiples of 32 and of the cap of 1024 partials."""
+    shapes = _gpu_shapes()
+    assert len(shapes) >= 11 and set(tp.HEAD_REGIMES) <= set(shapes)
+    grids = [(B, N) for B, N, _ in shapes]
+    grids += [(B, N) for N in tp.GRIDS for B in (1, 2, 3, 9, 23, 64, 130, 256, 257, 1023, 1024, 1025, 2 ** 29 // (N * N))]
+    grids += [(B, N) for N in tp.GRIDS for q in (32, 256, 1024) for B in (q * 256 // (N * N), q * 256 // (N * N) + 1) if B >= 1]
+    for B, N in grids:
+        rc, n = _workspace_bytes(B, N)
+        assert rc == 0 and n == tp.head_workspace_bytes(B, N), (B, N)
+
+
+def test_declared_regimes_hold_in_the_restated_plan():
+    for (B, N, Cn), regime in tp.HEAD_REGIMES.items():
+        plan = tp.head_plan(B, N)
+        assert {key: plan[key] for key in regime} == regime, (B, N, Cn)
+    # the plan's own invariants: every pixel in exactly one block, blocks whole multiples of the 256 threads
+    for N in tp.GRIDS:
+        for B in (1, 2, 3, 9, 23, 64, 130, 257, 1025, 5000):
+            p = tp.head_plan(B, N)
+            assert (p['nb'] - 1) * p['ppb'] < B * N * N <= p['nb'] * p['ppb'] and p['nb'] <= 1024 and p['ppb'] % 256 == 0
+    # fit_meanvar's batch of 64 at 64 x 64 sits on the boundary: one more image and k_head_loss takes a second pass
+    assert tp.head_plan(64, 64)['loss_passes'] == 1 and tp.head_plan(65, 64)['loss_passes'] == 2
 
 
 def test_var_net_is_the_reference_net_plus_softplus():

@@ -207,6 +207,14 @@ HEAD_TRAIN_SYMBOLS = [
     ('qgx_head_apply', C.c_int, _HEAD + [C.c_void_p] + _HEAD_SHAPE + [C.c_void_p]),
 ]
 
+# what include/qgx_flux_train.h declares: 10000 divergence(F) of a flux-form net and its adjoint (tools/train_ops.py)
+FLUX_PLANAR, FLUX_ENGINE = 0, 1
+_FLUX = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]                     # in, out, B, N, layout, stream
+FLUX_TRAIN_SYMBOLS = [
+    ('qgx_fluxdiv_forward', C.c_int, _FLUX),
+    ('qgx_fluxdiv_backward', C.c_int, _FLUX),
+]
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -219,7 +227,8 @@ def _load():
     # Load torch's first — torch finds no GPU when it is handed the other runtime.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS + TRAIN_SYMBOLS + CONV_TRAIN_SYMBOLS + HEAD_TRAIN_SYMBOLS:
+    for name, res, args in (SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS + TRAIN_SYMBOLS + CONV_TRAIN_SYMBOLS + HEAD_TRAIN_SYMBOLS
+                            + FLUX_TRAIN_SYMBOLS):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -14,63 +14,17 @@
 //   Hy(l,k) = i dk l for l != N/2; on the row l = N/2: i dk (-N/2) sign(k), and 0 at k = 0 and k = N/2
 // (tests/div_restatement.py states both forms and checks that they agree to 1e-12 in float64).
 #include "generator.hpp"
-#include "fft_lds_f32.hpp"
+#include "fluxdiv_core.hpp"
 
 namespace qgx {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fluxdiv_smem[];
 
-constexpr int fluxdiv_threads(int N) { return N >= 64 ? 1024 : 256; }
-constexpr size_t fluxdiv_lds_bytes(int N) { return (size_t)N * (N + 1) * sizeof(float2) + N * sizeof(float2) + N * sizeof(int); }
-
+// the body (load, FFT, pair multiply, inverse, scale, store) is fluxdiv_core.hpp's: the training step's forward in the engine
+// layout (fluxdiv_train.hip) is a second instantiation of the same function
 template <int N>
 __global__ __launch_bounds__(fluxdiv_threads(N)) void k_fluxdiv(const float *__restrict__ F, float *__restrict__ y) {
-    constexpr int LD = N + 1, H = N / 2;
-    float2 *Z = reinterpret_cast<float2 *>(fluxdiv_smem);      // [N][LD]
-    float2 *tw = Z + N * LD;                                     // exp(-2 pi i j / N), j < N
-    int *pos = reinterpret_cast<int *>(tw + N);                  // where the forward transform leaves frequency j
-    const int b = blockIdx.x >> 1, c = blockIdx.x & 1;
-    const float *fx = F + ((size_t)b * 4 + c) * N * N, *fy = fx + 2 * (size_t)N * N;
-    for (int i = threadIdx.x; i < N * N / 4; i += blockDim.x) {  // N % 4 == 0: a quad stays in its row
-        const float4 a = reinterpret_cast<const float4 *>(fx)[i], d = reinterpret_cast<const float4 *>(fy)[i];
-        const int r = 4 * i / N, col = 4 * i - r * N;
-        float2 *z = Z + r * LD + col;
-        z[0] = make_float2(a.x, d.x); z[1] = make_float2(a.y, d.y); z[2] = make_float2(a.z, d.z); z[3] = make_float2(a.w, d.w);
-    }
-    for (int j = threadIdx.x; j < N; j += blockDim.x) {
-        double s, co;
-        sincospi(-2.0 * j / N, &s, &co);                         // rounded ONCE from float64
-        tw[j] = make_float2((float)co, (float)s);
-        pos[j] = fft32::freq_pos(j, N);
-    }
-    __syncthreads();
-    fft32::fft2d_fwd<N>(Z, tw);
-    // every conjugate pair {(l,k), (-l,-k)} once: k = 0 .. N/2, and on the two self-paired columns l <= -l (mod N) only
-    const double dk = 6.283185307179586 / 1e6;
-    for (int w = threadIdx.x; w < N * (H + 1); w += blockDim.x) {
-        const int l = w / (H + 1), k = w - l * (H + 1);
-        const int lm = l ? N - l : 0, km = k ? N - k : 0;
-        if ((k == 0 || k == H) && l > lm) continue;
-        float2 *pa = Z + pos[l] * LD + pos[k], *pb = Z + pos[lm] * LD + pos[km];
-        const float2 A = *pa, Bc = make_float2(pb->x, -pb->y);
-        // X = (A + conj B) / 2, Y = (A - conj B) / (2 i): the spectra of fx and fy at (l, k)
-        const float2 X = make_float2(0.5f * (A.x + Bc.x), 0.5f * (A.y + Bc.y));
-        const float2 Y = make_float2(0.5f * (A.y - Bc.y), -0.5f * (A.x - Bc.x));
-        const float wk = k == H ? 0.f : (float)(dk * (double)k);
-        const float wl = l != H ? (float)(dk * (double)(l < H ? l : l - N)) : ((k == 0 || k == H) ? 0.f : (float)(dk * (double)(-H)));
-        const float2 t = make_float2(X.x * wk + Y.x * wl, X.y * wk + Y.y * wl);
-        const float2 D = make_float2(-t.y, t.x);                 // i t
-        *pa = D;
-        *pb = make_float2(D.x, -D.y);                            // (a self-paired bin: D = 0 there, both multipliers vanish)
-    }
-    __syncthreads();
-    fft32::fft2d_inv<N>(Z, tw);
-    float *out = y + ((size_t)b * 2 + c) * N * N;
-    constexpr float inv = 1.0f / (float)(N * N);
-    for (int i = threadIdx.x; i < N * N; i += blockDim.x) {
-        const int r = i / N, col = i - r * N;
-        out[i] = 10000.f * (Z[r * LD + col].x * inv);
-    }
+    fluxdiv_body<N, QGX_FLUX_PLANAR>(F, y, fluxdiv_smem);
 }
 
 bool fluxdiv_size_ok(int N) { return N == 16 || N == 32 || N == 48 || N == 64 || N == 96 || N == 128; }

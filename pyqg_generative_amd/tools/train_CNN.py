@@ -4,7 +4,8 @@ AndrewCNN, :402-421 prepare_PV_data, :607-700 minibatch / evaluate_test / train)
 This module holds the nets, the loop, the data preparation, the folder writers and the fits.  The device operations of a
 step (the convolutions, the batch gather, the loss head) are in tools/train_ops.py, what every fit shares in
 tools/train_common.py.  BatchNorm's batch statistics, ReLU, the MSE, Adam and the learning-rate schedule are torch ops on
-device tensors, and autograd does their backward.  ``fit_ols`` writes the reference's model folder (net.pt, x_scale.json,
+device tensors, and autograd does their backward.  ``fit_ols(div=True)`` trains the flux-form net, ``FluxFormCNN``, whose
+forward ends in the device's spectral divergence (train_ops.flux_divergence).  ``fit_ols`` writes the reference's model folder (net.pt, x_scale.json,
 y_scale.json, model_args.json, stats.nc) and returns ``OLSModel(folder=...)`` read back from those files.
 
 Training of MeanVarModel (reference: models/mean_var_model.py:14-17 VarCNN, :41-80 fit / save_model): ``fit_meanvar`` trains
@@ -25,7 +26,7 @@ from torch import nn
 from .. import weights as _weights
 from .cnn_tools import ChannelwiseScaler
 from .train_common import check_fit_args, command_line, cuda_device, log_epoch, print_start, save_state_dict, stacked, write_log
-from .train_ops import GRIDS, circular_conv2d, gather_batch, head_apply, head_loss, head_mode, to_engine_layout
+from .train_ops import GRIDS, circular_conv2d, flux_divergence, gather_batch, head_apply, head_loss, head_mode, to_engine_layout
 
 
 def _pad(v, n):
@@ -39,17 +40,20 @@ class TrainableAndrewCNN(nn.Module):
     in the engine layout (B, N, N, C8) between layers, ReLU and BatchNorm are torch expressions on them with the
     per-channel vectors padded by zeros to C8, so the pad channels stay zero."""
 
+    FLUX_FORM = False        # FluxFormCNN: the last convolution writes 2 n_out fluxes and the divergence follows it
+
     def __init__(self, n_in, n_out, hidden_channels=(128, 64, 32, 32, 32, 32, 32), batch_norm=True, bias=True, div=False,
                  final_activation='None', seed=0):
         super().__init__()
-        if div:
-            raise NotImplementedError('div=True: the backward of the divergence has no device path yet')
+        if div and not self.FLUX_FORM:
+            raise NotImplementedError('div=True: a flux-form net is a FluxFormCNN, which ends in the divergence kernels; this '
+                                      'class has no divergence behind its last convolution')
         if final_activation != 'None':
             raise NotImplementedError(f'final_activation={final_activation!r} has no device path')
         hidden = _weights.check_hidden_channels(hidden_channels)
         self.n_in, self.n_out, self.hidden_channels = int(n_in), int(n_out), hidden
         self.batch_norm, self.bias = bool(batch_norm), bool(bias)
-        ch = [self.n_in] + hidden + [self.n_out]
+        ch = [self.n_in] + hidden + [2 * self.n_out if self.FLUX_FORM else self.n_out]
         ks = _weights.arch_kernels(hidden)
         blocks = []
         with torch.random.fork_rng(devices=[]):
@@ -102,6 +106,27 @@ class TrainableAndrewCNN(nn.Module):
 
     def compute_loss(self, x, ytrue):
         return {'loss': nn.functional.mse_loss(self.forward(x), ytrue)}
+
+
+class FluxFormCNN(TrainableAndrewCNN):
+    """AndrewCNN(n_in, n_out, div=True, ...) (cnn_tools.py:100-123, 139-142, 170-175): the last convolution writes 2 n_out
+    fluxes [fx of both layers, fy of both layers] and the net returns 10000 * divergence(fluxes), so its output has zero
+    spatial mean by construction.  The state dict is the reference's div=True net's (a last weight of 2 n_out outputs), the
+    seeded initialisation follows the parent's rule, and the divergence is train_ops.flux_divergence: the kernel body the
+    generators run at inference forward, its adjoint backward.  n_out = 2 only: the kernels take the two layers' fluxes."""
+
+    FLUX_FORM = True
+
+    def __init__(self, n_in, n_out, hidden_channels=(128, 64, 32, 32, 32, 32, 32), batch_norm=True, bias=True,
+                 final_activation='None', seed=0):
+        if int(n_out) != 2:
+            raise ValueError(f'n_out = {n_out}: the divergence kernels take the fluxes of 2 layers')
+        super().__init__(n_in, n_out, hidden_channels=hidden_channels, batch_norm=batch_norm, bias=bias, div=True,
+                         final_activation=final_activation, seed=seed)
+
+    def forward_engine(self, a):
+        """(B, N, N, c8(n_in)) -> (B, N, N, 8) with channels [y1, y2, 0, ...]"""
+        return flux_divergence(super().forward_engine(a))
 
 
 class FusedHeadCNN(TrainableAndrewCNN):
@@ -319,12 +344,13 @@ def fit_ols(ds_train, ds_test, *, div=False, batch_norm=True, bias=True, final_a
     """OLSModel(...).fit(ds_train, ds_test, num_epochs, batch_size, learning_rate) on the device, then save_model; returns
     OLSModel(folder=folder) read back from the files.  The net is initialised with torch's Conv2d / BatchNorm2d defaults
     under `seed` (the reference's OLSModel does not call weights_init); the epochs' shuffles come from numpy's global
-    stream unless orders(epoch, n) gives them."""
+    stream unless orders(epoch, n) gives them.  div=True trains a FluxFormCNN: the folder's model_args.json says "div": true
+    and the model read back runs the four-channel last layer with the device's divergence behind it."""
     from ..models.ols_model import OLSModel
     num_epochs, batch_size = int(num_epochs), int(batch_size)
     check_fit_args('fit_ols', num_epochs, batch_size, learning_rate)
-    net = TrainableAndrewCNN(2, 2, hidden_channels=hidden_channels, batch_norm=batch_norm, bias=bias, div=div,
-                             final_activation=final_activation, seed=seed)
+    net_args = dict(hidden_channels=hidden_channels, batch_norm=batch_norm, bias=bias, final_activation=final_activation, seed=seed)
+    net = FluxFormCNN(2, 2, **net_args) if div else TrainableAndrewCNN(2, 2, **net_args)
     X_train, Y_train, X_test, Y_test, x_scale, y_scale = prepare_PV_data(ds_train, ds_test, 'fit_ols')
     train(net, X_train, Y_train, X_test, Y_test, num_epochs, batch_size, learning_rate, device=device, orders=orders, verbose=verbose)
     args = dict(div=bool(div), batch_norm=bool(batch_norm), bias=bool(bias), final_activation=final_activation,

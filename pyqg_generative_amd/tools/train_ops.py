@@ -1,9 +1,10 @@
-"""The device operations of a CNN training step: ctypes wrappers over include/qgx_conv_train.h and include/qgx_head_train.h
-and the two torch.autograd.Functions that put them behind autograd.
+"""The device operations of a CNN training step: ctypes wrappers over include/qgx_conv_train.h, include/qgx_head_train.h and
+include/qgx_flux_train.h and the torch.autograd.Functions that put them behind autograd.
 
 The convolutions — more than 95 % of a step's FLOPs — are the kernels of csrc/conv_train.hip behind ``circular_conv2d``.  The
 two ends of a step — the gather of a batch from the resident set into the engine layout, and the loss head (MSE, or softplus
 then MSE) with its gradient — are the kernels of csrc/train_head.hip behind ``gather_batch``, ``head_loss`` and ``head_apply``.
+A flux-form net (div=True) ends in ``flux_divergence``: the generators' spectral divergence and its adjoint, csrc/fluxdiv_train.hip.
 Every tensor is checked here, once per layout (``_engine``, ``_planar``, ``_rows``), before a pointer reaches the library.
 The nets and loops that use these operations are in tools/train_CNN.py.
 """
@@ -158,6 +159,39 @@ def to_engine_layout(x):
     out = torch.zeros((B, N, N, c8(Cn)), dtype=torch.float32, device=x.device)
     out[..., :Cn] = x.permute(0, 2, 3, 1)
     return out
+
+
+FLUX_LAUNCHES = {'forward': 0, 'backward': 0}                             # counted per call of the Function (tests, timing)
+
+
+def _flux_call(call, t, name, channels):
+    """one call of include/qgx_flux_train.h in the engine layout: (B, N, N, 8) -> (B, N, N, 8), no workspace"""
+    t = _aligned(_engine(t, name, channels))
+    B, N = int(t.shape[0]), int(t.shape[1])
+    with torch.cuda.device(t.device):
+        out = torch.empty((B, N, N, 8), dtype=torch.float32, device=t.device)
+        check(call(t.data_ptr(), out.data_ptr(), B, N, _lib.FLUX_ENGINE, _lib.current_stream_ptr()))
+    return out
+
+
+class _FluxDivergence(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, F):
+        FLUX_LAUNCHES['forward'] += 1
+        return _flux_call(lib.qgx_fluxdiv_forward, F, 'F', 4)
+
+    @staticmethod
+    def backward(ctx, dy):
+        FLUX_LAUNCHES['backward'] += 1
+        return _flux_call(lib.qgx_fluxdiv_backward, dy, 'dy', 2)
+
+
+def flux_divergence(F):
+    """10000 * divergence(F) of a flux-form net (AndrewCNN(div=True)) on the engine layout, differentiable: F (B, N, N, 8) with
+    channels [fx1, fx2, fy1, fy2, 0, 0, 0, 0] -> (B, N, N, 8) with channels [y1, y2, 0, ...].  The forward is the kernel body
+    the generators run at inference, the backward its adjoint (csrc/fluxdiv_core.hpp); the operator is linear, so nothing is
+    saved.  One HIP call each way."""
+    return _FluxDivergence.apply(F)
 
 
 HEADS = {'mse': _lib.HEAD_MSE, 'softplus_mse': _lib.HEAD_SOFTPLUS_MSE}     # the modes of include/qgx_head_train.h

@@ -543,6 +543,11 @@ int qgx_histogram(const void *x_dev, int is_double, int64_t R, int64_t T, int64_
  * the engine layout, and its adjoint.  Declared and documented in qgx_flux_train.h, which this header includes. */
 #include "qgx_flux_train.h"
 
+/* The latent step of a conditional VAE's training (CVAERegression), between the encoder's last convolution and the decoder's
+ * first: the reparameterised sample, the KL divergence with its variance diagnostics, and their gradient.  Declared and
+ * documented in qgx_latent_train.h, which this header includes. */
+#include "qgx_latent_train.h"
+
 /* ---- latent noise ------------------------------------------------------------
  * z <- a z + b xi with xi ~ N(0,1) from Philox4x32-10 (stochastic_pyqg.py:43-49).  z: (B, n_per_member) float or double,
  * n_per_member a positive multiple of 4; a == 0 overwrites z (its previous contents are not read).  Counter of the four

@@ -215,6 +215,16 @@ FLUX_TRAIN_SYMBOLS = [
     ('qgx_fluxdiv_backward', C.c_int, _FLUX),
 ]
 
+# what include/qgx_latent_train.h declares: the latent step of a conditional VAE's training (tools/train_ops.py)
+_DRAW = [C.c_uint64, C.c_uint64]                                                              # seed, step
+LATENT_TRAIN_SYMBOLS = [
+    ('qgx_latent_workspace', C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
+    ('qgx_latent_forward', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + _DRAW + [C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_int, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ('qgx_latent_backward', C.c_int, [C.c_void_p, C.c_void_p] + _DRAW + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                      C.c_void_p]),
+]
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -228,7 +238,7 @@ def _load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, res, args in (SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS + TRAIN_SYMBOLS + CONV_TRAIN_SYMBOLS + HEAD_TRAIN_SYMBOLS
-                            + FLUX_TRAIN_SYMBOLS):
+                            + FLUX_TRAIN_SYMBOLS + LATENT_TRAIN_SYMBOLS):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -1,12 +1,14 @@
-"""The device operations of a CNN training step: ctypes wrappers over include/qgx_conv_train.h, include/qgx_head_train.h and
-include/qgx_flux_train.h and the torch.autograd.Functions that put them behind autograd.
+"""The device operations of a CNN training step: ctypes wrappers over include/qgx_conv_train.h, include/qgx_head_train.h,
+include/qgx_flux_train.h and include/qgx_latent_train.h and the torch.autograd.Functions that put them behind autograd.
 
 The convolutions — more than 95 % of a step's FLOPs — are the kernels of csrc/conv_train.hip behind ``circular_conv2d``.  The
 two ends of a step — the gather of a batch from the resident set into the engine layout, and the loss head (MSE, or softplus
 then MSE) with its gradient — are the kernels of csrc/train_head.hip behind ``gather_batch``, ``head_loss`` and ``head_apply``.
 A flux-form net (div=True) ends in ``flux_divergence``: the generators' spectral divergence and its adjoint, csrc/fluxdiv_train.hip.
+A conditional VAE has ``latent_sample`` between its encoder and its decoder: the reparameterised sample, the KL divergence and
+the variance diagnostics in one call each way, csrc/latent_train.hip; ``latent_prior`` is the same forward without an encoder.
 Every tensor is checked here, once per layout (``_engine``, ``_planar``, ``_rows``), before a pointer reaches the library.
-The nets and loops that use these operations are in tools/train_CNN.py.
+The nets and loops that use these operations are in tools/train_CNN.py and tools/train_CVAE.py.
 """
 import ctypes as C
 
@@ -27,7 +29,8 @@ _WORK = {}
 
 
 def workspace(kind, size_call, shape, device):
-    """the workspace of one kind ('conv': one size for the three calls; 'head': the loss partials) and shape, of
+    """the workspace of one kind ('conv': one size for the three calls; 'head': the loss partials; 'latent': the partial sums
+    of the KL divergence and the variances) and shape, of
     size_call(*shape, &bytes) bytes, cached per device, stream and shape: calls on one stream run in order, so they may share
     it; calls on different streams may not"""
     key = (kind, device.index, torch.cuda.current_stream(device).cuda_stream) + shape
@@ -299,3 +302,102 @@ def head_apply(y_engine, channels, mode, T=None, idx=None, out=None):
                                  _lib.current_stream_ptr()))
     HEAD_LAUNCHES['apply'] += 1
     return out
+
+
+LATENT_LAUNCHES = {'forward': 0, 'backward': 0, 'prior': 0}               # counted per call of a wrapper (tests, timing)
+_U64 = (1 << 64) - 1
+
+
+def _latent_args(enc, X, idx, eps, seed, step):
+    """(enc, X, idx, eps, B, N, n, seed, step) of a call of include/qgx_latent_train.h: enc (B, N, N, 8) in the engine layout
+    or None, rows idx of the planar PV set X (n, 2, N, N), eps planar (B, 2, N, N) or None"""
+    X = _planar(X, 'X')
+    idx = _rows(idx, X)
+    N, n = int(X.shape[-1]), len(X)
+    B = n if idx is None else len(idx)
+    if enc is not None:
+        enc = _aligned(_engine(enc, 'enc', 4))
+        B = int(enc.shape[0]) if idx is None else B
+    if int(X.shape[1]) != 2 or (enc is not None and (enc.device != X.device or tuple(enc.shape) != (B, N, N, 8))) or n < B:
+        raise ValueError(f'enc {None if enc is None else tuple(enc.shape)}, X {tuple(X.shape)}, idx '
+                         f'{None if idx is None else tuple(idx.shape)} do not fit: X has 2 channels, enc is (B, N, N, 8)')
+    if eps is not None:
+        eps = _planar(eps, 'eps')
+        if eps.device != X.device or tuple(eps.shape) != (B, 2, N, N):
+            raise ValueError(f'eps {tuple(eps.shape)}: expected {(B, 2, N, N)} on {X.device}')
+    seed, step = int(seed), int(step)
+    if not (0 <= seed <= _U64 and 0 <= step <= _U64):
+        raise ValueError(f'seed = {seed}, step = {step}: unsigned 64-bit numbers')
+    return enc, X, idx, eps, B, N, n, seed, step
+
+
+def latent_forward(enc, X, idx, seed, step, eps=None):
+    """qgx_latent_forward -> (dec_in (B, N, N, 8), stats (3) float64 on the device: loss_KL, var_latent, var_aggr; None
+    without enc).  No autograd: see latent_sample"""
+    enc, X, idx, eps, B, N, n, seed, step = _latent_args(enc, X, idx, eps, seed, step)
+    with torch.cuda.device(X.device):
+        dec_in = torch.empty((B, N, N, 8), dtype=torch.float32, device=X.device)
+        stats = ws = None
+        if enc is not None:
+            ws = workspace('latent', lib.qgx_latent_workspace, (B, N), X.device)
+            stats = torch.empty((3,), dtype=torch.float64, device=X.device)
+        check(lib.qgx_latent_forward(_ptr(enc), X.data_ptr(), _ptr(idx), _ptr(eps), seed, step, dec_in.data_ptr(), _ptr(stats), B, N, n,
+                                     _ptr(ws), 0 if ws is None else ws.numel(), _lib.current_stream_ptr()))
+    LATENT_LAUNCHES['prior' if enc is None else 'forward'] += 1
+    return dec_in, stats
+
+
+def latent_backward(enc, eps, seed, step, d_dec_in, gout_kl):
+    """qgx_latent_backward -> d_enc (B, N, N, 8); gout_kl is one number on the device, read there"""
+    enc = _aligned(_engine(enc, 'enc', 4))
+    B, N = int(enc.shape[0]), int(enc.shape[1])
+    d_dec_in = _aligned(_engine(d_dec_in, 'd_dec_in', 4))
+    if d_dec_in.shape != enc.shape or d_dec_in.device != enc.device:
+        raise ValueError(f'd_dec_in {tuple(d_dec_in.shape)} and enc {tuple(enc.shape)} differ')
+    if eps is not None:
+        eps = _planar(eps, 'eps')
+        if eps.device != enc.device or tuple(eps.shape) != (B, 2, N, N):
+            raise ValueError(f'eps {tuple(eps.shape)}: expected {(B, 2, N, N)} on {enc.device}')
+    if not (torch.is_tensor(gout_kl) and gout_kl.numel() == 1 and gout_kl.device == enc.device):
+        raise ValueError('gout_kl: one number on the device of enc')
+    gout_kl = _aligned(gout_kl.detach().to(torch.float64).contiguous())
+    with torch.cuda.device(enc.device):
+        d_enc = torch.empty_like(enc)
+        check(lib.qgx_latent_backward(enc.data_ptr(), _ptr(eps), int(seed), int(step), d_dec_in.data_ptr(), gout_kl.data_ptr(),
+                                      d_enc.data_ptr(), B, N, _lib.current_stream_ptr()))
+    LATENT_LAUNCHES['backward'] += 1
+    return d_enc
+
+
+class _LatentSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, enc, X, idx, seed, step, eps):
+        dec_in, stats = latent_forward(enc, X, idx, seed, step, eps)
+        ctx.save_for_backward(enc, eps)
+        ctx.draw = (int(seed), int(step))
+        loss_KL, var_latent, var_aggr = stats[0], stats[1], stats[2]
+        ctx.mark_non_differentiable(var_latent, var_aggr)
+        return dec_in, loss_KL, var_latent, var_aggr
+
+    @staticmethod
+    def backward(ctx, d_dec_in, g_kl, _g_latent, _g_aggr):
+        enc, eps = ctx.saved_tensors          # an output that took no part in the loss comes with a zero gradient
+        return latent_backward(enc, eps, *ctx.draw, d_dec_in.contiguous(), g_kl), None, None, None, None, None
+
+
+def latent_sample(enc, X, idx, seed, step, eps=None):
+    """The latent step of a conditional VAE between its encoder and its decoder, differentiable in enc.  enc (B, N, N, 8) is the
+    encoder's last activation in the engine layout, channels [mu1, mu2, logvar1, logvar2]; X the planar PV set (n, 2, N, N) on
+    the device and idx its B rows (None: rows 0 ... B - 1).  Returns (dec_in, loss_KL, var_latent, var_aggr): dec_in (B, N, N, 8)
+    with channels [x1, x2, z1, z2], z = eps exp(logvar / 2) + mu, and three 0-dim float64 device tensors, the KL divergence to
+    the standard normal summed over pixels and channels and averaged over the batch, the mean of exp(logvar), and the latter plus
+    the unbiased variance of mu (the two are diagnostics: no gradient).  eps planar (B, 2, N, N), or None: the standard
+    normals of the Philox stream (seed, member b, step), drawn in the forward and AGAIN in the backward: nothing but enc is
+    kept (a given eps is).  One HIP call forward (two launches: the kernel and the finish of its sums), one backward."""
+    return _LatentSample.apply(enc, X, idx, seed, step, eps)
+
+
+def latent_prior(X, idx, seed, step):
+    """dec_in (B, N, N, 8) = [x1, x2, z1, z2] with z drawn from the prior: the standard normals of the Philox stream (seed,
+    member b, step); what a decoder predicts from.  Not differentiable."""
+    return latent_forward(None, X, idx, seed, step)[0]

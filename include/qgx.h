@@ -548,6 +548,12 @@ int qgx_histogram(const void *x_dev, int is_double, int64_t R, int64_t T, int64_
  * documented in qgx_latent_train.h, which this header includes. */
 #include "qgx_latent_train.h"
 
+/* The layer of CGANRegression's discriminator (DCGAN_discriminator): Conv2d(cin, cout, 4, stride=2, padding=1, bias=False)
+ * with zero padding, its data gradient and its weight gradient as stateless operations; each one's derivative is another of
+ * the three, so tools/train_ops.py builds a twice-differentiable layer of them for the gradient penalty.  Declared and
+ * documented in qgx_dconv_train.h, which this header includes. */
+#include "qgx_dconv_train.h"
+
 /* ---- latent noise ------------------------------------------------------------
  * z <- a z + b xi with xi ~ N(0,1) from Philox4x32-10 (stochastic_pyqg.py:43-49).  z: (B, n_per_member) float or double,
  * n_per_member a positive multiple of 4; a == 0 overwrites z (its previous contents are not read).  Counter of the four

@@ -225,6 +225,15 @@ LATENT_TRAIN_SYMBOLS = [
                                       C.c_void_p]),
 ]
 
+# what include/qgx_dconv_train.h declares: the discriminator's stride-2 convolution and its two gradients (tools/train_ops.py)
+_DCONV = [C.c_int64, C.c_int, C.c_int, C.c_int]                                               # B, N, cin, cout
+DCONV_TRAIN_SYMBOLS = [
+    ('qgx_dconv2d_workspace', C.c_int, _DCONV + [C.POINTER(C.c_size_t)]),
+    ('qgx_dconv2d_forward', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + _DCONV + _CONV_WORK),
+    ('qgx_dconv2d_backward_data', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + _DCONV + _CONV_WORK),
+    ('qgx_dconv2d_backward_weight', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + _DCONV + _CONV_WORK),
+]
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -238,7 +247,7 @@ def _load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, res, args in (SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS + TRAIN_SYMBOLS + CONV_TRAIN_SYMBOLS + HEAD_TRAIN_SYMBOLS
-                            + FLUX_TRAIN_SYMBOLS + LATENT_TRAIN_SYMBOLS):
+                            + FLUX_TRAIN_SYMBOLS + LATENT_TRAIN_SYMBOLS + DCONV_TRAIN_SYMBOLS):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -1,5 +1,6 @@
 """The device operations of a CNN training step: ctypes wrappers over include/qgx_conv_train.h, include/qgx_head_train.h,
-include/qgx_flux_train.h and include/qgx_latent_train.h and the torch.autograd.Functions that put them behind autograd.
+include/qgx_flux_train.h, include/qgx_latent_train.h and include/qgx_dconv_train.h and the torch.autograd.Functions that put them
+behind autograd.
 
 The convolutions — more than 95 % of a step's FLOPs — are the kernels of csrc/conv_train.hip behind ``circular_conv2d``.  The
 two ends of a step — the gather of a batch from the resident set into the engine layout, and the loss head (MSE, or softplus
@@ -7,9 +8,12 @@ then MSE) with its gradient — are the kernels of csrc/train_head.hip behind ``
 A flux-form net (div=True) ends in ``flux_divergence``: the generators' spectral divergence and its adjoint, csrc/fluxdiv_train.hip.
 A conditional VAE has ``latent_sample`` between its encoder and its decoder: the reparameterised sample, the KL divergence and
 the variance diagnostics in one call each way, csrc/latent_train.hip; ``latent_prior`` is the same forward without an encoder.
+A GAN's discriminator is made of ``strided_conv2d``, csrc/dconv_train.hip: three Functions whose backwards are each other, so that
+the gradient penalty's second derivative runs on the same three kernels.
 Every tensor is checked here, once per layout (``_engine``, ``_planar``, ``_rows``), before a pointer reaches the library.
-The nets and loops that use these operations are in tools/train_CNN.py and tools/train_CVAE.py.
+The nets and loops that use these operations are in tools/train_CNN.py, tools/train_CVAE.py and tools/train_CGAN.py.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -29,8 +33,8 @@ _WORK = {}
 
 
 def workspace(kind, size_call, shape, device):
-    """the workspace of one kind ('conv': one size for the three calls; 'head': the loss partials; 'latent': the partial sums
-    of the KL divergence and the variances) and shape, of
+    """the workspace of one kind ('conv', 'dconv': one size for the three calls; 'head': the loss partials; 'latent': the partial
+    sums of the KL divergence and the variances) and shape, of
     size_call(*shape, &bytes) bytes, cached per device, stream and shape: calls on one stream run in order, so they may share
     it; calls on different streams may not"""
     key = (kind, device.index, torch.cuda.current_stream(device).cuda_stream) + shape
@@ -154,6 +158,127 @@ def circular_conv2d(x, w, b=None):
     the device with zero pad channels, w (cout, cin, k, k), b (cout) or None -> (B, N, N, c8(cout)).  The data gradient is
     computed only if x requires it (a net's first layer does not)."""
     return _CircularConv2d.apply(x, w, b)
+
+
+def _dconv_weight(w):
+    w, cout, cin, k = _weight(w)
+    if k != 4:
+        raise ValueError(f'weight: (cout, cin, 4, 4), not {tuple(w.shape)}')
+    return _aligned(w), cout, cin
+
+
+def _dconv_call(call, a, b, out, B, N, cin, cout):
+    """one call of include/qgx_dconv_train.h: two inputs, one output, the workspace of the shape"""
+    with torch.cuda.device(out.device):
+        ws = workspace('dconv', lib.qgx_dconv2d_workspace, (B, N, cin, cout), out.device)
+        check(call(a.data_ptr(), b.data_ptr(), out.data_ptr(), B, N, cin, cout, ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()))
+    return out
+
+
+def dconv2d_forward(x, w):
+    """y (B, N/2, N/2, c8(cout)) = conv(x (B, N, N, c8(cin)), w (cout, cin, 4, 4); stride 2, zero padding 1)"""
+    w, cout, cin = _dconv_weight(w)
+    x = _aligned(_engine(x, 'x', cin))
+    B, N = int(x.shape[0]), int(x.shape[1])
+    y = torch.empty((B, N // 2, N // 2, c8(cout)), dtype=torch.float32, device=x.device)
+    return _dconv_call(lib.qgx_dconv2d_forward, x, w, y, B, N, cin, cout)
+
+
+def dconv2d_backward_data(dy, w):
+    """dx (B, N, N, c8(cin)) of dy (B, N/2, N/2, c8(cout))"""
+    w, cout, cin = _dconv_weight(w)
+    dy = _aligned(_engine(dy, 'dy', cout))
+    B, N = int(dy.shape[0]), 2 * int(dy.shape[1])
+    dx = torch.empty((B, N, N, c8(cin)), dtype=torch.float32, device=dy.device)
+    return _dconv_call(lib.qgx_dconv2d_backward_data, dy, w, dx, B, N, cin, cout)
+
+
+def dconv2d_backward_weight(x, dy, cin, cout):
+    """dw (cout, cin, 4, 4) of x (B, N, N, c8(cin)) and dy (B, N/2, N/2, c8(cout))"""
+    x, dy = _aligned(_engine(x, 'x', cin)), _aligned(_engine(dy, 'dy', cout))
+    B, N = int(x.shape[0]), int(x.shape[1])
+    if dy.shape[0] != B or 2 * dy.shape[1] != N or dy.device != x.device:
+        raise ValueError(f'x {tuple(x.shape)} and dy {tuple(dy.shape)} differ in batch, grid or device: dy has half of x\'s grid')
+    dw = torch.empty((int(cout), int(cin), 4, 4), dtype=torch.float32, device=x.device)
+    return _dconv_call(lib.qgx_dconv2d_backward_weight, x, dy, dw, B, N, int(cin), int(cout))
+
+
+DCONV_LAUNCHES = {'forward': 0, 'backward_data': 0, 'backward_weight': 0}  # counted per call of a Function (tests, timing)
+_DATA_ONLY = [False]      # a module-level flag, not a thread-local one: autograd runs a backward on a thread of its own
+
+
+@contextlib.contextmanager
+def data_gradient_only():
+    """Inside the block the backward of strided_conv2d's forward computes the data gradient alone.  A Function's
+    needs_input_grad says which inputs require a gradient, not which of them the caller of autograd.grad asked for; a
+    gradient penalty asks for the input's alone, and a generator step uses the discriminator's alone, so both would pay a
+    weight gradient per layer for nothing.  The weights then receive None, which autograd reads as zero."""
+    old, _DATA_ONLY[0] = _DATA_ONLY[0], True
+    try:
+        yield
+    finally:
+        _DATA_ONLY[0] = old
+
+
+# The convolution is bilinear in (x, w), so the derivative of each of the three operations with respect to either operand is
+# another of the three.  Each Function's backward calls the other two through their .apply: under create_graph=True the graph
+# of a backward exists, and the layer is differentiable as often as one likes.
+class _DconvForward(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w):
+        ctx.save_for_backward(x, w)
+        DCONV_LAUNCHES['forward'] += 1
+        return dconv2d_forward(x, w)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = _DconvBackwardData.apply(dy, w) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1] and not _DATA_ONLY[0]:
+            dw = _DconvBackwardWeight.apply(x, dy, int(w.shape[1]), int(w.shape[0]))
+        return dx, dw
+
+
+class _DconvBackwardData(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dy, w):
+        ctx.save_for_backward(dy, w)
+        DCONV_LAUNCHES['backward_data'] += 1
+        return dconv2d_backward_data(dy, w)
+
+    @staticmethod
+    def backward(ctx, g):                    # <g, dx(dy, w)> = <forward(g, w), dy> = <backward_weight(g, dy), w>
+        dy, w = ctx.saved_tensors
+        g = g.contiguous()
+        d_dy = _DconvForward.apply(g, w) if ctx.needs_input_grad[0] else None
+        d_w = _DconvBackwardWeight.apply(g, dy, int(w.shape[1]), int(w.shape[0])) if ctx.needs_input_grad[1] else None
+        return d_dy, d_w
+
+
+class _DconvBackwardWeight(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, dy, cin, cout):
+        ctx.save_for_backward(x, dy)
+        DCONV_LAUNCHES['backward_weight'] += 1
+        return dconv2d_backward_weight(x, dy, cin, cout)
+
+    @staticmethod
+    def backward(ctx, g):                    # <g, dw(x, dy)> = <backward_data(dy, g), x> = <forward(x, g), dy>
+        x, dy = ctx.saved_tensors
+        g = g.contiguous()
+        d_x = _DconvBackwardData.apply(dy, g) if ctx.needs_input_grad[0] else None
+        d_dy = _DconvForward.apply(x, g) if ctx.needs_input_grad[1] else None
+        return d_x, d_dy, None, None
+
+
+def strided_conv2d(x, w):
+    """Conv2d(cin, cout, 4, stride=2, padding=1, bias=False) — zero padding — on the engine layout, differentiable TWICE (and
+    more): x (B, N, N, c8(cin)) float32 on the device, w (cout, cin, 4, 4) -> (B, N/2, N/2, c8(cout)).  The layer of
+    CGANRegression's discriminator, whose gradient penalty differentiates a gradient.  A gradient is computed only where it
+    is asked for."""
+    return _DconvForward.apply(x, w)
 
 
 def to_engine_layout(x):

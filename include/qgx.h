@@ -554,6 +554,12 @@ int qgx_histogram(const void *x_dev, int is_double, int64_t R, int64_t T, int64_
  * documented in qgx_dconv_train.h, which this header includes. */
 #include "qgx_dconv_train.h"
 
+/* The layer of the DeepInversion U-Net generator's training (CGANRegression(generator='DeepInversion')): the circular 3 x 3 or
+ * 1 x 1 convolution on any grid 2 ... 128 with up to 512 -> 1024 channels, its data gradient and its weight gradient as
+ * stateless operations (tools/train_ops.py: unet_conv2d).  Declared and documented in qgx_uconv_train.h, which this header
+ * includes. */
+#include "qgx_uconv_train.h"
+
 /* ---- latent noise ------------------------------------------------------------
  * z <- a z + b xi with xi ~ N(0,1) from Philox4x32-10 (stochastic_pyqg.py:43-49).  z: (B, n_per_member) float or double,
  * n_per_member a positive multiple of 4; a == 0 overwrites z (its previous contents are not read).  Counter of the four

@@ -234,6 +234,14 @@ DCONV_TRAIN_SYMBOLS = [
     ('qgx_dconv2d_backward_weight', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + _DCONV + _CONV_WORK),
 ]
 
+# what include/qgx_uconv_train.h declares: the U-Net's circular 3 x 3 / 1 x 1 convolution and its two gradients (tools/train_ops.py)
+UCONV_TRAIN_SYMBOLS = [
+    ('qgx_uconv2d_workspace', C.c_int, _CONV + [C.POINTER(C.c_size_t)]),
+    ('qgx_uconv2d_forward', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + _CONV + _CONV_WORK),
+    ('qgx_uconv2d_backward_data', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + _CONV + _CONV_WORK),
+    ('qgx_uconv2d_backward_weight', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + _CONV + _CONV_WORK),
+]
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -247,7 +255,7 @@ def _load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, res, args in (SYMBOLS + ARCH_SYMBOLS + STATS_SYMBOLS + TRAIN_SYMBOLS + CONV_TRAIN_SYMBOLS + HEAD_TRAIN_SYMBOLS
-                            + FLUX_TRAIN_SYMBOLS + LATENT_TRAIN_SYMBOLS + DCONV_TRAIN_SYMBOLS):
+                            + FLUX_TRAIN_SYMBOLS + LATENT_TRAIN_SYMBOLS + DCONV_TRAIN_SYMBOLS + UCONV_TRAIN_SYMBOLS):
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -8,11 +8,14 @@ csrc/dconv_train.hip behind three autograd.Functions whose backwards are each ot
 through D runs on the same three kernels.  The data, the epoch's order and its interpolation weights are resident on the device,
 the latent noise is drawn there from the Philox stream (two steps per batch), and the four losses are accumulated there and
 read once per epoch.  ``fit_cgan`` writes the reference's model folder (G.pt, D.pt, [net_mean.pt], x_scale.json, y_scale.json,
-model_args.json, stats.nc) and returns ``CGANRegression(folder=...)`` read back from those files.
+model_args.json, stats.nc) and returns ``CGANRegression(folder=...)`` read back from those files.  ``fit_cgan_unet`` is the same
+fit of ``CGANRegression(generator='DeepInversion')``: G is the U-Net of tools/train_UNet.py on ``train_ops.unet_conv2d``
+(csrc/uconv_train.hip); the loop, D and the folder are the same.
 
 Command line:
     python -m pyqg_generative_amd.tools.train_CGAN --train 'GLOB' --validate 'GLOB' [--test 'GLOB'] \\
         --model_args "{'regression': 'full_loss', 'folder': 'model'}" --fit_args "{'num_epochs': 200}"
+    --model CGANRegression-Unet (the reference's sweep name) trains the U-Net generator; the default is CGANRegression.
 """
 import os
 from time import time
@@ -25,6 +28,7 @@ from .cnn_tools import ChannelwiseScaler
 from .train_common import check_fit_args, command_line, cuda_device, print_start, stacked
 from .train_CNN import FluxFormCNN, TrainableAndrewCNN, _write_folder, prepare_PV_data, train
 from .train_CVAE import _forward_all
+from .train_UNet import UNET_GRIDS, TrainableUNet
 from .train_ops import GRIDS, data_gradient_only, gather_batch, head_apply, latent_prior, strided_conv2d
 
 LAMBDA_DRIFT = 1e-3                                                               # cgan_regression.py:18-19
@@ -115,18 +119,27 @@ class TrainableCGAN(nn.Module):
                  generator='Andrew', ndf=64):
         super().__init__()
         if generator == 'DeepInversion':
-            raise NotImplementedError("generator='DeepInversion': the U-Net generator has no backward on the device; only "
-                                      "generator='Andrew' is trained here")
+            raise NotImplementedError("generator='DeepInversion': the U-Net generator is trained by TrainableUNetCGAN and "
+                                      "fit_cgan_unet; this class and fit_cgan train generator='Andrew'")
         if generator != 'Andrew':
             raise ValueError(f'generator={generator!r}: not implemented')
+        self._build(regression, nx, div, hidden_channels, seed, generator, ndf)
+
+    def _build(self, regression, nx, div, hidden_channels, seed, generator, ndf):
         if regression not in REGRESSIONS:
             raise ValueError(f'regression={regression!r}: one of {REGRESSIONS}')
         self.regression, self.nx, self.div, self.seed, self.generator = regression, int(nx), bool(div), int(seed), generator
         if not 0 <= self.seed < _U64 - 1:
             raise ValueError(f'seed = {seed}: 0 ... 2^64 - 3')
         net = FluxFormCNN if self.div else TrainableAndrewCNN
-        self.G = _seeded_init(net(4, 2, hidden_channels=hidden_channels, seed=self.seed), self.seed)
-        self.hidden_channels = list(self.G.hidden_channels)
+        if generator == 'DeepInversion':
+            if self.nx not in UNET_GRIDS:
+                raise ValueError(f'nx = {nx}: the U-Net generator runs on one of {UNET_GRIDS}')
+            self.G = TrainableUNet(self.seed)
+            self.hidden_channels = list(hidden_channels)
+        else:
+            self.G = _seeded_init(net(4, 2, hidden_channels=hidden_channels, seed=self.seed), self.seed)
+            self.hidden_channels = list(self.G.hidden_channels)
         self.D = TrainableDiscriminator(self.nx, ndf, self.seed + 1)
         if regression != 'None':
             self.net_mean = net(2, 2, seed=self.seed + 2)
@@ -156,6 +169,18 @@ class TrainableCGAN(nn.Module):
     def generator_loss(self, xe, f1, f2):
         """G_loss = -mean D([x, yfake1, yfake2]) (:310), differentiable in the fakes"""
         return -self.D.forward_engine(critic_input(xe, f1, f2)).mean()
+
+
+class TrainableUNetCGAN(TrainableCGAN):
+    """The nets of CGANRegression(regression, nx, generator='DeepInversion', div=, hidden_channels=): TrainableCGAN with
+    G = TrainableUNet (tools/train_UNet.py: DeepInversionGenerator(4, 2) on ``unet_conv2d``, weights_init under seed — which in
+    the reference reaches the ConvTranspose2d weights too).  nx is one of the grids the U-Net's device inference admits (32,
+    48, 64, 96, 128); `div` reaches net_mean alone, as in the reference (the U-Net has no flux form); `hidden_channels` is
+    recorded for model_args.json and not used.  D, net_mean, the losses and train_CGAN are TrainableCGAN's."""
+
+    def __init__(self, regression='None', nx=64, div=False, hidden_channels=(128, 64, 32, 32, 32, 32, 32), seed=0, ndf=64):
+        nn.Module.__init__(self)
+        self._build(regression, nx, div, hidden_channels, seed, 'DeepInversion', ndf)
 
 
 def run_epoch(batches, critic_step, generator_step, acc):
@@ -368,28 +393,17 @@ def write_cgan_folder(folder, net, x_scale, y_scale, optim_loss, log_train, log_
     return epoch_opt
 
 
-def fit_cgan(ds_train, ds_test, *, regression='None', nx=64, generator='Andrew', div=False,
-             hidden_channels=[128, 64, 32, 32, 32, 32, 32], folder='model', num_epochs=200, num_epochs_regression=50, batch_size=64,
-             learning_rate=2e-4, nruns=5, seed=0, device=0, orders=None, mixes=None, runs=None, verbose=True, ndf=64):
-    """CGANRegression(regression, nx, generator, folder, div, hidden_channels).fit(ds_train, ds_test, num_epochs,
-    num_epochs_regression, batch_size, learning_rate, nruns) on the device (cgan_regression.py:68-107), then save_model;
-    returns CGANRegression(folder=folder) read back from the files, with the trained nets attached as trained_G, trained_D and
-    (with a regression) trained_net_mean.
-
-    With a regression, net_mean is read from `folder` if net_mean.pt is there — the folder's scales must then equal those of
-    ds_train bit for bit — and is otherwise trained with MSE for num_epochs_regression epochs at learning rate 0.001, as the
-    reference does.  G and D are initialised by weights_init under seed and seed + 1, net_mean by torch's defaults under
-    seed + 2; the epochs' shuffles, interpolation weights and coins and the choice of the nruns scored runs come from numpy's
-    global stream unless orders(epoch, n), mixes(epoch, steps, batch_size) and runs(R, nruns) give them."""
+def _fit(who, net, ds_train, ds_test, regression, folder, num_epochs, num_epochs_regression, batch_size, learning_rate, nruns,
+         device, orders, mixes, runs, verbose):
+    """the body of fit_cgan and fit_cgan_unet (`who`, for messages) for the nets `net` (a TrainableCGAN): net_mean read or
+    trained, train_CGAN, the folder, and the model read back from it"""
     from ..models.cgan_regression import CGANRegression
     num_epochs, num_epochs_regression, batch_size = int(num_epochs), int(num_epochs_regression), int(batch_size)
-    check_fit_args('fit_cgan', num_epochs, batch_size, learning_rate)
-    net = TrainableCGAN(regression, nx, div, hidden_channels, seed, generator=generator, ndf=ndf)
     if regression != 'None':
-        check_fit_args('fit_cgan', num_epochs_regression, batch_size, 0.001)
-    X_train, Y_train, X_test, Y_test, net.x_scale, net.y_scale = prepare_PV_data(ds_train, ds_test, 'fit_cgan')
+        check_fit_args(who, num_epochs_regression, batch_size, 0.001)
+    X_train, Y_train, X_test, Y_test, net.x_scale, net.y_scale = prepare_PV_data(ds_train, ds_test, who)
     if X_train.shape[-1] != net.nx:
-        raise ValueError(f'fit_cgan: the datasets are on a {X_train.shape[-1]} x {X_train.shape[-1]} grid, nx = {net.nx}')
+        raise ValueError(f'{who}: the datasets are on a {X_train.shape[-1]} x {X_train.shape[-1]} grid, nx = {net.nx}')
     dev = cuda_device(device)
     X_train, Y_train, X_test, Y_test = (torch.as_tensor(a).to(dev) for a in (X_train, Y_train, X_test, Y_test))
     if regression != 'None':
@@ -397,7 +411,7 @@ def fit_cgan(ds_train, ds_test, *, regression='None', nx=64, generator='Andrew',
             for name, have in (('x_scale.json', net.x_scale), ('y_scale.json', net.y_scale)):
                 old = ChannelwiseScaler().read(name, folder)
                 if not (np.array_equal(old.std.reshape(-1), have.std.reshape(-1)) and np.array_equal(old.mean.reshape(-1), have.mean.reshape(-1))):
-                    raise ValueError(f'fit_cgan: {os.path.join(folder, name)} is not the scale of ds_train: net_mean.pt of this '
+                    raise ValueError(f'{who}: {os.path.join(folder, name)} is not the scale of ds_train: net_mean.pt of this '
                                      'folder was trained on other data')
             if verbose:
                 print('Net mean is loaded instead of training')
@@ -411,7 +425,7 @@ def fit_cgan(ds_train, ds_test, *, regression='None', nx=64, generator='Andrew',
     logs = train_CGAN(net, X_train, Y_train, num_epochs, batch_size, learning_rate, ds_train=ds_train, ds_test=ds_test, nruns=nruns,
                       device=dev, orders=orders, mixes=mixes, runs=runs, verbose=verbose)
     write_cgan_folder(folder, net, net.x_scale, net.y_scale, *logs, verbose=verbose)
-    model = CGANRegression(regression=regression, nx=net.nx, generator='Andrew', folder=folder, div=net.div,
+    model = CGANRegression(regression=regression, nx=net.nx, generator=net.generator, folder=folder, div=net.div,
                            hidden_channels=list(net.hidden_channels), device=device)
     model.trained_G, model.trained_D, model.trained = net.G, net.D, net
     if regression != 'None':
@@ -419,8 +433,42 @@ def fit_cgan(ds_train, ds_test, *, regression='None', nx=64, generator='Andrew',
     return model
 
 
+def fit_cgan(ds_train, ds_test, *, regression='None', nx=64, generator='Andrew', div=False,
+             hidden_channels=[128, 64, 32, 32, 32, 32, 32], folder='model', num_epochs=200, num_epochs_regression=50, batch_size=64,
+             learning_rate=2e-4, nruns=5, seed=0, device=0, orders=None, mixes=None, runs=None, verbose=True, ndf=64):
+    """CGANRegression(regression, nx, generator, folder, div, hidden_channels).fit(ds_train, ds_test, num_epochs,
+    num_epochs_regression, batch_size, learning_rate, nruns) on the device (cgan_regression.py:68-107), then save_model;
+    returns CGANRegression(folder=folder) read back from the files, with the trained nets attached as trained_G, trained_D and
+    (with a regression) trained_net_mean.
+
+    With a regression, net_mean is read from `folder` if net_mean.pt is there — the folder's scales must then equal those of
+    ds_train bit for bit — and is otherwise trained with MSE for num_epochs_regression epochs at learning rate 0.001, as the
+    reference does.  G and D are initialised by weights_init under seed and seed + 1, net_mean by torch's defaults under
+    seed + 2; the epochs' shuffles, interpolation weights and coins and the choice of the nruns scored runs come from numpy's
+    global stream unless orders(epoch, n), mixes(epoch, steps, batch_size) and runs(R, nruns) give them."""
+    check_fit_args('fit_cgan', int(num_epochs), int(batch_size), learning_rate)
+    net = TrainableCGAN(regression, nx, div, hidden_channels, seed, generator=generator, ndf=ndf)
+    return _fit('fit_cgan', net, ds_train, ds_test, regression, folder, num_epochs, num_epochs_regression, batch_size, learning_rate,
+                nruns, device, orders, mixes, runs, verbose)
+
+
+def fit_cgan_unet(ds_train, ds_test, *, regression='None', nx=64, div=False, hidden_channels=[128, 64, 32, 32, 32, 32, 32],
+                  folder='model', num_epochs=200, num_epochs_regression=50, batch_size=64, learning_rate=2e-4, nruns=5, seed=0,
+                  device=0, orders=None, mixes=None, runs=None, verbose=True, ndf=64):
+    """fit_cgan for CGANRegression(generator='DeepInversion'): the same loop (train_CGAN), the same folder with generator:
+    'DeepInversion' in model_args.json, and CGANRegression(generator='DeepInversion', folder=folder) read back from the files,
+    with the trained nets attached as fit_cgan attaches them.  The generator is TrainableUNet: its convolutions, their data
+    and weight gradients are the kernels of csrc/uconv_train.hip; BatchNorm, LeakyReLU, pooling and Adam are torch's.  nx is
+    32, 48, 64, 96 or 128; div reaches net_mean alone; hidden_channels is recorded and not used."""
+    check_fit_args('fit_cgan_unet', int(num_epochs), int(batch_size), learning_rate)
+    net = TrainableUNetCGAN(regression, nx, div, hidden_channels, seed, ndf=ndf)
+    return _fit('fit_cgan_unet', net, ds_train, ds_test, regression, folder, num_epochs, num_epochs_regression, batch_size,
+                learning_rate, nruns, device, orders, mixes, runs, verbose)
+
+
 def main(argv=None):
-    return command_line('train CGANRegression on the device and write its model folder', {'CGANRegression': fit_cgan}, argv)
+    return command_line('train CGANRegression on the device and write its model folder',
+                        {'CGANRegression': fit_cgan, 'CGANRegression-Unet': fit_cgan_unet}, argv)
 
 
 if __name__ == '__main__':

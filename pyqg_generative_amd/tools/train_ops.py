@@ -10,6 +10,8 @@ A conditional VAE has ``latent_sample`` between its encoder and its decoder: the
 the variance diagnostics in one call each way, csrc/latent_train.hip; ``latent_prior`` is the same forward without an encoder.
 A GAN's discriminator is made of ``strided_conv2d``, csrc/dconv_train.hip: three Functions whose backwards are each other, so that
 the gradient penalty's second derivative runs on the same three kernels.
+The DeepInversion U-Net generator is made of ``unet_conv2d``, csrc/uconv_train.hip (include/qgx_uconv_train.h): the circular 3 x 3
+and 1 x 1 convolution on any grid down to 2 x 2 with up to 512 -> 1024 channels, differentiable once.
 Every tensor is checked here, once per layout (``_engine``, ``_planar``, ``_rows``), before a pointer reaches the library.
 The nets and loops that use these operations are in tools/train_CNN.py, tools/train_CVAE.py and tools/train_CGAN.py.
 """
@@ -33,7 +35,7 @@ _WORK = {}
 
 
 def workspace(kind, size_call, shape, device):
-    """the workspace of one kind ('conv', 'dconv': one size for the three calls; 'head': the loss partials; 'latent': the partial
+    """the workspace of one kind ('conv', 'dconv', 'uconv': one size for the three calls; 'head': the loss partials; 'latent': the partial
     sums of the KL divergence and the variances) and shape, of
     size_call(*shape, &bytes) bytes, cached per device, stream and shape: calls on one stream run in order, so they may share
     it; calls on different streams may not"""
@@ -158,6 +160,85 @@ def circular_conv2d(x, w, b=None):
     the device with zero pad channels, w (cout, cin, k, k), b (cout) or None -> (B, N, N, c8(cout)).  The data gradient is
     computed only if x requires it (a net's first layer does not)."""
     return _CircularConv2d.apply(x, w, b)
+
+
+UCONV_LAUNCHES = {'forward': 0, 'backward_data': 0, 'backward_weight': 0}  # counted per call of the Function (tests, timing)
+
+
+def _uconv_call(call, ptrs, B, N, cin, cout, k, device):
+    """one call of include/qgx_uconv_train.h with the workspace of the shape"""
+    with torch.cuda.device(device):
+        ws = workspace('uconv', lib.qgx_uconv2d_workspace, (B, N, cin, cout, k), device)
+        check(call(*ptrs, B, N, cin, cout, k, ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()))
+
+
+def uconv2d_forward(x, w, b=None):
+    """y (B, N, N, c8(cout)) = conv_circular(x (B, N, N, c8(cin)), w (cout, cin, k, k)) + b: k 1 or 3, any grid 2 ... 128"""
+    w, cout, cin, k = _weight(w)
+    x, w = _aligned(_engine(x, 'x', cin)), _aligned(w)
+    if b is not None:
+        if not (b.is_cuda and b.dtype == torch.float32 and tuple(b.shape) == (cout,)):
+            raise ValueError(f'bias: a float32 device tensor ({cout},), not {tuple(b.shape)} {b.dtype} on {b.device}')
+        b = _aligned(b.contiguous())
+    B, N = int(x.shape[0]), int(x.shape[1])
+    y = torch.empty((B, N, N, c8(cout)), dtype=torch.float32, device=x.device)
+    _uconv_call(lib.qgx_uconv2d_forward, (x.data_ptr(), w.data_ptr(), _ptr(b), y.data_ptr()), B, N, cin, cout, k, x.device)
+    return y
+
+
+def uconv2d_backward_data(dy, w):
+    """dx (B, N, N, c8(cin)) of dy (B, N, N, c8(cout))"""
+    w, cout, cin, k = _weight(w)
+    dy, w = _aligned(_engine(dy, 'dy', cout)), _aligned(w)
+    B, N = int(dy.shape[0]), int(dy.shape[1])
+    dx = torch.empty((B, N, N, c8(cin)), dtype=torch.float32, device=dy.device)
+    _uconv_call(lib.qgx_uconv2d_backward_data, (dy.data_ptr(), w.data_ptr(), dx.data_ptr()), B, N, cin, cout, k, dy.device)
+    return dx
+
+
+def uconv2d_backward_weight(x, dy, cin, cout, k, bias=True):
+    """dw (cout, cin, k, k) and db (cout) (None without `bias`)"""
+    x, dy = _aligned(_engine(x, 'x', cin)), _aligned(_engine(dy, 'dy', cout))
+    B, N = int(x.shape[0]), int(x.shape[1])
+    if dy.shape[:3] != x.shape[:3] or dy.device != x.device:
+        raise ValueError(f'x {tuple(x.shape)} and dy {tuple(dy.shape)} differ in batch, grid or device')
+    dw = torch.empty((int(cout), int(cin), int(k), int(k)), dtype=torch.float32, device=x.device)
+    db = torch.empty((int(cout),), dtype=torch.float32, device=x.device) if bias else None
+    _uconv_call(lib.qgx_uconv2d_backward_weight, (x.data_ptr(), dy.data_ptr(), dw.data_ptr(), _ptr(db)), B, N, int(cin), int(cout),
+                int(k), x.device)
+    return dw, db
+
+
+class _UnetConv2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = b is not None
+        UCONV_LAUNCHES['forward'] += 1
+        return uconv2d_forward(x, w, b)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            UCONV_LAUNCHES['backward_data'] += 1
+            dx = uconv2d_backward_data(dy, w)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            UCONV_LAUNCHES['backward_weight'] += 1
+            dw, db = uconv2d_backward_weight(x, dy, int(w.shape[1]), int(w.shape[0]), int(w.shape[2]), bias=ctx.has_bias)
+        return dx, dw, db
+
+
+def unet_conv2d(x, w, b=None):
+    """Conv2d(cin, cout, k, padding=k // 2, padding_mode='circular'), k 1 or 3, on the engine layout, differentiable ONCE (a
+    generator needs no second derivative; asking for one raises): x (B, N, N, c8(cin)) float32 on the device with zero pad
+    channels, any grid 2 ... 128, w (cout, cin, k, k) with cin <= 512 and cout <= 1024, b (cout) or None -> (B, N, N, c8(cout)).
+    The layer of the DeepInversion U-Net generator, csrc/uconv_train.hip.  A gradient is computed only where it is asked for:
+    the net's first layer gets no data gradient."""
+    return _UnetConv2d.apply(x, w, b)
 
 
 def _dconv_weight(w):
